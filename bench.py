@@ -130,6 +130,26 @@ def cpu_baseline(d, B, seconds, rows):
                       "gradients materialised like jax.vmap, clip pass, mean, ChaCha20 perturbation, Adam), float32"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 (float32 arrays) or float64 (everything else: integer words are
+    exact in float64), at most `limit` bytes in all.  An array larger than its equal share of `limit` is written as a fixed sample of
+    its flattened elements (seed 0, sorted positions), with the positions in out_dir/<name>_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            k = share // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N rank processes here.  The parent never initialises a
     GPU (counting devices does not), the ranks are fresh interpreters; rank 0 prints the JSON line to the shared stdout."""
@@ -488,7 +508,7 @@ class RunStopped(RuntimeError):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2048)   # whole prepared batches of 128 steps
+    ap.add_argument("--steps", type=int, default=2048, help="timed steps of the headline leg")
     ap.add_argument("--warmup", type=int, default=128)
     ap.add_argument("--rows-per-gpu", type=int, default=1_000_000)
     ap.add_argument("--batch-per-gpu", type=int, default=4096)
@@ -511,7 +531,12 @@ def main():
                          "collective (local cost of the data-parallel step)")
     ap.add_argument("--force-dist-loop", action="store_true",
                     help="developer switch: use the stepwise data-parallel loop (d3p_amd.dist) even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the run, write what the headline leg's last step returned (parameters, Adam moments, step counter, "
+                         "key; the losses of its timed steps) as DIR/<name>.npy; the inputs are fixed, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -807,6 +832,7 @@ def main():
             print(f"[bench] copy peak not measured ({type(e).__name__}: {e})", file=sys.stderr)
 
     aux = {}   # the other BASELINE workloads (single-GPU runs): filled by measure()
+    outputs = {}   # rank 0, --dump-outputs: what the headline leg's last step returned, filled by measure()
     progress = {}   # rank 0: the line's fields as soon as the headline leg of a measure() call is done (the legs behind it fill in)
 
     def measure(native, extra_legs):
@@ -841,6 +867,11 @@ def main():
         state, losses, elapsed, kt = timed_leg(run, state0, 0, args.warmup, args.steps)
         steps_per_s = args.steps / elapsed
         final_loss = float(losses[-1]) if losses is not None else None
+        if args.dump_outputs and rank == 0:   # (after the timed region; the last measure() call is the one the line reports)
+            step, par, m_, v_ = state.optim_state
+            outputs.clear()
+            outputs.update({k: t.detach().cpu().numpy() for k, t in (("params", par), ("adam_m", m_), ("adam_v", v_), ("step", step),
+                                                                      ("rng_key", state.rng_key), ("losses", losses)) if t is not None})
 
         # ---- dominant kernel: the step kernel of the timed region itself, HIP events on the launch stream
         roofline = None
@@ -1086,6 +1117,8 @@ def main():
     cpu = None
     if rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(d, args.batch_per_gpu, args.cpu_seconds, rows=200_000)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         emit(line(m, cpu, extra))
     if torch_only and rank == 0:   # (rank 0 alone, and after its line: a launcher ends the other ranks when one exits non-zero)

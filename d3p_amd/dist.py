@@ -58,8 +58,8 @@ def _runs_beside(a, b, spin_cycles=20_000_000):
 
 
 def concurrent_streams(n):
-    """`n` streams whose kernels run BESIDE each other's and beside the current stream's (n <= 3 unless the process was started with
-    GPU_MAX_HW_QUEUES > 4 in its environment: then up to that many - 1).  A HIP process has 4 hardware
+    """`n` streams whose kernels run BESIDE each other's and beside the current stream's (n <= GPU_MAX_HW_QUEUES - 1 of the process's
+    environment, 3 where it is unset).  A HIP process has 4 hardware
     queues by default (GPU_MAX_HW_QUEUES); further streams share them, and two streams that share a queue are serialised -- every
     fourth stream of torch's pool shares the default stream's (tools/probes/stream_queue_probe.py).  Ranks that live in ONE process
     on separate streams (XchgComm.local_group; d3p_xchg_simulate_peers on a side stream) wait for each other INSIDE their launches:
@@ -67,7 +67,7 @@ def concurrent_streams(n):
     assumed: a spin kernel on one, a small kernel on the other."""
     import os
     try:
-        queues = max(4, int(os.environ.get("GPU_MAX_HW_QUEUES", "4")))
+        queues = max(1, int(os.environ.get("GPU_MAX_HW_QUEUES", "4")))
     except ValueError:
         queues = 4
     if n > queues - 1:

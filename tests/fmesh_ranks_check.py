@@ -8,9 +8,11 @@ oracle/ on rank 0); driven by tests/test_dist.py, never imported by the product.
 
 Process mode: the parent never touches a GPU; it starts WORLD fresh rank processes (gloo carries the IPC handles), one per GPU
 when there are enough GPUs, else all on cuda:0 (the pool's GPU boxes allow at most 6 processes on a card: world <= 4 here).
-Virtual mode: WORLD ranks in one process on streams that run beside each other -- the parent sets GPU_MAX_HW_QUEUES so that the
-process has that many hardware queues -- inboxes wired directly: the many-rank code paths of an 8-GPU job (chunk = ceil(688 886 / 8),
-8 inboxes, 7 peers per poll) that no process-per-rank rehearsal on this pool can reach.
+Virtual mode: WORLD ranks in one process on streams that run beside each other -- the process needs as many hardware queues
+(GPU_MAX_HW_QUEUES of its environment) as ranks, else it skips -- inboxes wired directly: the many-rank code paths of an 8-GPU job
+(chunk = ceil(688 886 / 8), 8 inboxes, 7 peers per poll) that no process-per-rank rehearsal on one GPU can reach.
+Case mode (D3P_FMESH_CHECK_CASE, with D3P_FMESH_CHECK_WORLD processes): a case of tests/test_dist.py whose virtual ranks do not fit
+one process, run one process per rank (case_main).
 
 Checks (exit code 0 = all hold):
  (a) the bare collective on 688 886 floats (and 10 007): on every rank, over five epochs, bit for bit the RANK-ORDER fp32 sum
@@ -222,6 +224,118 @@ def rank_main():
     return 0 if (ok and not stopped) else 1
 
 
+def case_main(case):
+    """One PROCESS per rank for a case of tests/test_dist.py whose virtual ranks do not fit one process (a process has
+    GPU_MAX_HW_QUEUES hardware queues: no more ranks than that run beside each other).  The same checks as the test's in-process
+    form, with the inboxes mapped through hipIpc instead of wired directly:
+      collective-N          the bare collective on N floats (Inf / NaN entries where N > 10), five epochs, bit for bit the rank-order
+                            sum on every rank (test_fmesh_virtual_ranks_sum_in_rank_order_bit_for_bit);
+      vae-B-D-H-Z-H2        three data-parallel VAE steps in the fused and the three-launch form: forms and replicas bitwise equal, the
+                            single-process update-by-update run to fp32 rounding (test_vae_native_loop_over_the_full_mesh_with_virtual_ranks)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from d3p_amd import dist as ddist
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    shared = torch.cuda.device_count() < world
+    torch.cuda.set_device(0 if shared else rank)
+    grid = max(8, 128 // world)      # (ranks that share a GPU: room for each other's kernels)
+    kind, *shape = case.split("-")
+    shape = [int(v) for v in shape]
+    ok, stopped = True, False
+    if kind == "collective":
+        (n,) = shape
+        comm = ddist.FMeshComm(n)
+        if shared:
+            comm.set_grid(grid)
+        try:
+            vecs = [torch.randn(n, generator=torch.Generator().manual_seed(1000 * n + r)) for r in range(world)]
+            if n > 10:
+                vecs[0][3] = float("inf")
+                vecs[world - 1][7] = float("nan")
+            for e in range(5):
+                scaled = [v * float(e + 1) for v in vecs]
+                want = _rank_order_sum(scaled)
+                work = scaled[rank].cuda()
+                torch.cuda.synchronize()
+                dist.barrier()
+                comm.allreduce(work)
+                torch.cuda.synchronize()
+                stopped |= comm.stopped()
+                got = work.cpu()
+                fin = ~torch.isnan(want)
+                good = bool(torch.equal(torch.isnan(got), torch.isnan(want)) and torch.equal(got[fin].view(torch.int32), want[fin].view(torch.int32)))
+                if not good:
+                    print(f"rank {rank}: n = {n}, epoch {e}: the sum differs from the rank-order sum", file=sys.stderr, flush=True)
+                ok &= good
+        finally:
+            comm.close(collective=sys.exc_info()[0] is None)
+    elif kind == "vae":
+        import d3p_amd.random as rng
+        from d3p_amd.models import Adam, Trace_ELBO, VAEGuide, VAEModel
+        from d3p_amd.svi import DPSVI
+        B, Dv, Hv, Zv, H2 = shape
+        N, steps = 60000, 3
+        model = VAEModel(z_dim=Zv, hidden_dim=(Hv, H2) if H2 else Hv, scale=1.0 / N)
+
+        def make():
+            return DPSVI(model, VAEGuide(model), Adam(1e-2), Trace_ELBO(), 3.0, 0.8, num_obs_total=N)
+        X = torch.tensor((np.random.default_rng(37).random((B, Dv)) < 0.4).astype(np.float32)).cuda()
+        st0 = make().init(rng.PRNGKey(87), X)
+        comm = ddist.FMeshComm(int(st0.optim_state[1].numel()) + 2)
+        if shared:
+            comm.set_grid(grid)
+        try:
+            pos0, bl = ddist.shard_batch(B, rank, world)
+            runs = {}
+            for form, buckets in (("fused", 0), ("three launches", 1)):
+                dist.barrier()
+                runs[form] = ddist.vae_run_steps(ddist.VaeHipEngine(make()), st0, X[pos0:pos0 + bl], B, pos0, steps, comm=comm, buckets=buckets,
+                                                 check_status=False)
+                torch.cuda.synchronize()
+                stopped |= comm.stopped()
+            (sa, la), (sb, lb) = runs["fused"], runs["three launches"]
+            same_forms = torch.equal(la, lb) and torch.equal(sa.rng_key, sb.rng_key) and all(torch.equal(a, b) for a, b in zip(sa.optim_state, sb.optim_state))
+            if not same_forms:
+                print(f"rank {rank}: the fused step and the three-launch step differ", file=sys.stderr, flush=True)
+            ok &= bool(same_forms)
+            res = [None] * world
+            dist.all_gather_object(res, tuple(t.cpu().numpy().tobytes() for t in (la, sa.rng_key) + tuple(sa.optim_state)))
+            bitwise = all(r == res[0] for r in res[1:])
+            if not bitwise:
+                print(f"rank {rank}: replicas differ", file=sys.stderr, flush=True)
+            ok &= bitwise and int(sa.optim_state[0]) == steps
+            if rank == 0 and not stopped:
+                svi, ref, ref_l = make(), st0, []
+                for _ in range(steps):
+                    ref, l = svi.update(ref, X)
+                    ref_l.append(float(l))
+                good = torch.equal(sa.rng_key, ref.rng_key)
+                good &= np.allclose(la.cpu().numpy(), np.asarray(ref_l, np.float32), rtol=2e-5, atol=0)
+                mr = ref.optim_state[2].cpu().numpy()
+                good &= np.allclose(sa.optim_state[2].cpu().numpy(), mr, rtol=2e-4, atol=2e-5 * np.abs(mr).max())
+                if not good:
+                    print("rank 0: the data-parallel run differs from the single-process run", file=sys.stderr, flush=True)
+                ok &= bool(good)
+        finally:
+            comm.close(collective=sys.exc_info()[0] is None)
+    else:
+        raise SystemExit(f"fmesh_ranks_check: unknown case {case!r}")
+    flags = [None] * world
+    dist.all_gather_object(flags, (bool(ok), bool(stopped)))
+    ok = all(f[0] for f in flags)
+    stopped = any(f[1] for f in flags)
+    if stopped:
+        print(f"rank {rank}: stopped -- a bounded wait of the full-mesh all-reduce ran out", file=sys.stderr, flush=True)
+    if rank == 0:
+        print(json.dumps({"fmesh_ranks_check": "ok" if (ok and not stopped) else ("STOPPED" if stopped else "MISMATCH"),
+                          "mode": "processes", "case": case, "world": world, "devices": torch.cuda.device_count()}), flush=True)
+    dist.destroy_process_group()
+    return 0 if (ok and not stopped) else 1
+
+
 def virtual_main(world):
     """`world` ranks in THIS process, one stream each."""
     sys.path.insert(0, ROOT)
@@ -232,7 +346,7 @@ def virtual_main(world):
     b_local = int(os.environ.get("D3P_FMESH_CHECK_B_LOCAL", "512"))
     L.require_device()
     try:
-        streams = ddist.concurrent_streams(world)
+        streams = [torch.cuda.current_stream()] + ddist.concurrent_streams(world - 1)
     except L.D3PError as e:
         print(json.dumps({"fmesh_ranks_check": "SKIPPED", "mode": "virtual", "world": world, "why": str(e)}), flush=True)
         return 77
@@ -318,14 +432,13 @@ def virtual_main(world):
 
 def main():
     if "RANK" in os.environ:
-        sys.exit(rank_main())
+        sys.exit(case_main(os.environ["D3P_FMESH_CHECK_CASE"]) if os.environ.get("D3P_FMESH_CHECK_CASE") else rank_main())
     if os.environ.get("D3P_FMESH_CHECK_VIRTUAL_CHILD"):
         sys.exit(virtual_main(int(os.environ["D3P_FMESH_CHECK_VIRTUAL_CHILD"])))
     virtual = int(os.environ.get("D3P_FMESH_CHECK_VIRTUAL", "0"))
     if virtual:
-        # a fresh process whose HIP runtime starts with enough hardware queues for `virtual` streams beside the default one
+        # a fresh process with the hardware queues of its environment (GPU_MAX_HW_QUEUES): it skips where they are fewer than the ranks
         env = dict(os.environ, D3P_FMESH_CHECK_VIRTUAL_CHILD=str(virtual))
-        env.setdefault("GPU_MAX_HW_QUEUES", str(virtual + 2))
         sys.exit(subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, timeout=900).returncode)
     world = int(os.environ.get("D3P_FMESH_CHECK_WORLD", "4"))
     assert 2 <= world <= 6, "at most 6 processes may use one GPU on this pool"

@@ -200,7 +200,7 @@ model = LogisticRegression(d)
 svi = DPSVI(model, AutoDiagonalNormal(model), Adam(1e-2), Trace_ELBO(), 1.0, 0.7, N=N)
 st0 = DPSVIState(svi.optim.init(torch.cat([torch.zeros(d), torch.full((d,), -2.0)]).cuda()), rng.PRNGKey(21), float(N))
 comms = ddist.XchgComm.local_group(world, 2 * d + 4)
-streams = ddist.concurrent_streams(world)
+streams = [torch.cuda.current_stream()] + ddist.concurrent_streams(world - 1)   # (rank 0 on the current stream)
 engines, results = [], []
 for r in range(world):
     lo, hi = ddist.shard_rows(N, r, world)

@@ -10,7 +10,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libd3p_hip.so")
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_vae.hip", "d3p_fmesh.hip")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
@@ -37,6 +37,16 @@ class GmmModel(C.Structure):
 class VaeModel(C.Structure):
     _fields_ = [("D", C.c_int32), ("H", C.c_int32), ("Z", C.c_int32), ("scale", C.c_float), ("inv_obs", C.c_float),
                 ("H2", C.c_int32)]   # H2 > 0: a second hidden layer on each side (BASELINE config 5's [400, 200] variant)
+
+
+class PredictSite(C.Structure):
+    """d3p_predict_site (include/d3p_hip.h): one latent sample site of the predictive draws."""
+    _fields_ = [("size", C.c_int32), ("offset", C.c_int32), ("chain", C.c_int32), ("key_index", C.c_int32),
+                ("scale_kind", C.c_int32), ("loc_c", C.c_float), ("scale_c", C.c_float), ("loc_dev", C.c_void_p),
+                ("scale_dev", C.c_void_p), ("value_dev", C.c_void_p)]
+
+
+D3P_PREDICT_SCALE_CONST, D3P_PREDICT_SCALE_GIVEN, D3P_PREDICT_SCALE_EXP = 0, 1, 2
 
 
 class DpsviHyper(C.Structure):
@@ -237,6 +247,11 @@ SIGNATURES = {
     "d3p_dpvi_leaves_finalize": (C.c_int, [_V, _PH, _V, _V, _V, C.POINTER(C.c_int32), _I32, _U32, C.c_float,
                                            _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "d3p_px_eps_sites": (C.c_int, [_V, _V, _U32, _U32, _U32, C.POINTER(C.c_int32), _I32, _V]),
+    "d3p_predict_draws": (C.c_int, [_V, _V, _U32, _I32, _I32, C.POINTER(PredictSite), _I32, _I32, _I32, _V, C.c_int64, _V]),
+    "d3p_predict_logreg": (C.c_int, [_V, _V, _U64, _I32, _V, C.c_int64, _I32, _I32, _U32, _V, _V]),
+    "d3p_predict_gauss": (C.c_int, [_V, _V, C.c_int64, _I32, _U64, _U32, _F, _V, _V]),
+    "d3p_predict_vae_workspace": (_SZ, [_V, _U32, _U32]),
+    "d3p_predict_vae": (C.c_int, [_V, _V, _V, _V, _U32, _V, _U32, _I32, _V, _V, _V, _V, _SZ]),
 }
 
 _lib = None

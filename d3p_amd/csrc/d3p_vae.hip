@@ -2391,6 +2391,49 @@ static int vae_enqueue_sums(hipStream_t s, const d3p_vae_model* m, const float* 
     return check_launch("d3p_vae sums");
 }
 
+// ---- predictive sampling (d3p_predict.hip): the guide's encoder and the model's decoder as plain forward passes through the
+// product kernels above (softplus layers: epilogue 1, its sigmoid output to `sg`, unused); no split-K.
+// encoder: zl = h Wl + bl, zs = h Ws + bs (the log of the guide's z_std, examples/vae.py:86) over the B rows of X
+int vae_predict_encode(hipStream_t s, const d3p_vae_model* m, const float* params, const float* X, uint32_t B, float* zl, float* zs, float* h0, float* h1,
+                       float* sg)
+{
+    const VaeNet N = vae_net(m);
+    const int Bi = (int)B, Z = N.Z, HE = N.HE;
+    const float* in = X;
+    float* bufs[2] = {h0, h1};
+    for (int l = 0; l < N.nh; ++l) {
+        const VaeDense& e = N.enc[l];
+        GemmOpts o;
+        o.epi = 1; o.C2 = sg;
+        if (int rc = gemm(s, in, e.in, 1, params + e.W, e.out, 1, bufs[l], e.out, Bi, e.out, e.in, params + e.b, 1.f, 0, o)) return rc;
+        in = bufs[l];
+    }
+    if (int rc = gemm(s, in, HE, 1, params + N.Wl, Z, 1, zl, Z, Bi, Z, HE, params + N.bl, 1.f, 0)) return rc;
+    return gemm(s, in, HE, 1, params + N.Ws, Z, 1, zs, Z, Bi, Z, HE, params + N.bs, 1.f, 0);
+}
+
+// decoder: logits = the output layer's pre-activation (rows x D) for the rows of z (rows x Z); the model's sigmoid is applied by the
+// Bernoulli draw that reads them
+int vae_predict_decode(hipStream_t s, const d3p_vae_model* m, const float* params, const float* z, uint32_t rows, float* logits, float* h0, float* h1,
+                       float* sg)
+{
+    const VaeNet N = vae_net(m);
+    const int R = (int)rows;
+    const float* in = z;
+    int ld_in = N.Z;
+    float* bufs[2] = {h0, h1};
+    for (int l = 0; l < N.nh; ++l) {
+        const VaeDense& d = N.dec[l];
+        GemmOpts o;
+        o.epi = 1; o.C2 = sg;
+        if (int rc = gemm(s, in, ld_in, 1, params + d.W, d.out, 1, bufs[l], d.out, R, d.out, d.in, params + d.b, 1.f, 0, o)) return rc;
+        in = bufs[l];
+        ld_in = d.out;
+    }
+    const VaeDense& o = N.dec[N.nh];
+    return gemm(s, in, ld_in, 1, params + o.W, o.out, 1, logits, o.out, R, o.out, o.in, params + o.b, 1.f, 0);
+}
+
 }  // namespace d3p
 
 using namespace d3p;

@@ -34,6 +34,13 @@ def create_toy_data(N, d, seed=123):
     return (X[:N].contiguous(), y[:N].contiguous()), (X[N:].contiguous(), y[N:].contiguous())
 
 
+def estimate_accuracy(X, y, model, guide, params, rng, num_iterations=100):
+    """Reference :110-116: the mean agreement of `num_iterations` posterior-predictive draws of the test labels with the labels."""
+    from d3p_amd.modelling import sample_multi_posterior_predictive
+    samples = sample_multi_posterior_predictive(rng, num_iterations, model, (X,), guide, (X,), params)
+    return float((samples["obs"] == y.to(torch.int32)).float().mean())
+
+
 def main(args):
     L.require_device()
     train, test = create_toy_data(args.num_samples, args.dimensions)
@@ -85,6 +92,10 @@ def main(args):
         train_losses.append(train_loss)
         print("Epoch {}: loss = {:.4f}, acc = {:.4f} (loss on training set: {:.4f}) ({:.3f} s.)".format(
             i, test_loss, acc, train_loss, t1 - t0))
+    if getattr(args, "predictive_accuracy", False):   # reference :230 (its posterior half)
+        import d3p_amd.random.debug as jax_random
+        acc_post = estimate_accuracy(test[0], test[1], model, guide, svi.get_params(svi_state), jax_random.PRNGKey(1), 100)
+        print("avg accuracy on test set with found posterior (100 posterior-predictive draws): {:.4f}".format(acc_post))
     return accs, train_losses
 
 
@@ -99,4 +110,6 @@ if __name__ == "__main__":
     parser.add_argument('-N', '--num-samples', default=10000, type=int, help='data samples count')
     parser.add_argument('--guide', choices=["auto", "handwritten"], default="auto",
                         help="auto: AutoDiagonalNormal (README.md:99); handwritten: the reference script's own two-site guide (:67-86)")
+    parser.add_argument('--predictive-accuracy', action='store_true',
+                        help="after training, print the test accuracy of 100 posterior-predictive draws (reference :110-116, :230)")
     main(parser.parse_args())

@@ -723,6 +723,44 @@ int d3p_logreg_evaluate_sites(void* stream, const d3p_logreg_model* model, const
  * a device-to-device copy peak on the box"), 8 or 4 (to calibrate the FETCH_SIZE / WRITE_SIZE counters per access width). */
 int d3p_hbm_copy(void* stream, void* dst_dev, const void* src_dev, uint64_t bytes, int32_t bytes_per_lane);
 
+/* ABI 9 additions -- prior and posterior predictive sampling (d3p/modelling.py:39-223; d3p_amd/modelling.py).  The key plumbing
+ * restates numpyro / jax (UNPINNED): draw i of n runs on split(key, n)[i] (multi) or on key itself;
+ * posterior: model_key, guide_key = split(draw key); every sample statement that takes a key advances its handler's
+ * `rng, site_key = split(rng)`.  Keys are threefry (jax) keys: two uint32 words in device memory. */
+#define D3P_PREDICT_SCALE_CONST 0   /* Normal(loc_c, scale_c) (a prior) */
+#define D3P_PREDICT_SCALE_GIVEN 1   /* scale_dev as given (AutoDiagonalNormal's auto_scale, already constrained) */
+#define D3P_PREDICT_SCALE_EXP 2     /* exp(scale_dev) (the hand-written guides' *_std_log, the VAE encoder's log-scale head) */
+typedef struct {
+    int32_t size;         /* elements of the site (a scalar site: 1) */
+    int32_t offset;       /* column of its first element in a row of latent_dev */
+    int32_t chain;        /* 0: the model's seed handler, 1: the guide's (posterior only) */
+    int32_t key_index;    /* how many key-taking sample statements precede it under that handler; -1: substituted */
+    int32_t scale_kind;   /* D3P_PREDICT_SCALE_* */
+    float loc_c, scale_c; /* used where loc_dev / scale_dev are NULL */
+    const float* loc_dev;     /* nullable: size elements */
+    const float* scale_dev;   /* nullable: size elements */
+    const float* value_dev;   /* key_index -1: the substituted value (size elements, the same for every draw) */
+} d3p_predict_site;
+
+/* latent_dev[i, offset + e] = loc[e] + normal(site key, (size,))[e] * scale[e] for draw i < n and every site (or the substituted
+ * value); obs_keys_dev (nullable): obs_keys[i] = the key of the observation site, key index obs_index under handler obs_chain. */
+int d3p_predict_draws(void* stream, const uint32_t* key_dev, uint32_t n, int32_t multi, int32_t posterior, const d3p_predict_site* sites_host,
+                      int32_t n_sites, int32_t obs_chain, int32_t obs_index, float* latent_dev, int64_t latent_ld, uint32_t* obs_keys_dev);
+/* logistic regression (fused): obs_dev[s, r] = uniform(obs_keys[s], (rows,))[r] < sigmoid(X[r] . latent[s, w_off .. w_off + d) + latent[s, b_col])
+ * as int32 (b_col = -1: no intercept), X row-major rows x d; the logits and uniforms never reach memory. */
+int d3p_predict_logreg(void* stream, const float* X_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld, int32_t w_off,
+                       int32_t b_col, uint32_t n, const uint32_t* obs_keys_dev, int32_t* obs_dev);
+/* Gaussian mean: obs_dev[i, r, c] = mu[i, c] + normal(obs_keys[i], (rows, d))[r d + c] * obs_scale */
+int d3p_predict_gauss(void* stream, const float* mu_dev, int64_t mu_ld, int32_t d, uint64_t rows, uint32_t n, float obs_scale,
+                      const uint32_t* obs_keys_dev, float* obs_dev);
+/* VAE (examples/vae.py:65-153): X_dev != NULL -> posterior (encoder over the B images once, z_i ~ Normal(z_loc, exp(z_log_std)) per draw),
+ * NULL -> prior (z_i ~ Normal(0, 1), or z_subst_dev (B x Z) for every draw); then the decoder over the n B rows and
+ * obs = uniform(obs key, (B, D)) < decoder output.  params_dev: the flat VAE parameter vector (d3p_vae_model's layout; the prior
+ * reads the decoder part only).  z_dev: n x B x Z floats, obs_dev: n x B x D int32. */
+size_t d3p_predict_vae_workspace(const d3p_vae_model* model, uint32_t B, uint32_t n);
+int d3p_predict_vae(void* stream, const d3p_vae_model* model, const float* params_dev, const float* X_dev, uint32_t B, const uint32_t* key_dev,
+                    uint32_t n, int32_t multi, const float* z_subst_dev, float* z_dev, int32_t* obs_dev, void* workspace_dev, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

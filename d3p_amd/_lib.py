@@ -137,6 +137,7 @@ SIGNATURES = {
     "d3p_last_error": (C.c_char_p, []),
     "d3p_device_count": (C.c_int, []),
     "d3p_rng_split": (C.c_int, [_V, _V, C.c_int, _V]),
+    "d3p_key_chain_host": (C.c_int, [_V, C.c_int, _V]),
     "d3p_rng_fold_in": (C.c_int, [_V, _V, _U32, _V]),
     "d3p_rng_random_bits": (C.c_int, [_V, _V, C.c_int, _U64, _V]),
     "d3p_rng_uniform": (C.c_int, [_V, _V, _U64, _F, _F, _V]),

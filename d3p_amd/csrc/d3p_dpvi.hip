@@ -163,11 +163,12 @@ __global__ void __launch_bounds__(64) k_chain(Sched* __restrict__ sched, StepSlo
 // 20-step run spent ~180 of its 350 us outside the step kernel).
 // k_run_init (1 workgroup): wave 0 walks the serial key chain of the first batch -- split(key, 3) per step with the 4-lane
 //   ChaCha block, three children in three quads (0.7 us per step instead of 1.9 for the one-lane form of k_chain) -- starting
-//   from the state's key and counters; the other waves zero the fixed-point accumulators and the run's status words.
+//   from the state's key and counters -- or takes the first links from its arguments when the host derived them from the state's
+//   key (RunInitLinks); the other 15 waves zero the fixed-point accumulators and the run's status words.
 //   Replaces k_sched_init + k_chain + two memsets (and k_pack, which only the two-kernel path reads).
 // k_flush (1 workgroup): applies the update that is still pending after the last step (the arithmetic of the step kernels'
 //   prologue), leaves the state in the caller's arrays, stores the final key of the schedule into the state's other key slot
-//   and copies the run's status words to pinned host memory.  Replaces the flush launch of the step kernel + k_sched_finish
+//   and copies the run's status words and its final key to pinned host memory.  Replaces the flush launch of the step kernel + k_sched_finish
 //   + the device-to-host copy of d3p_dpvi_logreg_run_status.
 // ------------------------------------------------------------------------------------------
 struct RunInitCopy {  // d3p_dpvi_logreg_run_from: the optimiser state is copied from `src` into the run's arrays here
@@ -187,20 +188,35 @@ struct RunInitCopy {  // d3p_dpvi_logreg_run_from: the optimiser state is copied
     uint32_t ll_tag, ll_cols;   // cols = D3P_ACC_COLS(P): the row stride of ll[0]
 };
 
-__global__ void __launch_bounds__(256) k_run_init(const uint32_t* __restrict__ state_key, const int32_t* __restrict__ adam_step,
+// The first links of the key chain, derived on the host (host_key_chain) from the key the workspace's previous run ended with (its
+// pinned record): a run usually continues from that key.  k_run_init takes them only if the state's key IS `parent`, word for word;
+// otherwise it walks the chain as before.  The host record only decides how often the links are used, never what a run computes.
+#define D3P_HOST_LINKS 32
+struct RunInitLinks {
+    uint32_t n;                        // links prepared (0: none)
+    uint32_t parent[16];               // the key they were derived from
+    uint32_t after[8];                 // words 4..11 of the key after link n - 1 (words 0..3 are parent's, 12..15 are zero)
+    uint32_t gp[D3P_HOST_LINKS][16];   // link t: words 4..11 of split(., 3)[1] (gradient key), then of split(., 3)[2] (perturbation key)
+};
+
+__global__ void __launch_bounds__(1024) k_run_init(const uint32_t* __restrict__ state_key, const int32_t* __restrict__ adam_step,
                                                   const uint32_t* __restrict__ batch_index, Sched* __restrict__ sched,
                                                   StepSlot* __restrict__ slots, int K, long long* __restrict__ acc, uint32_t acc_words,
-                                                  uint32_t* __restrict__ status, RunInitCopy cp)
+                                                  uint32_t* __restrict__ status, RunInitCopy cp, RunInitLinks lk)
 {
     const int tid = threadIdx.x;
-    if (tid >= 64) {  // waves 1..3: zero the accumulators (3 x R x cols int64) and the status words; copy the state if asked to
-        for (uint32_t i = tid - 64; i < acc_words; i += 192) acc[i] = 0;
+    if (tid >= 64) {  // waves 1..15: zero the accumulators (3 x R x cols int64) and the status words; copy the state if asked to
+        // (with the key chain's links from the host the launch is as long as this part: 16-byte stores over 15 waves.  acc_words is
+        // even -- 3 x R x cols with R = 4 -- and the accumulators start 256-byte aligned.)
+        const uint32_t nth = blockDim.x - 64;
+        d3p_u32x4* acc4 = reinterpret_cast<d3p_u32x4*>(acc);
+        for (uint32_t i = tid - 64; i < acc_words / 2; i += nth) acc4[i] = d3p_u32x4{0u, 0u, 0u, 0u};
         if (tid < 64 + 16) status[tid - 64] = 0u;
         if (cp.bar)
-            for (uint32_t i = tid - 64; i < cp.bar_words; i += 192) cp.bar[i] = 0u;
+            for (uint32_t i = tid - 64; i < cp.bar_words; i += nth) cp.bar[i] = 0u;
         if (cp.dst[0]) {
             for (int j = 0; j < 3; ++j)
-                for (int i = tid - 64; i < cp.n; i += 192) cp.dst[j][i] = cp.src[j][i];
+                for (int i = tid - 64; i < cp.n; i += (int)nth) cp.dst[j][i] = cp.src[j][i];
             if (tid == 64) {
                 *cp.step_dst = *adam_step;
                 if (cp.by_value) *cp.batch_index_dst = cp.batch0;
@@ -208,7 +224,7 @@ __global__ void __launch_bounds__(256) k_run_init(const uint32_t* __restrict__ s
         }
         if (cp.ll[0]) {
             const unsigned long long t = (unsigned long long)cp.ll_tag << 32, told = (unsigned long long)(cp.ll_tag - 1u) << 32;
-            for (uint32_t i = tid - 64; i < cp.ll_cols; i += 192) {
+            for (uint32_t i = tid - 64; i < cp.ll_cols; i += nth) {
                 const bool par = i < (uint32_t)cp.n;
                 cp.ll[0][(size_t)(cp.ll_tag & 1u) * cp.ll_cols + i] = t | (par ? __float_as_uint(cp.ll_src[0][i]) : 0u);
                 cp.ll[0][(size_t)((cp.ll_tag & 1u) ^ 1u) * cp.ll_cols + i] = told;
@@ -223,7 +239,29 @@ __global__ void __launch_bounds__(256) k_run_init(const uint32_t* __restrict__ s
     const uint32_t batch0 = cp.by_value ? cp.batch0 : (batch_index ? *batch_index : 0u);
     const uint32_t p0 = state_key[q];
     uint32_t p1 = state_key[4 + q], p2 = state_key[8 + q], p3 = state_key[12 + q];
-    for (int t = 0; t < K; ++t) {
+    int t0 = 0;
+    const int n = lk.n < (uint32_t)K ? (int)lk.n : K;
+    if (n > 0 && __all(lane >= 4 || (p0 == lk.parent[q] && p1 == lk.parent[4 + q] && p2 == lk.parent[8 + q] && p3 == lk.parent[12 + q]))) {
+        // hit: the state's key is the one the host derived the links from -- the slots take them as they are (word w of child 1 / 2
+        // of link t: parent word w below 4, block word w - 4 up to 11, zero above)
+        for (int i = lane; i < n * 8; i += 64) {  // item i: words 4 (i & 3) .. +3 of child 1 + ((i >> 2) & 1) of link i >> 3
+            const int t = i >> 3, r = i & 3;
+            const bool pert = (i & 4) != 0;
+            uint32_t* dst = (pert ? slots[t].pert_key : slots[t].grad_key) + 4 * r;
+            const uint32_t* src = (r == 0 || r == 3) ? lk.parent : lk.gp[t] + (pert ? 8 : 0) + 4 * (r - 1);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) dst[w] = r == 3 ? 0u : src[w];
+        }
+        for (int t = lane; t < n; t += 64) {
+            slots[t].adam_i = adam0 + t;
+            slots[t].batch_i = batch0 + (uint32_t)t;
+        }
+        t0 = n;
+        p1 = lk.after[q];
+        p2 = lk.after[4 + q];
+        p3 = 0u;
+    }
+    for (int t = t0; t < K; ++t) {  // (the links the host did not prepare: all of them on a miss)
         uint32_t a, b;
         derive_child_quad_regs(p0, p1, p2, p3, (uint32_t)child, D3P_TAG_SPLIT, 0u, a, b);
         if (lane >= 4 && lane < 12) {  // gradient key (child 1), perturbation key (child 2)
@@ -267,7 +305,7 @@ struct FlushArgs {
     const Sched* sched;
     uint32_t* key_out;          // the state's key slot after the run
     const uint32_t* status;
-    unsigned long long* host_status;  // nullable: pinned host record {abort, nonfinite, tag}
+    unsigned long long* host_status;  // nullable: pinned host record {abort, nonfinite, tag} + the final key (StatusSlots)
     unsigned long long host_tag;
     int dbg_print;
     int P, B;
@@ -283,6 +321,15 @@ __global__ void __launch_bounds__(1024) k_flush(FlushArgs a)
 {
     const int tid = threadIdx.x, PA = D3P_ACC_COLS(a.P);
     if (tid < 16) a.key_out[tid] = a.sched->key[tid];
+    if (tid >= 1 && tid <= 4 && a.host_status) {  // words 0..11 of the final key, three per 16-byte store, each store tagged
+        const int j = 3 * (tid - 1);
+        d3p_u32x4 rec;
+        rec.x = a.sched->key[j];
+        rec.y = a.sched->key[j + 1];
+        rec.z = a.sched->key[j + 2];
+        rec.w = (uint32_t)a.host_tag;
+        *reinterpret_cast<d3p_u32x4*>(a.host_status + 2 * tid) = rec;
+    }
     const uint32_t aborted = a.status[0];
     if (tid == 0 && aborted && a.dbg_print) {  // D3P_DBG=64: where the waits of the stopped launch stood
         printf("[d3p] run stopped, code %#x; earliest step a wait ran out at, by kind:", aborted);
@@ -377,11 +424,13 @@ __global__ void __launch_bounds__(1024) k_flush(FlushArgs a)
 // number, so a record is only ever read as the result of the LAST flush enqueued for that workspace: not a record of an earlier run
 // (a run form that ends without k_flush invalidates the slot and the reader copies the device words), not one of a workspace that
 // lived at the same address before.
+// Behind the status words the record carries words 0..11 of the run's final key (12..15 of a derived key are zero) in four more
+// 16-byte stores {3 key words, low half of the tag}: status_slot_key hands them to the next run's host key chain.
 struct StatusSlots {
-    static constexpr int N = 256;
+    static constexpr int N = 256, W = 10;  // W: 8-byte words per record (80 bytes)
     struct Entry { int slot; unsigned long long seq; bool valid; };
     std::mutex mu;
-    unsigned long long* table = nullptr;   // N x 2 words {abort | nonfinite << 32, tag}
+    unsigned long long* table = nullptr;   // N x W words {abort | nonfinite << 32, tag, 4 x {key words, tag & 0xffffffff}}
     bool tried = false;
     unsigned long long seq = 0;
     int next = 0;
@@ -392,8 +441,8 @@ struct StatusSlots {
         if (!tried) {
             tried = true;
             void* q = nullptr;
-            if (hipHostMalloc(&q, (size_t)N * 16, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); q = nullptr; }
-            if (q) memset(q, 0, (size_t)N * 16);
+            if (hipHostMalloc(&q, (size_t)N * W * 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); q = nullptr; }
+            if (q) memset(q, 0, (size_t)N * W * 8);
             table = (unsigned long long*)q;
         }
         return table;
@@ -421,7 +470,7 @@ static unsigned long long* status_slot_claim(const uint32_t* status_words, unsig
     it->second.seq = ++S.seq;
     it->second.valid = true;
     *tag_out = it->second.seq;
-    return t + 2 * (size_t)it->second.slot;
+    return t + StatusSlots::W * (size_t)it->second.slot;
 }
 
 // a run form that ends without k_flush: whatever the slot holds is not this run's
@@ -440,13 +489,102 @@ static bool status_slot_read(const uint32_t* status_words, uint32_t* aborted, ui
     std::lock_guard<std::mutex> lk(S.mu);
     auto it = S.by_ws.find((uintptr_t)status_words);
     if (it == S.by_ws.end() || !it->second.valid || !S.table) return false;
-    const volatile unsigned long long* rec = S.table + 2 * (size_t)it->second.slot;
+    const volatile unsigned long long* rec = S.table + StatusSlots::W * (size_t)it->second.slot;
     const unsigned long long w0 = rec[0], w1 = rec[1];
     if (w1 != it->second.seq) return false;
     *aborted = (uint32_t)w0;
     *nonfinite = (uint32_t)(w0 >> 32);
     return true;
 }
+
+// without synchronising, before the workspace's next run is enqueued: the final key of its last run, if that run's flush has
+// already reported it (every store of the record carries the tag of the workspace's last claim).  A torn or stale key is harmless
+// (k_run_init compares it with the state's key); a missing one only means the chain is walked on the device.
+static bool status_slot_key(const uint32_t* status_words, uint32_t key[16])
+{
+    StatusSlots& S = status_slots();
+    std::lock_guard<std::mutex> lk(S.mu);
+    auto it = S.by_ws.find((uintptr_t)status_words);
+    if (it == S.by_ws.end() || !it->second.valid || !S.table) return false;
+    const volatile unsigned long long* rec = S.table + StatusSlots::W * (size_t)it->second.slot;
+    const unsigned long long seq = it->second.seq;
+    if (rec[1] != seq) return false;
+    for (int j = 0; j < 4; ++j) {
+        const unsigned long long lo = rec[2 + 2 * j], hi = rec[3 + 2 * j];
+        if ((uint32_t)(hi >> 32) != (uint32_t)seq) return false;
+        key[3 * j] = (uint32_t)lo;
+        key[3 * j + 1] = (uint32_t)(lo >> 32);
+        key[3 * j + 2] = (uint32_t)hi;
+    }
+    key[12] = key[13] = key[14] = key[15] = 0u;
+    return true;
+}
+
+// The key chain on the host (the same derivation as k_run_init's: split(key, 3) per link, child c = words 0..7 of the ChaCha20 block
+// of the parent with layout_child_tweak(c, 0, D3P_TAG_SPLIT) applied).  Each block is held as its four rows in 4 x 32-bit vectors
+// (the diagonal rounds rotate rows 1..3 by one, two, three words), and the three blocks of a link -- independent of each other --
+// are interleaved round by round, so a link costs about one block's latency: 12 vector registers, no spills.
+// out[t]: words 4..11 of child 1, then of child 2 (or NULL); full[t]: the three children (or NULL); after8: words 4..11 of the key
+// after link n - 1 (words 0..3 stay the parent's, 12..15 become zero).
+typedef uint32_t d3p_hv4 __attribute__((vector_size(16)));
+static inline d3p_hv4 hrotl(d3p_hv4 x, int r) { return (x << r) | (x >> (32 - r)); }
+#define D3P_HQR(a, b, c, d)                   \
+    a += b; d ^= a; d = hrotl(d, 16);         \
+    c += d; b ^= c; b = hrotl(b, 12);         \
+    a += b; d ^= a; d = hrotl(d, 8);          \
+    c += d; b ^= c; b = hrotl(b, 7);
+#define D3P_HROT(v, k) v = __builtin_shufflevector(v, v, (k) & 3, ((k) + 1) & 3, ((k) + 2) & 3, ((k) + 3) & 3)
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+// (AVX-512VL rotates a vector in one instruction -- SSE2 needs three: 0.13 against 0.20 us per link on a Xeon host)
+__attribute__((target_clones("avx512vl", "default")))
+#endif
+static void host_key_chain(const uint32_t parent[16], int n, uint32_t (*out)[16], uint32_t (*full)[3][16], uint32_t after8[8])
+{
+    const d3p_hv4 r0 = {parent[0], parent[1], parent[2], parent[3]};
+    d3p_hv4 r1 = {parent[4], parent[5], parent[6], parent[7]}, r2 = {parent[8], parent[9], parent[10], parent[11]};
+    d3p_hv4 r3 = {parent[12], parent[13], parent[14], parent[15]};
+    for (int t = 0; t < n; ++t) {
+        // layout_child_tweak: counter + child, nonce[2] ^ tag
+        const d3p_hv4 d0 = r3 ^ (d3p_hv4){0u, 0u, 0u, D3P_TAG_SPLIT};
+        const d3p_hv4 d1 = d0 + (d3p_hv4){1u, 0u, 0u, 0u}, d2 = d0 + (d3p_hv4){2u, 0u, 0u, 0u};
+        d3p_hv4 a0 = r0, b0 = r1, c0 = r2, e0 = d0;
+        d3p_hv4 a1 = r0, b1 = r1, c1 = r2, e1 = d1;
+        d3p_hv4 a2 = r0, b2 = r1, c2 = r2, e2 = d2;
+        for (int i = 0; i < 10; ++i) {
+            D3P_HQR(a0, b0, c0, e0) D3P_HQR(a1, b1, c1, e1) D3P_HQR(a2, b2, c2, e2)
+            D3P_HROT(b0, 1); D3P_HROT(c0, 2); D3P_HROT(e0, 3);
+            D3P_HROT(b1, 1); D3P_HROT(c1, 2); D3P_HROT(e1, 3);
+            D3P_HROT(b2, 1); D3P_HROT(c2, 2); D3P_HROT(e2, 3);
+            D3P_HQR(a0, b0, c0, e0) D3P_HQR(a1, b1, c1, e1) D3P_HQR(a2, b2, c2, e2)
+            D3P_HROT(b0, 3); D3P_HROT(c0, 2); D3P_HROT(e0, 1);
+            D3P_HROT(b1, 3); D3P_HROT(c1, 2); D3P_HROT(e1, 1);
+            D3P_HROT(b2, 3); D3P_HROT(c2, 2); D3P_HROT(e2, 1);
+        }
+        a0 += r0; b0 += r1; a1 += r0; b1 += r1; a2 += r0; b2 += r1;  // block words 0..7: all a child key takes
+        if (out) {
+            memcpy(out[t], &a1, 16); memcpy(out[t] + 4, &b1, 16);
+            memcpy(out[t] + 8, &a2, 16); memcpy(out[t] + 12, &b2, 16);
+        }
+        if (full) {
+            const d3p_hv4 ch[3][2] = {{a0, b0}, {a1, b1}, {a2, b2}};
+            for (int c = 0; c < 3; ++c) {
+                memcpy(full[t][c], &r0, 16);
+                memcpy(full[t][c] + 4, &ch[c][0], 16);
+                memcpy(full[t][c] + 8, &ch[c][1], 16);
+                memset(full[t][c] + 12, 0, 16);
+            }
+        }
+        r1 = a0;
+        r2 = b0;
+        r3 = (d3p_hv4){0u, 0u, 0u, 0u};
+    }
+    if (after8) {
+        memcpy(after8, &r1, 16);
+        memcpy(after8 + 4, &r2, 16);
+    }
+}
+#undef D3P_HQR
+#undef D3P_HROT
 
 // ------------------------------------------------------------------------------------------
 // sampler: grid (ceil(B/256) + 1, K); blockIdx.y = step within the batch; the extra x-block of every
@@ -1977,9 +2115,19 @@ static int run_fused_steps(const Ctx& c, const float* X, const float* y, uint32_
     // (Measured and not kept: the sampler's workgroups inside this launch, each waiting for the key chain to pass its step -- the
     // launch then takes 36 us for 20 steps, exactly the 18 + 17 us of the two launches: the sampler's ~15 us are LATENCY of the
     // last step's blocks (serial ChaCha derivations, Feistel walk, six dependent threefry calls), not throughput.)
-    hipLaunchKernelGGL(k_run_init, dim3(1), dim3(256), 0, c.s, (const uint32_t*)(st0->rng_key + 16 * (st0->key_slot & 1)),
+    // The first batch's links from the final key of the workspace's last run, if its record is in (k_run_init takes them only if
+    // the state's key is that key).  D3P_NO_HOST_CHAIN=1: developer switch, read once -- the chain is always walked on the device.
+    static const bool no_host_chain = getenv("D3P_NO_HOST_CHAIN") != nullptr;
+    RunInitLinks lk;
+    lk.n = 0;
+    if (!no_host_chain && status_slot_key(run_status_words(c.ws), lk.parent)) {
+        const int n = batch_len(0) < D3P_HOST_LINKS ? batch_len(0) : D3P_HOST_LINKS;
+        host_key_chain(lk.parent, n, lk.gp, nullptr, lk.after);
+        lk.n = (uint32_t)n;
+    }
+    hipLaunchKernelGGL(k_run_init, dim3(1), dim3(1024), 0, c.s, (const uint32_t*)(st0->rng_key + 16 * (st0->key_slot & 1)),
                        (const int32_t*)st0->step, sampled ? (const uint32_t*)c.src->batch_index : nullptr, c.ws.sched, cb[0].ws.slots,
-                       batch_len(0), c.ws.acc, acc_words, run_status_words(c.ws), cp);
+                       batch_len(0), c.ws.acc, acc_words, run_status_words(c.ws), cp, lk);
     if ((rc = check_launch("k_run_init"))) return rc;
     if ((rc = enqueue_sampler(cb[0], batch_len(0), xchg))) return rc;
     static const bool no_piggy = getenv("D3P_NO_CHAIN_PIGGYBACK") != nullptr;  // developer switch, read once
@@ -2122,6 +2270,13 @@ static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d
 using namespace d3p;
 
 extern "C" {
+
+int d3p_key_chain_host(const uint32_t* key, int num_links, uint32_t* out_keys)
+{
+    D3P_REQUIRE(key && out_keys && num_links >= 0, "d3p_key_chain_host: null pointer or negative length");
+    host_key_chain(key, num_links, nullptr, reinterpret_cast<uint32_t(*)[3][16]>(out_keys), nullptr);
+    return D3P_OK;
+}
 
 size_t d3p_dpvi_logreg_workspace(const d3p_logreg_model* model, const d3p_batch_source* src)
 {

@@ -48,6 +48,10 @@ int d3p_device_count(void);
  * ------------------------------------------------------------------------------------------- */
 /* split(key, num) -> num keys   (d3p/random/__init__.py:29; svi.py:210, :491) */
 int d3p_rng_split(void* stream, const uint32_t* key_dev, int num, uint32_t* out_keys_dev);
+/* Host only (no device, no stream): the first num_links links of the key chain of DPSVI.update from `key` -- link t is
+ * split(k_t, 3), k_0 = key, k_{t+1} = split(k_t, 3)[0].  out_keys: num_links x 3 x 16 words (children 0, 1, 2 of each link).
+ * The derivation the runs' start uses for the links it prepares on the host; exported so that it can be checked without a GPU. */
+int d3p_key_chain_host(const uint32_t* key, int num_links, uint32_t* out_keys);
 /* fold_in(key, data)            (d3p/random/__init__.py:30; minibatch.py:115, :207, :230) */
 int d3p_rng_fold_in(void* stream, const uint32_t* key_dev, uint32_t data, uint32_t* out_key_dev);
 /* random_bits(key, bit_width in {8,16,32,64}, shape) -> `count` elements

@@ -55,10 +55,14 @@ __device__ __forceinline__ void seed_site_key(const uint32_t (&chain)[2], int in
     }
 }
 
-// numpyro Normal.sample: loc + random.normal(key, shape) * scale -- a product, then a sum (two roundings, no fused multiply-add)
+// numpyro Normal.sample: loc + random.normal(key, shape) * scale -- a product, then a sum (two roundings, no fused multiply-add).
+// The pragma is what keeps them apart: hipcc contracts across inlined code by default, and HIP's __fadd_rn / __fmul_rn are plain
+// `+` / `*` there, so without it the product and the sum became one v_fma_f32 (tests/test_gpu_predictive_edges.py checks the two
+// roundings bit for bit)
 __device__ __forceinline__ float normal_site_value(float loc, float eps, float scale)
 {
-    return __fadd_rn(loc, __fmul_rn(eps, scale));
+#pragma clang fp contract(off)
+    return loc + eps * scale;
 }
 
 // BernoulliLogits.probs = expit(logits) = 1 / (1 + exp(-logits))

@@ -9,10 +9,12 @@ restatement of d3p/svi.py:395-434 driven by the oracle's own samplers: state key
 losses and parameters (empty batches: svi.py:305, :365), final parameters
 (rtol 5e-4, atol 5e-5 of the largest) and step counter.
 
-    python tests/fuzz_vs_oracle.py [update|big|stepwise|staged|gmm|vae|rng|batches|shards|posshards] [first_seed=0] [count=40] [out.jsonl]
+    python tests/fuzz_vs_oracle.py [update|big|stepwise|staged|gmm|vae|rng|batches|shards|posshards|predict] [first_seed=0] [count=40] [out.jsonl]
 
 `gmm`: the mixture model's update (explicit batches with masks, Feistel runs) vs the oracle's stage composition; `rng`: split / fold_in /
-random_bits / randint / uniform / normal / Feistel / Poisson selection at random arguments, bit-exact (normal: 2e-6).
+random_bits / randint / uniform / normal / Feistel / Poisson selection at random arguments, bit-exact (normal: 2e-6); `predict`: prior and
+posterior predictive sampling (logistic regression with its three guides, the Gaussian mean, the prior with a random substitution set) at
+tile-edge shapes, every draw against tests/predictive_ref.py.
 
 `tests/test_gpu_fuzz.py` runs a fixed handful of seeds inside the suite; a long sweep is run by hand on a GPU box."""
 import json
@@ -1039,10 +1041,146 @@ def run_batches_case(c, O, dump=False):
     return c
 
 
+# ------------------------------------------------------------------ predictive sampling (d3p_amd.modelling)
+PRED_DIMS = [1, 2, 3, 5, 31, 32, 33, 63, 64, 65, 100, 127, 128, 129, 255, 257, 511, 513, 700, 1025]
+PRED_ROWS = [1, 2, 3, 5, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1000, 4097, 10007, 65537]
+PRED_DRAWS = [0, 0, 1, 2, 63, 127, 128, 129, 255, 256, 257, 384, 1000]     # 0: the single form
+
+
+def draw_predict_case(seed):
+    r = np.random.default_rng(1_500_007 * seed + 83)
+    c = {"seed": int(seed), "family": "predict"}
+    c["model"] = str(r.choice(["logreg", "logreg", "logreg", "gauss"]))
+    c["guide"] = str(r.choice(["auto", "diag", "meanfield", "prior"] if c["model"] == "logreg" else ["auto", "diag", "prior"]))
+    c["intercept"] = c["model"] == "logreg" and (c["guide"] == "meanfield" or bool(r.random() < 0.6))
+    sites = ["w", "intercept"] if c["intercept"] else (["w"] if c["model"] == "logreg" else ["mu"])
+    c["subst"] = [s for s in sites if r.random() < 0.5] if c["guide"] == "prior" else []
+    c["d"], c["rows"], c["n"] = int(r.choice(PRED_DIMS)), int(r.choice(PRED_ROWS)), int(r.choice(PRED_DRAWS))
+    # bound the oracle's work: n rows <= 2e6 and n rows d <= 2e8 (logistic regression: one float64 product per draw), n rows d <= 4e6
+    # (Gaussian mean: one oracle normal per outcome)
+    def over():
+        nr = max(c["n"], 1) * c["rows"]
+        return nr > 2e6 or nr * c["d"] > (2e8 if c["model"] == "logreg" else 4e6)
+    while over():
+        if c["n"] > 1 and (r.random() < 0.5 or c["rows"] <= 3):
+            c["n"] = int(r.choice([v for v in PRED_DRAWS if v < c["n"]]))
+        elif c["rows"] > 1:
+            c["rows"] = int(r.choice([v for v in PRED_ROWS if v < c["rows"]]))
+        else:
+            c["d"] = int(r.choice([v for v in PRED_DIMS if v < c["d"]]))
+    c["loc_scale"] = float(r.choice([0.0, 0.05, 0.3, 1.0, 5.0, 30.0]))   # 30 with large X: |logit| far above 90
+    c["std_log"] = float(r.choice([-0.5, -2.0, -5.0, -9.0, -14.0]))     # guide scales exp(std_log +- 1)
+    c["prior_scale"] = float(r.choice([0.25, 1.0, 3.0]))
+    c["obs_scale"] = float(r.choice([0.01, 0.25, 1.0, 10.0]))
+    c["x_dist"] = str(r.choice(["normal", "normal", "zero_rows", "large"]))
+    c["key"] = int(r.integers(0, 2**62))
+    return c
+
+
+def predict_inputs(c):
+    """(model, guide or None, params or None, substitutes, X or None) of a `predict` case, all on the host."""
+    from d3p_amd.models import AutoDiagonalNormal, DiagonalNormalGuide, GaussianMean, LogisticRegression, MeanFieldGuide
+    r = np.random.default_rng(c["seed"] + 37)
+    d, rows = c["d"], c["rows"]
+    ls, sl, ps = np.float32(c["loc_scale"]), c["std_log"], c["prior_scale"]
+
+    def std_logs(size):
+        return (sl + r.uniform(-1, 1, size)).astype(np.float32)
+
+    guide, params, sub, X = None, None, {}, None
+    if c["model"] == "logreg":
+        X = r.normal(size=(rows, d)).astype(np.float32)
+        if c["x_dist"] == "zero_rows":
+            X[r.random(rows) < 0.3] = 0
+        elif c["x_dist"] == "large":
+            X = (30 * X).astype(np.float32)
+        model = LogisticRegression(d, prior_scale=ps, intercept=c["intercept"], intercept_prior_scale=2 * ps)
+        D = d + (1 if c["intercept"] else 0)
+        if c["guide"] == "auto":
+            guide = AutoDiagonalNormal(model)
+            params = {"auto_loc": (ls * r.normal(size=D)).astype(np.float32), "auto_scale": np.exp(std_logs(D)).astype(np.float32)}
+        elif c["guide"] == "diag":
+            guide = DiagonalNormalGuide(model)
+            params = {guide.site + "_loc": (ls * r.normal(size=D)).astype(np.float32), guide.site + "_std_log": std_logs(D)}
+        elif c["guide"] == "meanfield":
+            guide = MeanFieldGuide(model)
+            params = {"w_loc": (ls * r.normal(size=d)).astype(np.float32), "w_std_log": std_logs(d),
+                      "intercept_loc": np.float32(ls * r.normal()), "intercept_std_log": std_logs(1)[0]}
+        else:
+            values = {"w": (ls * r.normal(size=d)).astype(np.float32), "intercept": np.float32(ls * r.normal())}
+            sub = {s: values[s] for s in c["subst"]}
+    else:
+        model = GaussianMean(d, prior_scale=ps, obs_scale=c["obs_scale"])
+        if c["guide"] == "auto":
+            guide = AutoDiagonalNormal(model)
+            params = {"auto_loc": (ls * r.normal(size=d)).astype(np.float32), "auto_scale": np.exp(std_logs(d)).astype(np.float32)}
+        elif c["guide"] == "diag":
+            guide = DiagonalNormalGuide(model)
+            params = {"mu_loc": (ls * r.normal(size=d)).astype(np.float32), "mu_std_log": std_logs(d)}
+        elif "mu" in c["subst"]:
+            sub = {"mu": (ls * r.normal(size=d)).astype(np.float32)}
+    return model, guide, params, sub, X
+
+
+def run_predict_case(c, O, dump=False):
+    """Every latent draw and every outcome against the CPU restatement of tests/predictive_ref.py (its tolerances), plus the vacuity
+    guard of the Bernoulli check."""
+    import torch
+    from d3p_amd import modelling as M
+    from tests import predictive_ref as P
+    d, rows, n = c["d"], c["rows"], c["n"] or None
+    nn = n or 1
+    posterior = c["guide"] != "prior"
+    key, okey = P.key(c["key"]), P.key_words(c["key"])
+    model, guide, params, sub, X = predict_inputs(c)
+
+    def call(model_args, guide_args):
+        if posterior:
+            return (M.sample_multi_posterior_predictive(key, n, model, model_args, guide, guide_args, params) if n else
+                    M.sample_posterior_predictive(key, model, model_args, guide, guide_args, params))
+        return M.sample_multi_prior_predictive(key, n, model, model_args, sub) if n else M.sample_prior_predictive(key, model, model_args, sub)
+
+    why = []
+    try:
+        if c["model"] == "logreg":
+            Xt = torch.tensor(X, device="cuda")
+            res = call((Xt,), (Xt,))
+            if n is None:
+                res = {k: v.unsqueeze(0) for k, v in res.items()}
+            exp, okeys = P.logreg_expect(O, okey, nn, n is not None, model, guide, params, X, sub)
+            c["band_share"] = P.check_logreg(O, res, exp, okeys, X, d, c["intercept"], nn, "", sharp=True)
+            c["obs_mean"] = float(res["obs"].double().mean())
+            P.assert_not_vacuous(c["band_share"], nn * rows)
+        else:
+            res = call((None, rows) if posterior else (None, rows, d), (None, rows))
+            if n is None:
+                res = {k: v.unsqueeze(0) for k, v in res.items()}
+            mus, obs = P.np_(res["mu"]).reshape(nn, d), P.np_(res["obs"]).reshape(nn, rows, d)
+            for i, dk in enumerate(P.draw_keys(O, okey, nn, n is not None)):
+                mk, gk = P.chains(O, dk, posterior)
+                if "mu" in sub:
+                    assert np.array_equal(mus[i], sub["mu"]), f"substituted mu[{i}]"
+                else:
+                    eps = O.tf_normal(P.site_key(O, gk if posterior else mk, 0), d)
+                    if c["guide"] == "auto":
+                        loc, sc = params["auto_loc"], params["auto_scale"].astype(np.float64)
+                    elif c["guide"] == "diag":
+                        loc, sc = params["mu_loc"], np.exp(params["mu_std_log"].astype(np.float64))
+                    else:
+                        loc, sc = np.zeros(d, np.float32), np.full(d, c["prior_scale"])
+                    P.assert_latent(mus[i], loc, eps, sc, f"mu[{i}]")
+                eps_o = O.tf_normal(P.site_key(O, mk, 0 if (posterior or "mu" in sub) else 1), rows * d).reshape(rows, d)
+                P.assert_latent(obs[i], np.broadcast_to(mus[i], (rows, d)), eps_o, np.full((rows, d), c["obs_scale"], np.float32), f"obs[{i}]")
+    except AssertionError as e:
+        why.append(str(e)[:400])
+    c["ok"], c["why"] = not why, "; ".join(why)
+    return c
+
+
 FAMILIES = {"big": (draw_big_case, None), "stepwise": (draw_stepwise_case, None), "batches": (draw_batches_case, run_batches_case), "shards": (draw_shards_case, run_shards_case),
             "posshards": (draw_posshards_case, run_posshards_case), "update": (draw_case, None), "staged": (draw_staged_case, run_staged_case), "gmm": (draw_gmm_case, run_gmm_case),
             "vae": (draw_vae_case, run_vae_case),
-            "rng": (draw_rng_case, run_rng_case)}
+            "rng": (draw_rng_case, run_rng_case), "predict": (draw_predict_case, run_predict_case)}
 
 
 def main():

@@ -81,3 +81,11 @@ def test_random_large_batch_case_vs_oracle(gpu, O, seed):
 def test_random_stepwise_batchifier_case_vs_oracle(gpu, O, seed):
     c = F.run_case(F.draw_stepwise_case(seed), O)
     assert c["ok"], c
+
+
+# (prior and posterior predictive sampling: logistic regression with its three guides, the Gaussian mean, the prior with a random
+#  substitution set; d, rows and draws on both sides of k_predict_logreg's tiles; every draw against tests/predictive_ref.py)
+@pytest.mark.parametrize("seed", list(range(30)))
+def test_random_predictive_case_vs_oracle(gpu, O, seed):
+    c = F.run_predict_case(F.draw_predict_case(seed), O)
+    assert c["ok"], c

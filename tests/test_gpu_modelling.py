@@ -1,26 +1,7 @@
 """Predictive sampling (d3p_amd.modelling) on the GPU against the oracle's threefry primitives (the reference's
 tests/test_modelling.py:31-250 re-expressed, plus bit-level checks of the key plumbing stated in DESIGN.md section 4b).
 
-Expected draws are rebuilt on the CPU from O.tf_split / O.tf_normal / O.tf_uniform following section 4b:
-  keys = split(key, n) (multi form), posterior: model_key, guide_key = split(draw key), the seed handler's
-  `chain, site_key = split(chain)` per key-taking sample statement; Normal: loc + normal * scale; Bernoulli: uniform < p.
-
-Tolerances (stated once, never widened after a failure without a written reason):
-  * latent sites: the device computes fl(loc + fl(eps * scale)) in float32 -- two roundings of at most 2^-24 relative each.  Its
-    eps agrees with the oracle's normal to the repository's normal() tolerance, rtol 2e-6 / atol 2e-7 (tests/test_gpu_rng.py:
-    v_log_f32 on the device, glibc's log1pf in the oracle -- NOT bit for bit); against the float64 value:
-    |dev - ref| <= 2e-6 |ref| + (2e-6 |eps| + 2e-7) |scale| + 2^-23 (|loc| + |eps scale|) ("rtol 2e-6 plus one multiply-add").
-    Scales that are exp(.) of a parameter add expf's own error (<= 2 ulp) to eps scale.
-  * Bernoulli outcomes: the device compares the float32 uniform u (bit-equal to the oracle's) with a float32 p.  The logit
-    x . w + b summed in float32 in ANY order is within gamma_K (sum |x_k w_k| + |b|) of the exact value, gamma_K = (K + 1) 2^-24 /
-    (1 - (K + 1) 2^-24) (Higham's bound; doubled here for the +b and the product roundings: (K + 2) 2^-23); the sigmoid is
-    1/4-Lipschitz and its float32 evaluation (expf, one add, one divide) adds at most 2^-21.  So an outcome may differ from the
-    float64 one only where |u - p64| <= band = gamma (sum |x w| + |b|) / 4 + 2^-21, and must be equal everywhere else.
-  * VAE: the dense products run on the bf16x3 / fp32 MFMA kernels; per product the error is bounded by the fp32 sum bound with
-    a 4x margin for the three-way bf16 split (the dropped lo x lo terms are below 2^-24 relative each): gamma_K = K 2^-22.  The
-    bound is propagated layer by layer in float64 (softplus and sigmoid are 1- and 1/4-Lipschitz; softplus' float32 evaluation
-    adds 2^-22 (|h| + 1)); z is checked with the propagated encoder bound, the outcomes with the decoder bound evaluated on the
-    DEVICE's z.
+The CPU restatement of section 4b and the tolerances of every check live in tests/predictive_ref.py (its docstring states them).
 """
 import math
 
@@ -32,120 +13,12 @@ from d3p_amd import modelling as M
 from d3p_amd.models import (AutoDiagonalNormal, DiagonalNormalGuide, GaussianMean, LogisticRegression, MeanFieldGuide,
                             VAEGuide, VAEModel)
 
+from .predictive_ref import (assert_bernoulli as _assert_bernoulli, assert_latent as _assert_latent, chains as _chains,
+                             check_logreg as _check_logreg, dense_bound as _dense_bound, key as _key, logreg_expect as _logreg_expect,
+                             logreg_params as _logreg_params, np_ as _np, site_key as _site_key, vae_decode_bound as _vae_decode_bound,
+                             vae_net as _vae_net)
+
 pytestmark = pytest.mark.gpu
-
-
-def _key(seed):
-    import d3p_amd.random.debug as jr
-    return jr.PRNGKey(seed)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-# ------------------------------------------------------------------------------- CPU restatement of section 4b
-def _draw_keys(O, key, n, multi):
-    return O.tf_split(key, n) if multi else np.asarray(key, np.uint32).reshape(1, 2)
-
-
-def _chains(O, dk, posterior):
-    if not posterior:
-        return dk, None
-    kk = O.tf_split(dk, 2)
-    return kk[0], kk[1]
-
-
-def _site_key(O, chain, index):
-    c = chain
-    for _ in range(index + 1):
-        kk = O.tf_split(c, 2)
-        c, s = kk[0], kk[1]
-    return s
-
-
-def _assert_latent(dev, loc, eps, scale, what):
-    ref = loc.astype(np.float64) + eps.astype(np.float64) * scale.astype(np.float64)
-    tol = (2e-6 * np.abs(ref) + (2e-6 * np.abs(eps) + 2e-7) * np.abs(scale) + 2.0 ** -23 * (np.abs(loc) + np.abs(eps.astype(np.float64) * scale))
-           + 1e-30)
-    err = np.abs(dev.astype(np.float64) - ref)
-    assert np.all(err <= tol), f"{what}: max err {err.max()} (tol at argmax {tol.ravel()[err.argmax()]})"
-
-
-def _assert_bernoulli(obs, u, p64, band, what):
-    obs, u, p64, band = (np.asarray(a) for a in (obs, u, p64, band))
-    exp = (u < p64).astype(np.int32)
-    bad = (obs != exp) & (np.abs(u - p64) > band)
-    assert not bad.any(), f"{what}: {int(bad.sum())} outcomes differ outside the band (first at {np.argwhere(bad)[0]})"
-    assert set(np.unique(obs)) <= {0, 1}
-
-
-def _logreg_expect(O, key, n, multi, model, guide, params, X, subst=None):
-    """(latent dict, obs keys) rebuilt on the CPU."""
-    d = X.shape[1]
-    subst = subst or {}
-    posterior = guide is not None
-    plan = M.site_plan(model, guide, set(subst), d=d, rows=X.shape[0])
-    out = {k: [] for k in [s.name for s in plan]}
-    okeys = []
-    for dk in _draw_keys(O, key, n, multi):
-        mk, gk = _chains(O, dk, posterior)
-        for st in plan:
-            if st.name == "obs":
-                okeys.append(_site_key(O, mk, st.key_index))
-                continue
-            if st.chain == "model" and st.substituted:
-                if not posterior:
-                    out[st.name].append(np.asarray(subst[st.name], np.float32).reshape(-1))
-                continue
-            chain = gk if st.chain == "guide" else mk
-            eps = O.tf_normal(_site_key(O, chain, st.key_index), st.size)
-            if posterior:
-                if isinstance(guide, AutoDiagonalNormal):
-                    loc, sc = params["auto_loc"], params["auto_scale"]
-                elif isinstance(guide, MeanFieldGuide):
-                    loc, sc = np.atleast_1d(params[st.name + "_loc"]), np.exp(np.atleast_1d(params[st.name + "_std_log"]).astype(np.float64))
-                else:
-                    loc, sc = params[guide.site + "_loc"], np.exp(params[guide.site + "_std_log"].astype(np.float64))
-            else:
-                prior = model.intercept_prior_scale if st.name == "intercept" else model.prior_scale
-                loc, sc = np.zeros(st.size, np.float32), np.full(st.size, prior)
-            out[st.name].append((np.asarray(loc, np.float32), eps, np.asarray(sc, np.float64)))
-    return out, okeys
-
-
-def _check_logreg(O, res, exp, okeys, X, d, intercept, n, what):
-    for name, draws in exp.items():
-        if name == "obs" or not draws:
-            continue
-        dev = _np(res[name]).reshape(n, -1)
-        if isinstance(draws[0], tuple) and draws[0][0].size == d + 1 and name == "w":   # one guide site 'w' over [w | intercept]
-            dev = np.concatenate([dev, _np(res["intercept"]).reshape(n, 1)], axis=1)
-        for i, dr in enumerate(draws):
-            if isinstance(dr, tuple):
-                loc, eps, sc = dr
-                _assert_latent(dev[i], loc, eps, sc, f"{what} {name}[{i}]")
-            else:
-                assert np.array_equal(dev[i], dr), f"{what}: substituted {name}"
-    w = _np(res["w"]).reshape(n, d).astype(np.float64)
-    b = _np(res["intercept"]).reshape(n).astype(np.float64) if intercept else np.zeros(n)
-    X64 = X.astype(np.float64)
-    obs = _np(res["obs"]).reshape(n, -1)
-    gamma = (d + 2) * 2.0 ** -23
-    for i in range(n):
-        logit = X64 @ w[i] + b[i]
-        band = gamma * (np.abs(X64) @ np.abs(w[i]) + abs(b[i])) / 4 + 2.0 ** -21
-        _assert_bernoulli(obs[i], O.tf_uniform(okeys[i], X.shape[0]), 1 / (1 + np.exp(-logit)), band, f"{what} obs[{i}]")
-
-
-def _logreg_params(guide, d, intercept, rng):
-    D = d + (1 if intercept else 0)
-    if isinstance(guide, AutoDiagonalNormal):
-        return {"auto_loc": rng.normal(size=D).astype(np.float32), "auto_scale": rng.uniform(0.05, 0.5, D).astype(np.float32)}
-    if isinstance(guide, MeanFieldGuide):
-        return {"w_loc": rng.normal(size=d).astype(np.float32), "w_std_log": rng.uniform(-3, -0.5, d).astype(np.float32),
-                "intercept_loc": np.float32(rng.normal()), "intercept_std_log": np.float32(-1.0)}
-    return {guide.site + "_loc": rng.normal(size=D).astype(np.float32), guide.site + "_std_log": rng.uniform(-3, -0.5, D).astype(np.float32)}
 
 
 LOGREG_CASES = [(False, AutoDiagonalNormal), (True, AutoDiagonalNormal), (False, DiagonalNormalGuide), (True, DiagonalNormalGuide),
@@ -235,48 +108,6 @@ def test_gaussian_mean_substituted_mu_is_returned_as_given(gpu, O):
 
 
 # ------------------------------------------------------------------------------- VAE
-def _vae_net(D, H, Z, H2, rng, scale=0.05):
-    from d3p_amd._lib import VaeModel
-    shapes, n_dec = M._vae_leaf_shapes(VaeModel(D, H, Z, 1.0, 1.0, H2))
-    leaves = [(scale * rng.normal(size=s)).astype(np.float32) for s in shapes]
-    nd = n_dec // 2
-    dec = []
-    for k in range(nd):
-        dec += [(leaves[2 * k], leaves[2 * k + 1]), ()]
-    enc = []
-    ne = (len(shapes) - n_dec - 4) // 2
-    for k in range(ne):
-        enc += [(leaves[n_dec + 2 * k], leaves[n_dec + 2 * k + 1]), ()]
-    Wl, bl, Ws, bs = leaves[-4:]
-    enc += [(), ((Wl, bl), ((Ws, bs), ()))]
-    layers_dec = [(leaves[2 * k], leaves[2 * k + 1]) for k in range(nd)]
-    layers_enc = [(leaves[n_dec + 2 * k], leaves[n_dec + 2 * k + 1]) for k in range(ne)]
-    return {"decoder$params": dec, "encoder$params": enc}, layers_dec, layers_enc, (Wl, bl, Ws, bs)
-
-
-def _softplus(x):
-    return np.logaddexp(0.0, x)
-
-
-def _dense_bound(h, E, W, b, act):
-    """float64 forward of one layer and the propagated bound of its float32 evaluation (module docstring)."""
-    W64, b64 = W.astype(np.float64), b.astype(np.float64)
-    o = h @ W64 + b64
-    K = W.shape[0]
-    Eo = E @ np.abs(W64) + K * 2.0 ** -22 * (np.abs(h) @ np.abs(W64) + np.abs(b64))
-    if act:
-        y = _softplus(o)
-        return y, Eo + 2.0 ** -22 * (np.abs(y) + 1)
-    return o, Eo
-
-
-def _vae_decode_bound(z, layers_dec):
-    h, E = z.astype(np.float64), np.zeros(z.shape)
-    for k, (W, b) in enumerate(layers_dec):
-        h, E = _dense_bound(h, E, W, b, k < len(layers_dec) - 1)
-    return h, E
-
-
 @pytest.mark.parametrize("H,H2", [(40, 0), (40, 24)])
 @pytest.mark.parametrize("posterior", [True, False])
 def test_vae_against_oracle(gpu, O, H, H2, posterior):

@@ -765,6 +765,7 @@ __device__ __forceinline__ float gmm_pending_count(const GmmPending& u)
 
 __device__ __forceinline__ float gmm_pending_loss(const GmmPending& u, float factor)
 {
+#pragma clang fp contract(off)  // (as in gmm_apply_column)
     float ls;
     if (u.fsums) {
         ls = u.fsums[u.P];
@@ -776,14 +777,18 @@ __device__ __forceinline__ float gmm_pending_loss(const GmmPending& u, float fac
         }
         ls = (float)loss_join(hi, lo);
     }
-    return __fmul_rn(__fmul_rn(__fdiv_rn(ls, u.Bf), u.obs_scale), factor);  // svi.py:342, :306
+    return (__fdiv_rn(ls, u.Bf) * u.obs_scale) * factor;  // svi.py:342, :306
 }
 
 // mean over the padded batch (svi.py:343-346), Gaussian mechanism (svi.py:365-375), rescale (svi.py:377), numpyro Adam
 // (svi.py:379-393) for column c.  Every rounding is explicit (no fused multiply-add left to the compiler): the head kernel,
-// the flush kernel and every workgroup that recomputes a Dirichlet column must agree bit for bit.
+// the flush kernel and every workgroup that recomputes a Dirichlet column must agree bit for bit.  HIP's __fadd_rn / __fmul_rn are
+// plain + / * that hipcc contracts wherever they are inlined (the noise term was one v_fmac_f32), so products and sums are written
+// as operators under the pragma; __fsqrt_rn is ocml's native (approximate) square root, sqrtf the correctly rounded one
+// (tests/test_gpu_gmm_update_edges.py checks every rounding bit for bit)
 __device__ __forceinline__ float gmm_apply_column(const GmmPending& u, int c, float n, float factor, float& m, float& v, float& g)
 {
+#pragma clang fp contract(off)
     float tot;
     if (u.fsums) {
         tot = u.fsums[c];
@@ -792,12 +797,12 @@ __device__ __forceinline__ float gmm_apply_column(const GmmPending& u, int c, fl
         for (int r = 0; r < D3P_GMM_ACC_R; ++r) s += u.acc[(size_t)r * D3P_ACC_COLS(u.P) + c];
         tot = (float)((double)s * u.inv_sg);
     }
-    const float noise_scale = __fmul_rn(u.dp_scale, __fdiv_rn(u.clip, n));
-    g = __fmul_rn(__fmul_rn(__fadd_rn(__fdiv_rn(tot, u.Bf), __fmul_rn(u.noise[c], noise_scale)), u.obs_scale), factor);
-    m = __fadd_rn(__fmul_rn(1.0f - u.b1, g), __fmul_rn(u.b1, u.in[1][c]));
-    v = __fadd_rn(__fmul_rn(__fmul_rn(1.0f - u.b2, g), g), __fmul_rn(u.b2, u.in[2][c]));
+    const float noise_scale = u.dp_scale * __fdiv_rn(u.clip, n);
+    g = ((__fdiv_rn(tot, u.Bf) + u.noise[c] * noise_scale) * u.obs_scale) * factor;
+    m = (1.0f - u.b1) * g + u.b1 * u.in[1][c];
+    v = ((1.0f - u.b2) * g) * g + u.b2 * u.in[2][c];
     const float mhat = __fdiv_rn(m, u.slot->bc1), vhat = __fdiv_rn(v, u.slot->bc2);
-    return __fsub_rn(u.in[0][c], __fdiv_rn(__fmul_rn(u.lr, mhat), __fadd_rn(__fsqrt_rn(vhat), u.adam_eps)));
+    return u.in[0][c] - __fdiv_rn(u.lr * mhat, sqrtf(vhat) + u.adam_eps);
 }
 
 // One link of the key chain of the NEXT batch of steps, made by an extra workgroup of a k_gmm_head launch (consecutive launches
@@ -1037,7 +1042,8 @@ static void gmm_fill(GmmArgs* a, const d3p_gmm_model* model, const float* params
 template <bool SUM>
 static int gmm_launch_px(hipStream_t s, const d3p_gmm_model* model, const GmmArgs& a)
 {
-    const int KH = (model->K + 1) / 2 <= 8 ? 8 : 16, DS = (model->d + 63) / 64;
+    // (three slots run the four-slot instantiation: `full` must see that DS, or K = 16, d = 192 took the d = 256 full tile)
+    const int KH = (model->K + 1) / 2 <= 8 ? 8 : 16, DS = (model->d + 63) / 64 == 3 ? 4 : (model->d + 63) / 64;
     // workgroups per CU = the kernel's launch bound (measured at K = 16, d = 64, B = 8192: 3 -> 57.4, 4 (128 VGPRs, 68 bytes of
     // scratch) -> 61.2, 2 -> 77.7 us per step)
     const int occ = KH * DS <= 8 ? 3 : KH * DS <= 16 ? 2 : 1;

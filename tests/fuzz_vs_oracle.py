@@ -11,7 +11,8 @@ losses and parameters (empty batches: svi.py:305, :365), final parameters
 
     python tests/fuzz_vs_oracle.py [update|big|stepwise|staged|gmm|vae|rng|batches|shards|posshards|predict] [first_seed=0] [count=40] [out.jsonl]
 
-`gmm`: the mixture model's update (explicit batches with masks, Feistel runs) vs the oracle's stage composition; `rng`: split / fold_in /
+`gmm`: the mixture model's update (explicit batches with masks, Feistel runs; half the cases from a live state: random Adam moments and
+step counter) vs the oracle's stage composition; `rng`: split / fold_in /
 random_bits / randint / uniform / normal / Feistel / Poisson selection at random arguments, bit-exact (normal: 2e-6); `predict`: prior and
 posterior predictive sampling (logistic regression with its three guides, the Gaussian mean, the prior with a random substitution set) at
 tile-edge shapes, every draw against tests/predictive_ref.py.
@@ -427,6 +428,10 @@ def draw_gmm_case(seed):
         c["steps"] = int(r2.choice([65, 70, 130]))       # across the native loop's batches of prepared steps
     c["alpha_scale"] = float(r2.choice([0.4, 0.4, 1.5]))   # log-concentrations ~ N(0, alpha_scale^2): Dirichlet concentrations 0.05 .. 20 at 1.5
     c["mu_scale"] = float(r2.choice([2.0, 2.0, 8.0]))
+    r3 = np.random.default_rng(1_700_009 * seed + 83)   # (its own stream too)
+    if r3.random() < 0.5:   # a live starting state: Adam moments m ~ N(0, v), v ~ live_v e^U(-2, 2), and a step counter
+        c["live_step"] = int(r3.choice([1, 7, 1000, 100_000]))
+        c["live_v"] = float(r3.choice([1e-4, 1.0, 1e4, 1e8]))
     return c
 
 
@@ -442,11 +447,17 @@ def run_gmm_case(c, O, dump=False):
     params = np.concatenate([r.normal(size=K) * c.get("alpha_scale", 0.4), r.normal(size=K * d) * c.get("mu_scale", 2.0)]).astype(np.float32)
     model = GaussianMixtureModel()
     svi = DPSVI(model, GaussianMixtureGuide(model), Adam(c["lr"]), Trace_ELBO(), c["clip"], c["sigma"], k=K, d=d, num_obs_total=N)
-    st = DPSVIState(svi.optim.init(torch.tensor(params).cuda()), rng.PRNGKey(c["key"]), float(N))
+    i0 = int(c.get("live_step", 0))
+    x, m, v = params.copy(), np.zeros_like(params), np.zeros_like(params)
+    if "live_step" in c:
+        rl = np.random.default_rng(c["seed"] + 13)
+        v = (np.exp(rl.uniform(-2, 2, params.size)) * c["live_v"]).astype(np.float32)
+        m = (rl.normal(size=params.size) * np.sqrt(v)).astype(np.float32)
+    optim_state = (torch.tensor(i0, dtype=torch.int32).cuda(),) + tuple(torch.tensor(a).cuda() for a in (x, m, v))
+    st = DPSVIState(optim_state, rng.PRNGKey(c["key"]), float(N))
     spec = O.gmm_spec(K, d, 10.0, lik_scale=N, obs_scale=N)
     Xd = torch.tensor(X).cuda()
     key = O.PRNGKey(c["key"])
-    x, m, v = params.copy(), np.zeros_like(params), np.zeros_like(params)
     el, mask = [], None
 
     blown = False     # a per-example gradient that is not finite (a Gamma draw of 1e-317 under a concentration of 0.05 ...)
@@ -460,7 +471,7 @@ def run_gmm_case(c, O, dump=False):
         eloss, avg = O.combine(O.clip_rows(G, c["clip"]), L)
         with np.errstate(all="ignore"):
             g = O.perturb(ks[2], avg, [K, K * d], c["sigma"], c["clip"], n, N, f)
-        x, m, v = O.adam(x, m, v, g, i, lr=c["lr"])
+        x, m, v = O.adam(x, m, v, g, i0 + i, lr=c["lr"])
         key = ks[0]
         return eloss
     if c["source"] == "explicit":
@@ -498,8 +509,8 @@ def run_gmm_case(c, O, dump=False):
             why.append(f"loss {k}: {got_l[fin][k]!r} vs {want_l[fin][k]!r}")
     if not np.array_equal(st.rng_key.cpu().numpy().ravel(), np.asarray(key).ravel()):
         why.append("state key differs")
-    if int(st.optim_state[0]) != steps:
-        why.append(f"step counter {int(st.optim_state[0])} != {steps}")
+    if int(st.optim_state[0]) != i0 + steps:
+        why.append(f"step counter {int(st.optim_state[0])} != {i0 + steps}")
     if not np.array_equal(np.isnan(got_p), np.isnan(x)):
         why.append("parameters: NaN pattern differs")
     else:

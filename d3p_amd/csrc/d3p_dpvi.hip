@@ -21,6 +21,7 @@
 #include "d3p_logreg_persist.h"
 #include "d3p_logreg_chain.h"
 #include "d3p_logreg_wide.h"
+#include "d3p_logreg_particles.h"
 #include "d3p_ipc_arena.h"
 
 #include <dlfcn.h>
@@ -1044,6 +1045,7 @@ struct Ctx {
     bool batch0_by_value = false;           // ... and from batch index batch0 instead of *src->batch_index
     uint32_t batch0 = 0;
     Workspace ws2;  // second slot buffer (slots / idx / skeys / noise) for the pipelined run loop
+    uint32_t K = 1;  // ELBO particles per example: K > 1 runs k_logreg_particles in two-kernel steps (main + k_finalize)
 };
 
 // zeroed status words for a run form that does not end with k_flush: the reader must not take an earlier run's pinned record
@@ -1208,6 +1210,13 @@ static int enqueue_main(const Ctx& c, int t, const float* X, const float* y, con
     a.clip = c.h->clip;
     a.stamps = stamps ? c.ws.stamps : nullptr;
     a.dbg = dev_dbg_flags();
+    if (c.K > 1) {  // multi-particle ELBO: the particle keys are derived in the kernel from the step's jax key (slot t)
+        ParticleArgs pa;
+        pa.a = a;
+        pa.jax_key = c.ws.slots[t].jax_key;
+        pa.K = c.K;
+        return launch_particles<false>(c.s, pa, c.g.blocks, e0, e1);
+    }
     if (c.g.wide) {  // wide rows: column-chunked kernel, same partial-row output
         if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(k_logreg_wide<false>), 160 * 1024, "k_logreg_wide")) return rc_;
         if (e0)
@@ -1292,7 +1301,7 @@ static void timing_pair(int steps, hipEvent_t* e0, hipEvent_t* e1)
 static bool use_fused_step(const Ctx& c)
 {
     static const bool off = getenv("D3P_NO_FUSED_STEP") != nullptr;  // two-kernel steps (main + finalize), kept for comparison
-    return !off && !c.g.wide;  // wide rows run as two-kernel steps with the column-chunked main kernel
+    return !off && !c.g.wide && c.K == 1;  // wide rows and K > 1 particles run as two-kernel steps
 }
 
 static void fill_fuse_common(const Ctx& c, StepFuse* f, int g)
@@ -2245,7 +2254,7 @@ static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_
 
 static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
                     const d3p_dpsvi_state* state, const d3p_batch_source* src, void* workspace_dev,
-                    size_t workspace_bytes)
+                    size_t workspace_bytes, uint32_t num_particles = 1)
 {
     int rc = validate(model, hyper, state, src);
     if (rc) return rc;
@@ -2262,6 +2271,11 @@ static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d
     c->src = src;
     c->D = model->d + (model->intercept ? 1 : 0);
     c->P = 2 * c->D;
+    c->K = num_particles;
+    if (num_particles > 1) {  // the step's partial rows come from k_logreg_particles (its own workgroup count)
+        D3P_REQUIRE(particles_waves(c->D, false) > 0, "num_particles > 1: the latent dimension is too large for the particle kernel");
+        c->g.blocks = particles_blocks(c->D, false, c->items_expected);
+    }
     return D3P_OK;
 }
 
@@ -2284,13 +2298,12 @@ size_t d3p_dpvi_logreg_workspace(const d3p_logreg_model* model, const d3p_batch_
     return carve(model, src, nullptr, nullptr);
 }
 
-int d3p_dpvi_logreg_local_sums(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
-                               const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev,
-                               const float* y_dev, const float* eps_dev, float* sums_dev, void* workspace_dev,
-                               size_t workspace_bytes)
+static int local_sums_k(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper, const d3p_dpsvi_state* state,
+                        const d3p_batch_source* src, const float* X_dev, const float* y_dev, const float* eps_dev, float* sums_dev,
+                        void* workspace_dev, size_t workspace_bytes, uint32_t num_particles)
 {
     Ctx c;
-    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes);
+    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes, num_particles);
     if (rc) return rc;
     D3P_REQUIRE(X_dev && sums_dev, "null data pointer");
     if (int rcm = validate_model(model, y_dev, "d3p_dpvi_logreg")) return rcm;
@@ -2300,6 +2313,29 @@ int d3p_dpvi_logreg_local_sums(void* stream, const d3p_logreg_model* model, cons
     hipLaunchKernelGGL(k_reduce_partials, dim3(cdiv(c.P + 2, 64)), dim3(64 * D3P_FIN_W), 0, c.s,
                        (const float*)c.ws.partials, c.g.blocks, (uint32_t)(c.P + 2), sums_dev);
     return check_launch("k_reduce_partials");
+}
+
+int d3p_dpvi_logreg_local_sums(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+                               const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev,
+                               const float* y_dev, const float* eps_dev, float* sums_dev, void* workspace_dev,
+                               size_t workspace_bytes)
+{
+    return local_sums_k(stream, model, hyper, state, src, X_dev, y_dev, eps_dev, sums_dev, workspace_dev, workspace_bytes, 1u);
+}
+
+// d3p_dpvi_logreg_local_sums with num_particles ELBO particles per example (K == 1: exactly d3p_dpvi_logreg_local_sums); eps_dev,
+// if given, is (B, K, D).  Single GPU only.
+int d3p_dpvi_logreg_local_sums_particles(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+                                         const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev,
+                                         const float* y_dev, const float* eps_dev, uint32_t num_particles, float* sums_dev,
+                                         void* workspace_dev, size_t workspace_bytes)
+{
+    D3P_REQUIRE(num_particles >= 1, "d3p_dpvi_logreg_local_sums_particles: num_particles must be >= 1");
+    if (num_particles == 1)
+        return d3p_dpvi_logreg_local_sums(stream, model, hyper, state, src, X_dev, y_dev, eps_dev, sums_dev, workspace_dev, workspace_bytes);
+    D3P_REQUIRE(src, "d3p_dpvi_logreg_local_sums_particles: null pointer");
+    D3P_REQUIRE(src->row_lo == 0 && src->row_hi == src->n_rows, "d3p_dpvi_logreg_local_sums_particles is the single-GPU path");
+    return local_sums_k(stream, model, hyper, state, src, X_dev, y_dev, eps_dev, sums_dev, workspace_dev, workspace_bytes, num_particles);
 }
 
 int d3p_dpvi_logreg_finalize(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
@@ -2652,17 +2688,21 @@ int d3p_dpvi_logreg_run_dist(void* stream, void* comm, const d3p_logreg_model* m
 // batch index first_batch (by value), and leaves its result in `state` (key in slot num_steps & 1 of state->rng_key; its
 // key_slot is taken as 0) -- the copies and the batch-index word that the caller would otherwise prepare with four small
 // launches happen inside the run's first kernel.  Fused-step configurations only (the default).
-int d3p_dpvi_logreg_run_from(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+static int logreg_run_k(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper, const d3p_dpsvi_state* state,
+                        const d3p_batch_source* src, const float* X_dev, const float* y_dev, uint32_t num_steps, float* losses_dev,
+                        void* workspace_dev, size_t workspace_bytes, uint32_t num_particles);
+
+static int logreg_run_from_k(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
                              const d3p_dpsvi_state* state, const d3p_dpsvi_state* from, const d3p_batch_source* src,
                              uint32_t first_batch, const float* X_dev, const float* y_dev, uint32_t num_steps, float* losses_dev,
-                             void* workspace_dev, size_t workspace_bytes)
+                             void* workspace_dev, size_t workspace_bytes, uint32_t num_particles)
 {
     D3P_REQUIRE(from && from->rng_key && from->params && from->adam_m && from->adam_v && from->step, "d3p_dpvi_logreg_run_from: null source state");
     D3P_REQUIRE(src && workspace_dev, "d3p_dpvi_logreg_run_from: null pointer");
     d3p_batch_source s2 = *src;
     if (s2.kind != D3P_BATCH_EXPLICIT && !s2.batch_index) s2.batch_index = reinterpret_cast<uint32_t*>(workspace_dev);  // placeholder for validate(); set below
     Ctx c;
-    int rc = make_ctx(&c, stream, model, hyper, state, &s2, workspace_dev, workspace_bytes);
+    int rc = make_ctx(&c, stream, model, hyper, state, &s2, workspace_dev, workspace_bytes, num_particles);
     if (rc) return rc;
     D3P_REQUIRE(X_dev, "null data pointer");
     if (int rcm = validate_model(model, y_dev, "d3p_dpvi_logreg_run_from")) return rcm;
@@ -2670,7 +2710,7 @@ int d3p_dpvi_logreg_run_from(void* stream, const d3p_logreg_model* model, const 
     D3P_REQUIRE(state->key_slot == 0, "d3p_dpvi_logreg_run_from: state->key_slot must be 0");
     // the run's own batch-index word: a spare word of the workspace (k_run_init stores first_batch there, k_flush advances it)
     s2.batch_index = reinterpret_cast<uint32_t*>(c.ws.scratch_state + 3 * c.P + 2);
-    if (!use_fused_step(c)) {  // two-kernel steps (wide rows, D3P_NO_FUSED_STEP): copy here, then the in-place run
+    if (!use_fused_step(c)) {  // two-kernel steps (wide rows, K > 1 particles, D3P_NO_FUSED_STEP): copy here, then the in-place run
         hipStream_t hs = (hipStream_t)stream;
         const size_t pb = (size_t)c.P * sizeof(float);
         D3P_HIP_TRY(hipMemcpyAsync(state->params, from->params, pb, hipMemcpyDeviceToDevice, hs));
@@ -2679,13 +2719,38 @@ int d3p_dpvi_logreg_run_from(void* stream, const d3p_logreg_model* model, const 
         D3P_HIP_TRY(hipMemcpyAsync(state->step, from->step, sizeof(int32_t), hipMemcpyDeviceToDevice, hs));
         D3P_HIP_TRY(hipMemcpyAsync(state->rng_key, from->rng_key + 16 * (from->key_slot & 1), 16 * sizeof(uint32_t), hipMemcpyDeviceToDevice, hs));
         D3P_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s2.batch_index, (int)first_batch, 1, hs));
-        return d3p_dpvi_logreg_run(stream, model, hyper, state, &s2, X_dev, y_dev, num_steps, losses_dev, workspace_dev, workspace_bytes);
+        return logreg_run_k(stream, model, hyper, state, &s2, X_dev, y_dev, num_steps, losses_dev, workspace_dev, workspace_bytes,
+                            num_particles);
     }
     c.src = &s2;
     c.from = from;
     c.batch0_by_value = true;
     c.batch0 = first_batch;
     return run_fused_steps(c, X_dev, y_dev, num_steps, losses_dev);
+}
+
+int d3p_dpvi_logreg_run_from(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+                             const d3p_dpsvi_state* state, const d3p_dpsvi_state* from, const d3p_batch_source* src,
+                             uint32_t first_batch, const float* X_dev, const float* y_dev, uint32_t num_steps, float* losses_dev,
+                             void* workspace_dev, size_t workspace_bytes)
+{
+    return logreg_run_from_k(stream, model, hyper, state, from, src, first_batch, X_dev, y_dev, num_steps, losses_dev, workspace_dev,
+                             workspace_bytes, 1u);
+}
+
+// d3p_dpvi_logreg_run_from with num_particles ELBO particles per example (K == 1: exactly d3p_dpvi_logreg_run_from).  K > 1 runs
+// two-kernel steps (k_logreg_particles + k_finalize) in the workspace of d3p_dpvi_logreg_workspace; single GPU only.
+int d3p_dpvi_logreg_run_particles_from(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+                                       const d3p_dpsvi_state* state, const d3p_dpsvi_state* from, const d3p_batch_source* src,
+                                       uint32_t first_batch, const float* X_dev, const float* y_dev, uint32_t num_steps,
+                                       uint32_t num_particles, float* losses_dev, void* workspace_dev, size_t workspace_bytes)
+{
+    D3P_REQUIRE(num_particles >= 1, "d3p_dpvi_logreg_run_particles_from: num_particles must be >= 1");
+    if (num_particles == 1)
+        return d3p_dpvi_logreg_run_from(stream, model, hyper, state, from, src, first_batch, X_dev, y_dev, num_steps, losses_dev,
+                                        workspace_dev, workspace_bytes);
+    return logreg_run_from_k(stream, model, hyper, state, from, src, first_batch, X_dev, y_dev, num_steps, losses_dev, workspace_dev,
+                             workspace_bytes, num_particles);
 }
 
 // The data-parallel runs (d3p_dpvi_logreg_run_dist / _run_xchg) likewise as functions of an immutable state: `comm` (RCCL) or
@@ -2721,13 +2786,12 @@ int d3p_dpvi_logreg_run_dist_from(void* stream, void* comm, void* xchg, const d3
     return run_fused_steps(c, X_dev, y_dev, num_steps, losses_dev, (ncclComm_t)comm, (Xchg*)xchg);
 }
 
-int d3p_dpvi_logreg_run(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
-                        const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev,
-                        const float* y_dev, uint32_t num_steps, float* losses_dev, void* workspace_dev,
-                        size_t workspace_bytes)
+static int logreg_run_k(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper, const d3p_dpsvi_state* state,
+                        const d3p_batch_source* src, const float* X_dev, const float* y_dev, uint32_t num_steps, float* losses_dev,
+                        void* workspace_dev, size_t workspace_bytes, uint32_t num_particles)
 {
     Ctx c;
-    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes);
+    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes, num_particles);
     if (rc) return rc;
     D3P_REQUIRE(X_dev, "null data pointer");
     if (int rcm = validate_model(model, y_dev, "d3p_dpvi_logreg_run")) return rcm;
@@ -2761,6 +2825,14 @@ int d3p_dpvi_logreg_run(void* stream, const d3p_logreg_model* model, const d3p_d
         if (b + 1 < n_batches && (rc = enqueue_sampler(cb[nxt], K_next))) return rc;
     }
     return enqueue_sched_finish(c, (int)num_steps);
+}
+
+int d3p_dpvi_logreg_run(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+                        const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev,
+                        const float* y_dev, uint32_t num_steps, float* losses_dev, void* workspace_dev,
+                        size_t workspace_bytes)
+{
+    return logreg_run_k(stream, model, hyper, state, src, X_dev, y_dev, num_steps, losses_dev, workspace_dev, workspace_bytes, 1u);
 }
 
 int d3p_dpvi_logreg_set_run_form(int form)

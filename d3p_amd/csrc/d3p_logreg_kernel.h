@@ -76,6 +76,37 @@ __device__ __forceinline__ void px_sample_key(uint32_t j0, uint32_t j1, uint32_t
     threefry2x32(g0, g1, 1u, 3u, b, o1);
 }
 
+// Sample key of particle q of K for batch position p (numpyro Trace_ELBO(num_particles=K)):
+// K == 1: px_sample_key itself; K > 1: particle_key = split(split(jax_key, B)[p], K)[q], then guide_seed = split(particle_key)[1]
+// and sample_key = split(guide_seed)[1] as above.  The one place of the particle rule (the MeanFieldGuide eps of
+// d3p_px_eps_sites_particles starts from px_particle_key).
+__device__ __forceinline__ void px_particle_key(uint32_t j0, uint32_t j1, uint32_t B, uint32_t p, uint32_t K, uint32_t q,
+                                                uint32_t& k0, uint32_t& k1)
+{
+    k0 = tf_iota_word(j0, j1, 2ull * B, 2ull * p);
+    k1 = tf_iota_word(j0, j1, 2ull * B, 2ull * p + 1);
+    if (K > 1u) {
+        const uint32_t a = tf_iota_word(k0, k1, 2ull * K, 2ull * q), b = tf_iota_word(k0, k1, 2ull * K, 2ull * q + 1);
+        k0 = a;
+        k1 = b;
+    }
+}
+
+__device__ __forceinline__ void px_particle_sample_key(uint32_t j0, uint32_t j1, uint32_t B, uint32_t p, uint32_t K, uint32_t q,
+                                                       uint32_t& o0, uint32_t& o1)
+{
+    if (K == 1u) {
+        px_sample_key(j0, j1, B, p, o0, o1);
+        return;
+    }
+    uint32_t k0, k1, a, b, g0, g1;
+    px_particle_key(j0, j1, B, p, K, q, k0, k1);
+    threefry2x32(k0, k1, 0u, 2u, a, g0);
+    threefry2x32(k0, k1, 1u, 3u, a, g1);
+    threefry2x32(g0, g1, 0u, 2u, a, o0);
+    threefry2x32(g0, g1, 1u, 3u, b, o1);
+}
+
 
 
 // (row layout of a fixed-point accumulator replica, loss_split / loss_join: d3p_device.h)

@@ -2,6 +2,7 @@
 // directly), optimiser steps and the synthetic-table generator.
 #include "d3p_logreg_kernel.h"
 #include "d3p_logreg_wide.h"
+#include "d3p_logreg_particles.h"
 
 namespace d3p {
 
@@ -408,6 +409,53 @@ __global__ void k_px_keys(const uint32_t* __restrict__ jax_key, uint32_t B, uint
     skeys[2 * p + 1] = s1;
 }
 
+// Per-example, per-particle, per-site guide noise of a multi-site mean-field guide: k_px_eps_sites of d3p_rng.hip for the key of
+// particle q (px_particle_key) instead of example p's key.  Row (i, q) of eps = [normal(site_key_0) | normal(site_key_1) | ...].
+struct EpsSitesParticleArgs {
+    const uint32_t* jax_key;
+    uint32_t B_total, pos0, B_local, K;
+    int n_sites;
+    int32_t size[8];
+    int32_t row;     // sum of the sizes
+    float* eps;      // B_local x K x row
+};
+
+__global__ void __launch_bounds__(256) k_px_eps_sites_particles(EpsSitesParticleArgs a)
+{
+    const uint32_t i = blockIdx.x / a.K, q = blockIdx.x % a.K;
+    if (i >= a.B_local) return;
+    uint32_t k0, k1, t, r0, r1;
+    px_particle_key(a.jax_key[0], a.jax_key[1], a.B_total, a.pos0 + i, a.K, q, k0, k1);
+    threefry2x32(k0, k1, 0u, 2u, t, r0);   // guide seed = split(particle key)[1]
+    threefry2x32(k0, k1, 1u, 3u, t, r1);
+    float* row = a.eps + ((size_t)i * a.K + q) * a.row;
+    int off = 0;
+    for (int s = 0; s < a.n_sites; ++s) {
+        uint32_t c0, c1, s0, s1;
+        threefry2x32(r0, r1, 0u, 2u, c0, s0);   // rng, site_key = split(rng) at every sample statement
+        threefry2x32(r0, r1, 1u, 3u, c1, s1);
+        r0 = c0; r1 = c1;
+        const int n = a.size[s], half = (n + 1) >> 1;
+        for (int j = threadIdx.x; j < half; j += blockDim.x) {
+            const int j2 = j + half;
+            uint32_t wa, wb;
+            threefry2x32(s0, s1, (uint32_t)j, j2 < n ? (uint32_t)j2 : 0u, wa, wb);
+            row[off + j] = bits_to_normal(wa);
+            if (j2 < n) row[off + j2] = bits_to_normal(wb);
+        }
+        off += n;
+    }
+}
+
+// mean of the K particle losses of d3p_logreg_evaluate_particles
+__global__ void k_mean_losses(const float* __restrict__ losses, uint32_t K, float* __restrict__ out)
+{
+    if (threadIdx.x != 0) return;
+    float s = 0.f;
+    for (uint32_t q = 0; q < K; ++q) s += losses[q];
+    *out = s / (float)K;
+}
+
 }  // namespace d3p
 
 using namespace d3p;
@@ -469,6 +517,56 @@ int d3p_logreg_px_grads(void* stream, const d3p_logreg_model* model, const float
         return check_launch("k_logreg_wide");
     }
     return launch_main<1>(s, g, a);
+}
+
+size_t d3p_logreg_px_grads_particles_workspace(const d3p_logreg_model* model, uint32_t B, uint32_t num_particles)
+{
+    (void)num_particles;  // (the particle keys are derived in the kernel: the workspace of the single-particle stage)
+    return model ? px_ws_bytes(model, B) : 0;
+}
+
+// d3p_logreg_px_grads with num_particles ELBO particles per example: rows and losses are the means over the particles (eps_dev,
+// if given, is (B, K, D)).  K == 1: exactly d3p_logreg_px_grads.
+int d3p_logreg_px_grads_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
+                                  const float* y_dev, const uint8_t* mask_dev, uint32_t B, uint32_t num_particles, const float* eps_dev,
+                                  const uint32_t* jax_key_dev, float* px_loss_dev, float* px_grads_dev, float* meta_dev,
+                                  void* workspace_dev, size_t workspace_bytes)
+{
+    D3P_REQUIRE(num_particles >= 1, "d3p_logreg_px_grads_particles: num_particles must be >= 1");
+    if (num_particles == 1)
+        return d3p_logreg_px_grads(stream, model, params_dev, X_dev, y_dev, mask_dev, B, eps_dev, jax_key_dev, px_loss_dev, px_grads_dev,
+                                   meta_dev, workspace_dev, workspace_bytes);
+    D3P_REQUIRE(model && params_dev && X_dev && px_loss_dev && px_grads_dev && meta_dev && workspace_dev,
+                "d3p_logreg_px_grads_particles: null pointer");
+    if (int rc = validate_model(model, y_dev, "d3p_logreg_px_grads_particles")) return rc;
+    D3P_REQUIRE(eps_dev || jax_key_dev, "d3p_logreg_px_grads_particles: either eps_dev or jax_key_dev must be given");
+    D3P_REQUIRE(B >= 1, "d3p_logreg_px_grads_particles: B must be >= 1");
+    if (workspace_bytes < px_ws_bytes(model, B))
+        return fail(D3P_E_WORKSPACE, "d3p_logreg_px_grads_particles: workspace too small (%zu < %zu)", workspace_bytes,
+                    px_ws_bytes(model, B));
+    hipStream_t s = (hipStream_t)stream;
+    const int D = model->d + (model->intercept ? 1 : 0);
+    float* pack = (float*)workspace_dev;
+    hipLaunchKernelGGL(k_pack, dim3(cdiv(D, 256)), dim3(256), 0, s, *model, params_dev, pack);
+    hipLaunchKernelGGL(k_mask_meta, dim3(1), dim3(256), 0, s, mask_dev, B, meta_dev);
+    ParticleArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    fill_model_scalars(model, &pa.a);
+    pa.a.X = X_dev;
+    pa.a.y = y_dev;
+    pa.a.mask = mask_dev;
+    pa.a.eps_ext = eps_dev;
+    pa.a.pack = pack;
+    pa.a.px_grads = px_grads_dev;
+    pa.a.px_loss = px_loss_dev;
+    pa.a.meta = meta_dev;
+    pa.a.B = B;
+    pa.a.row_lo = 0;
+    pa.a.row_hi = B;
+    pa.a.clip = 1.0f;
+    pa.jax_key = jax_key_dev;
+    pa.K = num_particles;
+    return launch_particles<true>(s, pa, particles_blocks(D, true, B));
 }
 
 int d3p_clip_rows(void* stream, float* px_grads_dev, uint32_t B, uint32_t P, float c)
@@ -638,6 +736,71 @@ int d3p_logreg_evaluate_sites(void* stream, const d3p_logreg_model* model, const
                        (const float*)z, B, ll);
     hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(256), 0, s, *model, (const float*)ll, B, (const float*)lat, loss_dev);
     return check_launch("d3p_logreg_evaluate");
+}
+
+size_t d3p_logreg_evaluate_particles_workspace(const d3p_logreg_model* model, uint32_t B, uint32_t num_particles)
+{
+    if (!model) return 0;
+    return d3p_logreg_evaluate_workspace(model, B) + align_up(2 * (size_t)num_particles * sizeof(uint32_t), 256) +
+           align_up((size_t)num_particles * sizeof(float), 256);
+}
+
+// Mean over q of d3p_logreg_evaluate_sites at the key split(jax_key, K)[q] (numpyro Trace_ELBO(num_particles=K).loss; each
+// particle's guide draw is shared by the whole batch).  K == 1: exactly d3p_logreg_evaluate_sites.
+int d3p_logreg_evaluate_sites_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
+                                        const float* y_dev, uint32_t B, const uint32_t* jax_key_dev, const int32_t* site_sizes_host,
+                                        int32_t n_sites, uint32_t num_particles, float* loss_dev, void* workspace_dev, size_t workspace_bytes)
+{
+    D3P_REQUIRE(num_particles >= 1, "d3p_logreg_evaluate_particles: num_particles must be >= 1");
+    if (num_particles == 1)
+        return d3p_logreg_evaluate_sites(stream, model, params_dev, X_dev, y_dev, B, jax_key_dev, site_sizes_host, n_sites, loss_dev,
+                                         workspace_dev, workspace_bytes);
+    D3P_REQUIRE(model && jax_key_dev && loss_dev && workspace_dev, "d3p_logreg_evaluate_particles: null pointer");
+    const size_t base = d3p_logreg_evaluate_workspace(model, B);
+    if (workspace_bytes < d3p_logreg_evaluate_particles_workspace(model, B, num_particles))
+        return fail(D3P_E_WORKSPACE, "d3p_logreg_evaluate_particles: workspace too small");
+    uint32_t* keys = (uint32_t*)((char*)workspace_dev + base);
+    float* losses = (float*)((char*)keys + align_up(2 * (size_t)num_particles * sizeof(uint32_t), 256));
+    if (int rc = d3p_tf_split(stream, jax_key_dev, (int)num_particles, keys)) return rc;
+    for (uint32_t q = 0; q < num_particles; ++q)
+        if (int rc = d3p_logreg_evaluate_sites(stream, model, params_dev, X_dev, y_dev, B, keys + 2 * q, site_sizes_host, n_sites,
+                                               losses + q, workspace_dev, base))
+            return rc;
+    hipLaunchKernelGGL(k_mean_losses, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)losses, num_particles, loss_dev);
+    return check_launch("d3p_logreg_evaluate_particles");
+}
+
+int d3p_logreg_evaluate_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
+                                  const float* y_dev, uint32_t B, const uint32_t* jax_key_dev, uint32_t num_particles, float* loss_dev,
+                                  void* workspace_dev, size_t workspace_bytes)
+{
+    return d3p_logreg_evaluate_sites_particles(stream, model, params_dev, X_dev, y_dev, B, jax_key_dev, nullptr, 1, num_particles,
+                                               loss_dev, workspace_dev, workspace_bytes);
+}
+
+int d3p_px_eps_sites_particles(void* stream, const uint32_t* jax_key_dev, uint32_t B_total, uint32_t pos0, uint32_t B_local,
+                               uint32_t num_particles, const int32_t* site_sizes_host, int32_t n_sites, float* eps_dev)
+{
+    D3P_REQUIRE(num_particles >= 1, "d3p_px_eps_sites_particles: num_particles must be >= 1");
+    if (num_particles == 1) return d3p_px_eps_sites(stream, jax_key_dev, B_total, pos0, B_local, site_sizes_host, n_sites, eps_dev);
+    D3P_REQUIRE(jax_key_dev && site_sizes_host && eps_dev, "d3p_px_eps_sites_particles: null pointer");
+    D3P_REQUIRE(n_sites >= 1 && n_sites <= 8, "d3p_px_eps_sites_particles: 1 <= n_sites <= 8");
+    D3P_REQUIRE((uint64_t)pos0 + B_local <= B_total, "d3p_px_eps_sites_particles: pos0 + B_local must not exceed B_total");
+    D3P_REQUIRE((uint64_t)B_local * num_particles <= 0x7fffffffull, "d3p_px_eps_sites_particles: B_local x num_particles too large");
+    if (B_local == 0) return D3P_OK;
+    EpsSitesParticleArgs a;
+    a.jax_key = jax_key_dev; a.B_total = B_total; a.pos0 = pos0; a.B_local = B_local; a.K = num_particles; a.n_sites = n_sites;
+    a.eps = eps_dev;
+    int64_t row = 0;
+    for (int s = 0; s < n_sites; ++s) {
+        D3P_REQUIRE(site_sizes_host[s] >= 1, "d3p_px_eps_sites_particles: a site has at least one element (a scalar site has size 1)");
+        a.size[s] = site_sizes_host[s];
+        row += site_sizes_host[s];
+    }
+    D3P_REQUIRE(row <= 0x7fffffff, "d3p_px_eps_sites_particles: row too long");
+    a.row = (int32_t)row;
+    hipLaunchKernelGGL(k_px_eps_sites_particles, dim3(B_local * num_particles), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("d3p_px_eps_sites_particles");
 }
 
 int d3p_tf_randint(void* stream, const uint32_t* key_dev, uint64_t n, int32_t minval, int32_t maxval, int32_t* out_dev)

@@ -87,11 +87,21 @@ def concurrent_streams(n):
     raise _lib.D3PError(f"concurrent_streams: found only {len(chosen)} of {n} streams that run beside the current stream")
 
 
+def _refuse_particles(svi, who):
+    """The data-parallel engines run one ELBO particle per example: a DPSVI with Trace_ELBO(num_particles > 1) is refused
+    before anything touches a device (its single-GPU routes run the particles)."""
+    k = int(getattr(svi.loss, "num_particles", 1))
+    if k != 1:
+        raise NotImplementedError(f"{who}: Trace_ELBO(num_particles={k}) is not supported by the data-parallel engines "
+                                  "(one particle only); run it on one GPU through DPSVI")
+
+
 class HipEngine:
     """local_sums / finalize through libd3p_hip.so for one rank's shard."""
 
     def __init__(self, svi, X_local, y_local, n_rows_global, row_lo, row_hi, kind, batch_size, q=0.0,
                  suppress=False, **model_kwargs):
+        _refuse_particles(svi, type(self).__name__)
         _lib.require_device()
         self.svi, self.X, self.y = svi, _device_shard(X_local, "HipEngine: X"), _device_shard(y_local, "HipEngine: y")
         assert self.X.shape[0] == row_hi - row_lo
@@ -618,6 +628,7 @@ class VaeHipEngine:
     """local_sums / apply of one rank through libd3p_hip.so (d3p_dpvi_vae_local_sums / d3p_dpvi_vae_apply)."""
 
     def __init__(self, svi, **model_kwargs):
+        _refuse_particles(svi, "VaeHipEngine")
         _lib.require_device()
         if not svi._is_vae():
             raise _lib.D3PError("VaeHipEngine: the DPSVI object must hold a VAEModel / VAEGuide pair")
@@ -715,6 +726,7 @@ class GmmHipEngine:
     """local_sums / apply of one rank for the mixture model (d3p_dpvi_gmm_local_sums / d3p_dpvi_gmm_apply)."""
 
     def __init__(self, svi, **model_kwargs):
+        _refuse_particles(svi, "GmmHipEngine")
         _lib.require_device()
         if not svi._is_gmm():
             raise _lib.D3PError("GmmHipEngine: the DPSVI object must hold a GaussianMixtureModel / GaussianMixtureGuide pair")

@@ -250,12 +250,16 @@ class AutoDiagonalNormal:
 
 
 class Trace_ELBO:
-    """Marker for numpyro.infer.Trace_ELBO (num_particles = 1)."""
+    """Marker for numpyro.infer.Trace_ELBO(num_particles=K): each example's loss and gradient are the means over K guide draws,
+    particle q drawing from split(example key, K)[q] (K == 1: the example key itself).  ``vectorize_particles`` does not change
+    numpyro's results: accepted and ignored."""
 
-    def __init__(self, num_particles=1):
-        if num_particles != 1:
-            raise NotImplementedError("only num_particles=1 is supported")
-        self.num_particles = 1
+    def __init__(self, num_particles=1, vectorize_particles=True):
+        import numbers
+        if isinstance(num_particles, bool) or not isinstance(num_particles, numbers.Integral) or num_particles < 1:
+            raise ValueError(f"num_particles must be an integer >= 1 (got {num_particles!r})")
+        self.num_particles = int(num_particles)
+        self.vectorize_particles = bool(vectorize_particles)
 
 
 def _flat_params(params):

@@ -234,6 +234,11 @@ class DPSVI:
         self.loss = per_example_loss
         self.static_kwargs = static_kwargs
         self._ws = {}
+        # Trace_ELBO(num_particles=K): every example's loss and gradient are means over K guide draws (clipped after the mean)
+        self._num_particles = int(getattr(per_example_loss, "num_particles", 1))
+        if self._num_particles > 1 and isinstance(model, (GaussianMixtureModel, VAEModel)):
+            raise NotImplementedError(f"DPSVI: Trace_ELBO(num_particles={self._num_particles}) is supported for the logistic-regression "
+                                      "and Gaussian-mean models only")
 
     # ---------------------------------------------------------------- state helpers (svi.py:192-211)
     @staticmethod
@@ -546,6 +551,7 @@ class DPSVI:
         px_loss = torch.empty(B, dtype=torch.float32, device=X.device)
         px_grads = torch.empty((B, 2 * D), dtype=torch.float32, device=X.device)
         meta = torch.empty(2, dtype=torch.float32, device=X.device)
+        K = self._num_particles
         ws = self._workspace(lib.d3p_logreg_px_grads_workspace(C.byref(model), B), X.device, "px")
         eps = kwargs.get("_eps")
         multi = isinstance(self.guide, MeanFieldGuide)
@@ -558,11 +564,22 @@ class DPSVI:
             params = kern
             if eps is None:
                 sizes = (C.c_int32 * 2)(d, 1)
-                eps = torch.empty((B, D), dtype=torch.float32, device=X.device)
-                check(lib.d3p_px_eps_sites(stream_ptr(), ptr(jax_rng_key), B, 0, B, sizes, 2, ptr(eps)))
-        check(lib.d3p_logreg_px_grads(stream_ptr(), C.byref(model), ptr(params), ptr(X), ptr(y), ptr(mask_t), B,
-                                      ptr(eps), ptr(jax_rng_key), ptr(px_loss), ptr(px_grads), ptr(meta),
-                                      ptr(ws), ws.numel()))
+                if K > 1:   # (B, K, D): every particle's sites from its own key
+                    eps = torch.empty((B, K, D), dtype=torch.float32, device=X.device)
+                    check(lib.d3p_px_eps_sites_particles(stream_ptr(), ptr(jax_rng_key), B, 0, B, K, sizes, 2, ptr(eps)))
+                else:
+                    eps = torch.empty((B, D), dtype=torch.float32, device=X.device)
+                    check(lib.d3p_px_eps_sites(stream_ptr(), ptr(jax_rng_key), B, 0, B, sizes, 2, ptr(eps)))
+        if K > 1:
+            if eps is not None and tuple(eps.shape) != (B, K, D):
+                raise _lib.D3PError(f"_eps: expected shape {(B, K, D)} for {K} particles, got {tuple(eps.shape)}")
+            check(lib.d3p_logreg_px_grads_particles(stream_ptr(), C.byref(model), ptr(params), ptr(X), ptr(y), ptr(mask_t), B, K,
+                                                    ptr(eps), ptr(jax_rng_key), ptr(px_loss), ptr(px_grads), ptr(meta),
+                                                    ptr(ws), ws.numel()))
+        else:
+            check(lib.d3p_logreg_px_grads(stream_ptr(), C.byref(model), ptr(params), ptr(X), ptr(y), ptr(mask_t), B,
+                                          ptr(eps), ptr(jax_rng_key), ptr(px_loss), ptr(px_grads), ptr(meta),
+                                          ptr(ws), ws.numel()))
         if multi:
             grads = {"intercept_loc": px_grads[:, d], "intercept_std_log": px_grads[:, D + d],
                      "w_loc": px_grads[:, :d], "w_std_log": px_grads[:, D:D + d]}
@@ -883,15 +900,21 @@ class DPSVI:
         # kernel-order parameters + [sums | loss sum | n] + the new state + the loss in one allocation
         kern, sums, params, m, v, loss = torch.empty(5 * P + 3, dtype=torch.float32, device=dev).split((P, P + 2, P, P, P, 1))
         step = torch.empty_like(step0)
-        eps = torch.empty((B, D), dtype=torch.float32, device=dev)
+        K = self._num_particles
+        eps = torch.empty((B, K, D) if K > 1 else (B, D), dtype=torch.float32, device=dev)
         s = stream_ptr()
         check(lib.d3p_dpvi_leaves_begin(s, ptr(key0), n_leaves, ptr(params0), ptr(col_of), P, ptr(next_key), ptr(jax_key), ptr(leaf_keys),
                                         ptr(kern)))
-        check(lib.d3p_px_eps_sites(s, ptr(jax_key), B, 0, B, site_sizes, len(sites), ptr(eps)))
         st = self._state_struct(key0, 0, (step0, kern, m0, v0))      # (read only: the sums need the parameters, nothing else)
         ws = self._workspace(lib.d3p_dpvi_logreg_workspace(C.byref(model), C.byref(src)), dev)
-        check(lib.d3p_dpvi_logreg_local_sums(s, C.byref(model), C.byref(hyper), C.byref(st), C.byref(src), ptr(X), ptr(y), ptr(eps),
-                                             ptr(sums), ptr(ws), ws.numel()))
+        if K > 1:
+            check(lib.d3p_px_eps_sites_particles(s, ptr(jax_key), B, 0, B, K, site_sizes, len(sites), ptr(eps)))
+            check(lib.d3p_dpvi_logreg_local_sums_particles(s, C.byref(model), C.byref(hyper), C.byref(st), C.byref(src), ptr(X), ptr(y),
+                                                           ptr(eps), K, ptr(sums), ptr(ws), ws.numel()))
+        else:
+            check(lib.d3p_px_eps_sites(s, ptr(jax_key), B, 0, B, site_sizes, len(sites), ptr(eps)))
+            check(lib.d3p_dpvi_logreg_local_sums(s, C.byref(model), C.byref(hyper), C.byref(st), C.byref(src), ptr(X), ptr(y), ptr(eps),
+                                                 ptr(sums), ptr(ws), ws.numel()))
         check(lib.d3p_dpvi_leaves_finalize(s, C.byref(hyper), ptr(sums), ptr(col_of), ptr(leaf_keys), leaf_sizes, n_leaves, B,
                                            float(svi_state.observation_scale), ptr(params0), ptr(m0), ptr(v0), ptr(step0), ptr(params),
                                            ptr(m), ptr(v), ptr(step), ptr(loss), ptr(_grad_out)))
@@ -937,8 +960,13 @@ class DPSVI:
             st = self._state_struct(keybuf, 0, (step, params, m, v))
             frm = self._state_struct(key0, 0, (step0, params0, m0, v0))
             ws = self._workspace(lib.d3p_dpvi_logreg_workspace(C.byref(model), C.byref(src)), dev)
-            check(lib.d3p_dpvi_logreg_run_from(stream_ptr(), C.byref(model), C.byref(hyper), C.byref(st), C.byref(frm), C.byref(src),
-                                               0, ptr(X), ptr(y), 1, ptr(loss), ptr(ws), ws.numel()))
+            if self._num_particles > 1:
+                check(lib.d3p_dpvi_logreg_run_particles_from(stream_ptr(), C.byref(model), C.byref(hyper), C.byref(st), C.byref(frm),
+                                                             C.byref(src), 0, ptr(X), ptr(y), 1, self._num_particles, ptr(loss), ptr(ws),
+                                                             ws.numel()))
+            else:
+                check(lib.d3p_dpvi_logreg_run_from(stream_ptr(), C.byref(model), C.byref(hyper), C.byref(st), C.byref(frm), C.byref(src),
+                                                   0, ptr(X), ptr(y), 1, ptr(loss), ptr(ws), ws.numel()))
             return DPSVIState((step, params, m, v), keybuf[1].reshape(4, 4), svi_state.observation_scale), loss[0]
         step, params, m, v = _fresh_optim_state(svi_state.optim_state)
         keybuf = torch.empty((2, 16), dtype=torch.uint32, device=dev)
@@ -948,8 +976,15 @@ class DPSVI:
         sums = torch.empty(2 * D + 2, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         s = stream_ptr()
-        check(lib.d3p_dpvi_logreg_local_sums(s, C.byref(model), C.byref(hyper), C.byref(st), C.byref(src), ptr(X),
-                                             ptr(y), ptr(_eps), ptr(sums), ptr(ws), ws.numel()))
+        if self._num_particles > 1:
+            K = self._num_particles
+            if _eps is not None and tuple(_eps.shape) != (B, K, D):
+                raise _lib.D3PError(f"_eps: expected shape {(B, K, D)} for {K} particles, got {tuple(_eps.shape)}")
+            check(lib.d3p_dpvi_logreg_local_sums_particles(s, C.byref(model), C.byref(hyper), C.byref(st), C.byref(src), ptr(X),
+                                                           ptr(y), ptr(_eps), K, ptr(sums), ptr(ws), ws.numel()))
+        else:
+            check(lib.d3p_dpvi_logreg_local_sums(s, C.byref(model), C.byref(hyper), C.byref(st), C.byref(src), ptr(X),
+                                                 ptr(y), ptr(_eps), ptr(sums), ptr(ws), ws.numel()))
         check(lib.d3p_dpvi_logreg_finalize(s, C.byref(model), C.byref(hyper), C.byref(st), C.byref(src), ptr(sums),
                                            ptr(loss), ptr(_grad_out), ptr(ws), ws.numel()))
         new_state = DPSVIState((step, params, m, v), keybuf[1].reshape(4, 4), svi_state.observation_scale)
@@ -1013,6 +1048,12 @@ class DPSVI:
         n = params0.numel()
         self._require_sizes(n, 2 * self.model.latent_dim(d), N, y)
         nl = max(num_steps, 1)
+        K = self._num_particles
+        contiguous_state = (params0.dtype == m0.dtype == v0.dtype == torch.float32 and m0.numel() == n
+                            and v0.numel() == n and params0.is_contiguous() and m0.is_contiguous() and v0.is_contiguous()
+                            and key0.is_contiguous() and key0.dtype == torch.uint32 and step0.dtype == torch.int32)
+        if K > 1 and not contiguous_state:   # (the native particle loop is the run_from form only)
+            return self._run_steps_stepwise(svi_state, get_batch, batchifier_state, first_batch, num_steps, **kwargs)
         if (params0.dtype == m0.dtype == v0.dtype == torch.float32 and m0.numel() == n
                 and v0.numel() == n and params0.is_contiguous() and m0.is_contiguous() and v0.is_contiguous()
                 and key0.is_contiguous() and key0.dtype == torch.uint32 and step0.dtype == torch.int32):
@@ -1031,8 +1072,13 @@ class DPSVI:
             st = DpsviState(base + 4 * koff, 0, base, base + 4 * n, base + 8 * n, base + 4 * (3 * n + nl))
             frm = DpsviState(key0.data_ptr(), 0, params0.data_ptr(), m0.data_ptr(), v0.data_ptr(), step0.data_ptr())
             ws = self._workspace(lib.d3p_dpvi_logreg_workspace(C.byref(model), C.byref(src)), dev)
-            check(lib.d3p_dpvi_logreg_run_from(stream_ptr(), C.byref(model), C.byref(hyper), C.byref(st), C.byref(frm), C.byref(src),
-                                               int(first_batch), ptr(X), ptr(y), int(num_steps), base + 12 * n, ptr(ws), ws.numel()))
+            if K > 1:
+                check(lib.d3p_dpvi_logreg_run_particles_from(stream_ptr(), C.byref(model), C.byref(hyper), C.byref(st), C.byref(frm),
+                                                             C.byref(src), int(first_batch), ptr(X), ptr(y), int(num_steps), K,
+                                                             base + 12 * n, ptr(ws), ws.numel()))
+            else:
+                check(lib.d3p_dpvi_logreg_run_from(stream_ptr(), C.byref(model), C.byref(hyper), C.byref(st), C.byref(frm), C.byref(src),
+                                                   int(first_batch), ptr(X), ptr(y), int(num_steps), base + 12 * n, ptr(ws), ws.numel()))
             params, m, v, losses, tail = buf.split((n, n, n, nl, koff + 32 - 3 * n - nl))
             if params0.dim() != 1:
                 params, m, v = params.view_as(params0), m.view_as(m0), v.view_as(v0)
@@ -1154,8 +1200,21 @@ class DPSVI:
         params = self.optim.get_params(svi_state.optim_state).contiguous()
         model = self._model_struct(d, kwargs, 1.0)
         self._require_sizes(params.numel(), 2 * self.model.latent_dim(d), B, y)
-        ws = self._workspace(lib.d3p_logreg_evaluate_workspace(C.byref(model), B), X.device, "eval")
         loss = torch.empty(1, dtype=torch.float32, device=X.device)
+        K = self._num_particles
+        if K > 1:   # the mean over q of the single-particle loss at split(jax_key, K)[q]
+            ws = self._workspace(lib.d3p_logreg_evaluate_particles_workspace(C.byref(model), B, K), X.device, "eval")
+            if isinstance(self.guide, MeanFieldGuide):
+                kern = torch.empty_like(params)
+                kern[MeanFieldGuide.tree_from_kernel(d, X.device)] = params
+                sizes = (C.c_int32 * 2)(d, 1)
+                check(lib.d3p_logreg_evaluate_sites_particles(stream_ptr(), C.byref(model), ptr(kern), ptr(X), ptr(y), B, ptr(jax_rng_key),
+                                                              sizes, 2, K, ptr(loss), ptr(ws), ws.numel()))
+            else:
+                check(lib.d3p_logreg_evaluate_particles(stream_ptr(), C.byref(model), ptr(params), ptr(X), ptr(y), B, ptr(jax_rng_key), K,
+                                                        ptr(loss), ptr(ws), ws.numel()))
+            return loss[0]
+        ws = self._workspace(lib.d3p_logreg_evaluate_workspace(C.byref(model), B), X.device, "eval")
         if isinstance(self.guide, MeanFieldGuide):   # two sample sites, each with its own key; parameters into the kernels' order
             kern = torch.empty_like(params)
             kern[MeanFieldGuide.tree_from_kernel(d, X.device)] = params

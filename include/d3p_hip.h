@@ -765,6 +765,41 @@ size_t d3p_predict_vae_workspace(const d3p_vae_model* model, uint32_t B, uint32_
 int d3p_predict_vae(void* stream, const d3p_vae_model* model, const float* params_dev, const float* X_dev, uint32_t B, const uint32_t* key_dev,
                     uint32_t n, int32_t multi, const float* z_subst_dev, float* z_dev, int32_t* obs_dev, void* workspace_dev, size_t workspace_bytes);
 
+/* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
+ * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
+ * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The
+ * example's loss and gradient are the MEANS over its K particles; the mean gradient is what is clipped.  Every entry validates
+ * num_particles >= 1 and, at num_particles == 1, is exactly its single-particle counterpart.  K > 1 runs the two-kernel steps
+ * (k_logreg_particles + finalize) on one GPU: the data-parallel, chained and persistent forms are not reached. */
+/* d3p_logreg_px_grads, averaged over the particles; eps_dev (optional) is B x K x D. */
+size_t d3p_logreg_px_grads_particles_workspace(const d3p_logreg_model* model, uint32_t B, uint32_t num_particles);
+int d3p_logreg_px_grads_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
+                                  const float* y_dev, const uint8_t* mask_dev, uint32_t B, uint32_t num_particles, const float* eps_dev,
+                                  const uint32_t* jax_key_dev, float* px_loss_dev, float* px_grads_dev, float* meta_dev,
+                                  void* workspace_dev, size_t workspace_bytes);
+/* d3p_dpvi_logreg_local_sums with K particles (eps_dev optional, B x K x D); single GPU (row_lo == 0, row_hi == n_rows). */
+int d3p_dpvi_logreg_local_sums_particles(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+                                         const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev,
+                                         const float* y_dev, const float* eps_dev, uint32_t num_particles, float* sums_dev,
+                                         void* workspace_dev, size_t workspace_bytes);
+/* d3p_dpvi_logreg_run_from with K particles (explicit batches: DPSVI.update; Feistel / Poisson: the native run_steps loop); the
+ * workspace is d3p_dpvi_logreg_workspace's. */
+int d3p_dpvi_logreg_run_particles_from(void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
+                                       const d3p_dpsvi_state* state, const d3p_dpsvi_state* from, const d3p_batch_source* src,
+                                       uint32_t first_batch, const float* X_dev, const float* y_dev, uint32_t num_steps,
+                                       uint32_t num_particles, float* losses_dev, void* workspace_dev, size_t workspace_bytes);
+/* DPSVI.evaluate with K particles: the mean over q of d3p_logreg_evaluate(_sites) at the key split(jax_key, K)[q]. */
+size_t d3p_logreg_evaluate_particles_workspace(const d3p_logreg_model* model, uint32_t B, uint32_t num_particles);
+int d3p_logreg_evaluate_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
+                                  const float* y_dev, uint32_t B, const uint32_t* jax_key_dev, uint32_t num_particles, float* loss_dev,
+                                  void* workspace_dev, size_t workspace_bytes);
+int d3p_logreg_evaluate_sites_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
+                                        const float* y_dev, uint32_t B, const uint32_t* jax_key_dev, const int32_t* site_sizes_host,
+                                        int32_t n_sites, uint32_t num_particles, float* loss_dev, void* workspace_dev, size_t workspace_bytes);
+/* d3p_px_eps_sites for every particle: eps_dev is B_local x K x (sum of the site sizes). */
+int d3p_px_eps_sites_particles(void* stream, const uint32_t* jax_key_dev, uint32_t B_total, uint32_t pos0, uint32_t B_local,
+                               uint32_t num_particles, const int32_t* site_sizes_host, int32_t n_sites, float* eps_dev);
+
 #ifdef __cplusplus
 }
 #endif

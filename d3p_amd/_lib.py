@@ -16,7 +16,7 @@ _DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_ho
 
 D3P_BATCH_EXPLICIT, D3P_BATCH_FEISTEL, D3P_BATCH_POISSON = 0, 1, 2
 D3P_FAMILY_LOGREG, D3P_FAMILY_GAUSS_MEAN = 0, 1
-D3P_GUIDE_SOFTPLUS, D3P_GUIDE_EXP = 0, 1
+D3P_GUIDE_SOFTPLUS, D3P_GUIDE_EXP, D3P_GUIDE_EXP_SITES = 0, 1, 2
 
 
 class D3PError(RuntimeError):

@@ -203,6 +203,25 @@ __device__ __forceinline__ void threefry2x32(uint32_t k0, uint32_t k1, uint32_t 
     o1 = x1;
 }
 
+// The guide's seed for an example key (px0, px1): guide_seed = split(key)[1] (svi.py:289-290).
+__device__ __forceinline__ void px_guide_seed(uint32_t px0, uint32_t px1, uint32_t& r0, uint32_t& r1)
+{
+    uint32_t t;
+    threefry2x32(px0, px1, 0u, 2u, t, r0);  // split(key, 2): counts [0, 1 | 2, 3]; key 1 = (y1(0, 2), y1(1, 3))
+    threefry2x32(px0, px1, 1u, 3u, t, r1);
+}
+
+// numpyro's seed handler at a sample statement: `rng, site_key = split(rng)`.  (r0, r1) is the handler's key, advanced in place;
+// (k0, k1) the site's key.  A multi-site guide calls it once per site in program order (d3p_px_eps_sites, the run's sampler).
+__device__ __forceinline__ void seed_next_site(uint32_t& r0, uint32_t& r1, uint32_t& k0, uint32_t& k1)
+{
+    uint32_t c0, c1;
+    threefry2x32(r0, r1, 0u, 2u, c0, k0);
+    threefry2x32(r0, r1, 1u, 3u, c1, k1);
+    r0 = c0;
+    r1 = c1;
+}
+
 // Word j of jax's threefry_2x32(key, iota(n)): counts are split in two halves (odd n zero-padded).
 __device__ __forceinline__ uint32_t tf_iota_word(uint32_t k0, uint32_t k1, uint64_t n, uint64_t j)
 {

@@ -58,7 +58,10 @@ struct Workspace {
     unsigned long long* stamps;  // 2 x max_blocks
     void* poisson_ws;
     size_t poisson_bytes;
+    float* ieps;      // D3P_GUIDE_EXP_SITES: D3P_STEP_BATCH x B, the intercept site's eps per batch position (nullptr otherwise)
 };
+
+static inline bool is_sites(const d3p_logreg_model* m) { return m->guide_transform == D3P_GUIDE_EXP_SITES; }
 
 static size_t carve(const d3p_logreg_model* m, const d3p_batch_source* src, char* base, Workspace* ws,
                     Workspace* ws2 = nullptr)
@@ -97,6 +100,10 @@ static size_t carve(const d3p_logreg_model* m, const d3p_batch_source* src, char
     p = take(K * B * sizeof(uint32_t)); if (ws2) ws2->plist = (uint32_t*)p;
     p = take(K * P * sizeof(float)); if (ws2) ws2->noise = (float*)p;
     p = take(pb); if (ws2) ws2->poisson_ws = p;
+    // (behind everything else: the other regions keep their offsets)
+    const size_t ib = is_sites(m) ? K * B * sizeof(float) : 0;
+    p = take(ib); if (ws) ws->ieps = ib ? (float*)p : nullptr;
+    p = take(ib); if (ws2) ws2->ieps = ib ? (float*)p : nullptr;
     return off;
 }
 
@@ -187,7 +194,16 @@ struct RunInitCopy {  // d3p_dpvi_logreg_run_from: the optimiser state is copied
     unsigned long long* ll[3];  // nullable
     const float* ll_src[3];
     uint32_t ll_tag, ll_cols;   // cols = D3P_ACC_COLS(P): the row stride of ll[0]
+    int perm_d;                 // D3P_GUIDE_EXP_SITES: d -- `src` is in tree order, `dst` gets the kernels' column order (0: plain copy)
 };
+
+// D3P_GUIDE_EXP_SITES: the tree-order index of kernel column `col` (kernel order [w_loc (d), intercept_loc | w_std_log (d),
+// intercept_std_log], tree order [intercept_loc, intercept_std_log, w_loc (d), w_std_log (d)]: MeanFieldGuide.tree_from_kernel).
+// A run permutes its state once on entry (k_run_init) and once on exit (k_flush), never per step.
+__device__ __forceinline__ int sites_tree_index(int col, int d)
+{
+    return col < d ? 2 + col : col == d ? 0 : col == 2 * d + 1 ? 1 : col + 1;
+}
 
 // The first links of the key chain, derived on the host (host_key_chain) from the key the workspace's previous run ended with (its
 // pinned record): a run usually continues from that key.  k_run_init takes them only if the state's key IS `parent`, word for word;
@@ -217,7 +233,7 @@ __global__ void __launch_bounds__(1024) k_run_init(const uint32_t* __restrict__ 
             for (uint32_t i = tid - 64; i < cp.bar_words; i += nth) cp.bar[i] = 0u;
         if (cp.dst[0]) {
             for (int j = 0; j < 3; ++j)
-                for (int i = tid - 64; i < cp.n; i += (int)nth) cp.dst[j][i] = cp.src[j][i];
+                for (int i = tid - 64; i < cp.n; i += (int)nth) cp.dst[j][i] = cp.src[j][cp.perm_d ? sites_tree_index(i, cp.perm_d) : i];
             if (tid == 64) {
                 *cp.step_dst = *adam_step;
                 if (cp.by_value) *cp.batch_index_dst = cp.batch0;
@@ -316,10 +332,12 @@ struct FlushArgs {
     // is unpacked from the tagged words {fp32 | ll_tag} (parameters: row ll_tag & 1) into the caller's arrays
     const unsigned long long* ll[3];  // nullable
     uint32_t ll_tag;
+    int perm_d;  // D3P_GUIDE_EXP_SITES: d -- the caller's arrays take the state in tree order (staged in 3 P floats of dynamic LDS)
 };
 
 __global__ void __launch_bounds__(1024) k_flush(FlushArgs a)
 {
+    extern __shared__ float flush_stage[];
     const int tid = threadIdx.x, PA = D3P_ACC_COLS(a.P);
     if (tid < 16) a.key_out[tid] = a.sched->key[tid];
     if (tid >= 1 && tid <= 4 && a.host_status) {  // words 0..11 of the final key, three per 16-byte store, each store tagged
@@ -352,6 +370,13 @@ __global__ void __launch_bounds__(1024) k_flush(FlushArgs a)
     status_to_host(aborted);
     if (aborted) {  // the pending sums are incomplete: leave the state where the run stopped
         if (tid == 0 && a.loss_out) *a.loss_out = __builtin_nanf("");
+        if (a.perm_d) {  // (D3P_GUIDE_EXP_SITES: in tree order, as the caller's arrays always hold it)
+            for (int j = 0; j < 3; ++j)
+                for (int col = tid; col < a.P; col += blockDim.x) flush_stage[j * a.P + col] = a.state_in[j][col];
+            __syncthreads();
+            for (int j = 0; j < 3; ++j)
+                for (int col = tid; col < a.P; col += blockDim.x) a.state_out[j][sites_tree_index(col, a.perm_d)] = flush_stage[j * a.P + col];
+        }
         return;
     }
     if (a.ll[0]) {
@@ -398,11 +423,24 @@ __global__ void __launch_bounds__(1024) k_flush(FlushArgs a)
         const float mm = (1.0f - a.b1) * g + a.b1 * a.state_in[1][col];
         const float vv = (1.0f - a.b2) * g * g + a.b2 * a.state_in[2][col];
         const float xx = x0 - a.lr * (mm * inv_bc1) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vv * inv_bc2) + a.adam_eps);
-        a.state_out[0][col] = xx;
-        a.state_out[1][col] = mm;
-        a.state_out[2][col] = vv;
+        if (a.perm_d) {  // (state_in may BE state_out: every column is read before any is stored at its permuted place)
+            flush_stage[col] = xx;
+            flush_stage[a.P + col] = mm;
+            flush_stage[2 * a.P + col] = vv;
+        } else {
+            a.state_out[0][col] = xx;
+            a.state_out[1][col] = mm;
+            a.state_out[2][col] = vv;
+        }
     }
     x_bad = __syncthreads_or(x_bad);
+    if (a.perm_d)
+        for (int col = tid; col < a.P; col += blockDim.x) {
+            const int o = sites_tree_index(col, a.perm_d);
+            a.state_out[0][o] = flush_stage[col];
+            a.state_out[1][o] = flush_stage[a.P + col];
+            a.state_out[2][o] = flush_stage[2 * a.P + col];
+        }
     if (tid == 0) {
         long long lll = 0, lhh = 0;
         for (int r = 0; r < a.nrep; ++r) {
@@ -607,15 +645,20 @@ struct SamplerArgs {
     unsigned long long* own_mask;  // nullable: per step ceil(B / 64) words, bit l of word w = "position 64 w + l is this rank's" (k_owned_pack)
     int ppt;                  // batch positions per thread (1, or 4 for the large padded batches of a row-sharded rank: the per-step prefix --
                               // two dependent ChaCha blocks -- is then made by a quarter of the blocks)
+    float* ieps;              // D3P_GUIDE_EXP_SITES (k_sampler_sites): K x B, the intercept site's eps
 };
 
 // The sampler work of x-block bx (of gx) for step t of the batch.
 // (every ChaCha block of the sampler runs on a quad of lanes -- chacha20_block_quad, ~310 instructions instead of ~970 for the
 // one-lane form: the sampler is a chain of three dependent derivations per block, i.e. latency, and sits on the start-up path
 // of every run)
+// SITES (D3P_GUIDE_EXP_SITES): per position the two site keys of the guide -- 'w''s into skeys, and the intercept's one-word
+// eps, normal(site_key_1, ()), into ieps --; the aux block draws one Gaussian-mechanism key per parameter leaf, split(perturbation_key, 4)
+// (svi.py:487-491), and writes the leaves' normals into the noise row in the kernels' column order.
+template <bool SITES>
 __device__ __forceinline__ void sampler_block(const SamplerArgs& a, int bx, int gx, int t)
 {
-    __shared__ uint32_t sh_key[2][16], sh_jax[2], sh_rc[32];
+    __shared__ uint32_t sh_key[SITES ? 4 : 2][16], sh_jax[2], sh_rc[32];
     const int tid = threadIdx.x, quad = tid >> 2, q = tid & 3;
     StepSlot* slot = a.slots + t;
     const bool aux = bx == gx - 1;
@@ -659,7 +702,18 @@ __device__ __forceinline__ void sampler_block(const SamplerArgs& a, int bx, int 
             }
             if (owned) {  // six dependent threefry calls: skipped for positions another rank processes
                 uint32_t s0, s1;
-                px_sample_key(sh_jax[0], sh_jax[1], a.B, p, s0, s1);
+                if constexpr (SITES) {
+                    const uint32_t px0 = tf_iota_word(sh_jax[0], sh_jax[1], 2ull * a.B, 2ull * p);
+                    const uint32_t px1 = tf_iota_word(sh_jax[0], sh_jax[1], 2ull * a.B, 2ull * p + 1);
+                    uint32_t r0, r1, i0, i1, wa, wb;
+                    px_guide_seed(px0, px1, r0, r1);
+                    seed_next_site(r0, r1, s0, s1);   // 'w'
+                    seed_next_site(r0, r1, i0, i1);   // 'intercept'
+                    threefry2x32(i0, i1, 0u, 0u, wa, wb);   // a one-word stream: jax pads the counter pair with a zero
+                    a.ieps[(size_t)t * a.B + p] = bits_to_normal(wa);
+                } else {
+                    px_sample_key(sh_jax[0], sh_jax[1], a.B, p, s0, s1);
+                }
                 a.skeys[((size_t)t * a.B + p) * 2] = s0;
                 a.skeys[((size_t)t * a.B + p) * 2 + 1] = s1;
             }
@@ -672,7 +726,7 @@ __device__ __forceinline__ void sampler_block(const SamplerArgs& a, int bx, int 
         return;
     }
     // ---- aux block: per-site keys split(perturbation_key, 2) (svi.py:491), then the normals
-    if (quad < 2) {
+    if (quad < (SITES ? 4 : 2)) {
         uint32_t ka, kb;
         derive_child_quad(slot->pert_key, (uint32_t)quad, D3P_TAG_SPLIT, 0u, ka, kb);
         store_child(sh_key[quad], slot->pert_key, ka, kb);
@@ -697,6 +751,23 @@ __device__ __forceinline__ void sampler_block(const SamplerArgs& a, int bx, int 
         }
     }
     __syncthreads();
+    if constexpr (SITES) {
+        // leaves [intercept_loc, intercept_std_log, w_loc, w_std_log] -> kernel columns d, 2 D - 1, 0 .. d - 1, D .. D + d - 1
+        const int d = a.D - 1, bw = (d + 15) / 16;
+        for (int j = quad; j < 2 * bw + 2; j += (int)blockDim.x / 4) {
+            const int leaf = j < 2 * bw ? 2 + j / bw : j - 2 * bw, b = j < 2 * bw ? j % bw : 0, n = leaf < 2 ? 1 : d;
+            const int base = leaf == 0 ? d : leaf == 1 ? a.D + d : leaf == 2 ? 0 : a.D;
+            uint32_t w[4];
+            keystream_block_quad(sh_key[leaf], (uint32_t)b, w[0], w[1], w[2], w[3]);
+            float* dst = a.noise + (size_t)t * 2 * a.D + base;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = 16 * b + 4 * i + q;
+                if (e < n) dst[e] = bits_to_normal(w[i]);
+            }
+        }
+        return;
+    }
     // noise[site * D + e] = normal(site_key[site])[e]  (svi.py:487): ChaCha block e/16, word e%16; one quad per block
     const int blocks_per_site = (a.D + 15) / 16;
     for (int j = quad; j < 2 * blocks_per_site; j += (int)blockDim.x / 4) {
@@ -712,7 +783,8 @@ __device__ __forceinline__ void sampler_block(const SamplerArgs& a, int bx, int 
     }
 }
 
-__global__ void __launch_bounds__(256) k_sampler(SamplerArgs a) { sampler_block(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y); }
+__global__ void __launch_bounds__(256) k_sampler(SamplerArgs a) { sampler_block<false>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y); }
+__global__ void __launch_bounds__(256) k_sampler_sites(SamplerArgs a) { sampler_block<true>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y); }
 
 // ------------------------------------------------------------------------------------------
 // dense list of the batch positions a rank processes: valid (p < counts[1]) and row in [row_lo, row_hi).
@@ -1048,6 +1120,19 @@ struct Ctx {
     uint32_t K = 1;  // ELBO particles per example: K > 1 runs k_logreg_particles in two-kernel steps (main + k_finalize)
 };
 
+static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_source* src, bool allow_tail = true);
+
+// The geometry of k_logreg_main's step forms.  D3P_GUIDE_EXP_SITES at d = 512 has the tail geometry, which selects the lean chain
+// kernel (k_logreg_chain_sites); the generic kernel has no two-site tail form, so its launches there -- one launch per step, the
+// chained form when the lean kernel is not taken -- use the scalar-load geometry.
+static MainGeom generic_geom(const Ctx& c)
+{
+    if (!(is_sites(c.m) && c.g.tail)) return c.g;
+    Ctx t = c;
+    if (fill_geometry(&t, c.m, c.src, false) != D3P_OK) return c.g;  // (cannot fail: the scalar-load form holds D = 513)
+    return t.g;
+}
+
 // zeroed status words for a run form that does not end with k_flush: the reader must not take an earlier run's pinned record
 static hipError_t reset_status_words(const Ctx& c)
 {
@@ -1125,7 +1210,12 @@ static int enqueue_sampler(const Ctx& c, int K, Xchg* xchg)
 {
     SamplerArgs sa;
     fill_sampler_args(c, &sa);
-    hipLaunchKernelGGL(k_sampler, dim3(cdiv(c.src->B, 256u * (uint32_t)sa.ppt) + 1, K), dim3(256), 0, c.s, sa);
+    if (is_sites(c.m)) {
+        sa.ieps = c.ws.ieps;
+        hipLaunchKernelGGL(k_sampler_sites, dim3(cdiv(c.src->B, 256u * (uint32_t)sa.ppt) + 1, K), dim3(256), 0, c.s, sa);
+    } else {
+        hipLaunchKernelGGL(k_sampler, dim3(cdiv(c.src->B, 256u * (uint32_t)sa.ppt) + 1, K), dim3(256), 0, c.s, sa);
+    }
     int rc = check_launch("k_sampler");
     if (rc) return rc;
     static const bool full_mask = getenv("D3P_POISSON_FULL_MASK") != nullptr;   // developer switch: every rank makes the whole mask (round 3)
@@ -1346,6 +1436,7 @@ static int enqueue_fused_step(const Ctx& c, int g, int t, const StepSlot* prev_s
         a.n_list = &c.ws.slots[t].n_owned;
     }
     a.skeys = c.ws.skeys + (size_t)t * 2 * c.src->B;
+    if (is_sites(c.m)) a.eps_ext = c.ws.ieps + (size_t)t * c.src->B;  // (EPS == 2: the intercept's eps, see k_logreg_main)
     a.pack = c.ws.pack;
     a.partials = c.ws.partials;
     a.B = c.src->B;
@@ -1379,7 +1470,7 @@ static int enqueue_fused_step(const Ctx& c, int g, int t, const StepSlot* prev_s
     a.fuse.chain_slot = chain_slot;
     a.fuse.chain_t = chain_t;
     a.fuse.chain_last = chain_last;
-    MainGeom g2 = c.g;
+    MainGeom g2 = generic_geom(c);
     if (flush_only) g2.blocks = 1;
     if (chain_slot) g2.blocks += 1;
     return launch_main<2>(c.s, g2, a, e0, e1);
@@ -1576,10 +1667,12 @@ static int enqueue_chained_batch(const Ctx& c, int g0, int K, const StepSlot* pr
     a.row_lo = c.src->row_lo;
     a.row_hi = c.src->row_hi;
     a.clip = c.h->clip;
+    if (is_sites(c.m)) a.eps_ext = c.ws.ieps;  // (EPS == 2: the K rows of the intercept's eps; the kernel offsets by step)
     fill_fuse_common(c, &a.fuse, g0);
     a.fuse.chain_sched = c.ws.sched;
     ChainFuse& cf = a.chain;
-    cf.nw = (int)c.g.blocks;
+    const MainGeom gg = generic_geom(c);
+    cf.nw = (int)gg.blocks;
     cf.g0 = g0;
     cf.K = K;
     cf.slots = c.ws.slots;
@@ -1640,7 +1733,7 @@ static int enqueue_chained_batch(const Ctx& c, int g0, int K, const StepSlot* pr
         const bool icpt = c.g.tail;  // 512 features + intercept (D = 513): the ICPT instantiations
         // (data-parallel runs: the 16-wave updater form; D3P_XCHG_W8=1: the 8-wave form with two exchange workgroups per step)
         const bool w16 = (!xchg || xchg_updater_form(c)) && chain_w16_enabled();
-        if (lean_chain_ok(c, w16)) {
+        if (lean_chain_ok(c, w16) && (!is_sites(c.m) || (w16 && !xchg))) {   // (the two-site form: single-rank, 16 waves)
             const uint32_t nw = w16 ? chain16_blocks(c.items_expected) : c.g.blocks;
             ChainArgs ca;
             memset(&ca, 0, sizeof(ca));
@@ -1676,6 +1769,7 @@ static int enqueue_chained_batch(const Ctx& c, int g0, int K, const StepSlot* pr
             ca.c1_b = a.c1_b; ca.hz_b = a.hz_b; ca.log_prior_b = logf(c.m->prior_b);
             ca.gexp = a.gexp;
             ca.dbg = dev_dbg_flags();
+            ca.ieps_base = c.ws.ieps;
             if (xchg) {  // data-parallel run: the step's exchange rides in the launch
                 xchg_fill_dev(xchg, &ca.x, K);
                 ca.x.xflag = c.ws.xflags;
@@ -1695,7 +1789,7 @@ static int enqueue_chained_batch(const Ctx& c, int g0, int K, const StepSlot* pr
             const dim3 grid((uint32_t)K * (nw + (w16 ? 0u : 1u) + ((xchg && !w16) ? (uint32_t)D3P_XCHG_WGS : 0u))), block(64 * W);
             const bool plist = ca.plist_base != nullptr;
             const size_t lds = chain_lds_bytes(icpt, W);
-            const bool stamped = (ca.dbg & 32) && K >= 2 && (!xchg || (w16 && !icpt));  // D3P_DBG=32: the stamped instantiation + the phase anatomy on stderr
+            const bool stamped = (ca.dbg & 32) && K >= 2 && (!xchg || (w16 && !icpt)) && !is_sites(c.m);  // D3P_DBG=32: the stamped instantiation + the phase anatomy on stderr
             if (stamped) ca.stamps = c.ws.stamps;
             hipEvent_t e0 = nullptr, e1 = nullptr;
             if (!stamped) timing_pair(K, &e0, &e1);
@@ -1720,7 +1814,18 @@ static int enqueue_chained_batch(const Ctx& c, int g0, int K, const StepSlot* pr
         if (e0) hipExtLaunchKernelGGL((k_logreg_chain<PL_, ST_, IC_, true, 16>), grid, block, lds, c.s, e0, e1, 0, ca);         \
         else hipLaunchKernelGGL((k_logreg_chain<PL_, ST_, IC_, true, 16>), grid, block, lds, c.s, ca);                          \
     } while (0)
-            if (w16 && xchg) {
+            if (is_sites(c.m)) {
+                const void* fn = plist ? reinterpret_cast<const void*>(&k_logreg_chain_sites<true>)
+                                       : reinterpret_cast<const void*>(&k_logreg_chain_sites<false>);
+                if (int rc_ = ensure_dynamic_lds(fn, 96 * 1024, "k_logreg_chain_sites")) return rc_;
+                if (plist) {
+                    if (e0) hipExtLaunchKernelGGL(k_logreg_chain_sites<true>, grid, block, lds, c.s, e0, e1, 0, ca);
+                    else hipLaunchKernelGGL(k_logreg_chain_sites<true>, grid, block, lds, c.s, ca);
+                } else {
+                    if (e0) hipExtLaunchKernelGGL(k_logreg_chain_sites<false>, grid, block, lds, c.s, e0, e1, 0, ca);
+                    else hipLaunchKernelGGL(k_logreg_chain_sites<false>, grid, block, lds, c.s, ca);
+                }
+            } else if (w16 && xchg) {
                 if (stamped) {  // (the anatomy is taken at the production shape: owned lists, no intercept)
                     if (plist) D3P_CHAIN16_XCHG_LAUNCH(true, true, false); else D3P_CHAIN16_XCHG_LAUNCH(false, true, false);
                 } else {
@@ -1753,7 +1858,7 @@ static int enqueue_chained_batch(const Ctx& c, int g0, int K, const StepSlot* pr
             return print_chain_anatomy(c, nw, xchg != nullptr);
         }
     }
-    MainGeom g2 = c.g;
+    MainGeom g2 = gg;
     {
         // Pipelined geometry (D3P_NO_PIPELINED_STEPS=1 keeps one 16-wave workgroup per CU): the same number of workgroups
         // with 8 waves each, so two of them are resident per CU and the noise generation of step t + 1 overlaps with the
@@ -1763,13 +1868,13 @@ static int enqueue_chained_batch(const Ctx& c, int g0, int K, const StepSlot* pr
         // the next step just halves the occupancy of the working one (B = 32768: 44 -> 55 us per step).  The 12 % slack
         // admits Poisson batches padded to a quantile above 16 x workgroups (a few waves then take a third example and
         // generate its noise in the loop): 63.2 -> 68.6 k steps/s at q = 4096 / 1e6.
-        if (!off && c.g.full && c.g.V == 4 && c.g.NK == 1 && c.g.W == 16 && (uint64_t)c.src->B <= 18ull * c.g.blocks) {
+        if (!off && gg.full && gg.V == 4 && gg.NK == 1 && gg.W == 16 && (uint64_t)c.src->B <= 18ull * gg.blocks) {
             g2.W = 8;
             g2.lds = main_lds_bytes(c.D, g2.W);
             cf.pregen = 1;
         }
     }
-    g2.blocks = (uint32_t)K * (c.g.blocks + 1u);
+    g2.blocks = (uint32_t)K * (gg.blocks + 1u);
     a.dbg = dev_dbg_flags();
     if ((a.dbg & 32) && K >= 2) {  // developer diagnostic (D3P_DBG=32): phase stamps of the last two steps, printed to stderr
         a.stamps = c.ws.stamps;
@@ -2100,6 +2205,7 @@ static int run_fused_steps(const Ctx& c, const float* X, const float* y, uint32_
         cp.by_value = c.batch0_by_value ? 1 : 0;
         cp.batch0 = c.batch0;
         cp.batch_index_dst = c.src->batch_index;
+        cp.perm_d = is_sites(c.m) ? c.m->d : 0;  // (tree order in, the kernels' order inside the run)
     }
     // (data-parallel with the one-shot exchange: chained too when the shape has the dedicated kernel -- the exchange then rides
     // in the launch; D3P_XCHG_PER_STEP=1 keeps one step launch + one exchange launch per step)
@@ -2225,14 +2331,15 @@ static int run_fused_steps(const Ctx& c, const float* X, const float* y, uint32_
     fa.dp_scale = c.h->dp_scale; fa.clip = c.h->clip; fa.obs_scale = 1.0f / c.m->inv_obs;
     fa.lr = c.h->lr; fa.b1 = c.h->b1; fa.b2 = c.h->b2; fa.adam_eps = c.h->adam_eps;
     fa.inv_sg = 1.0 / (1099511627776.0 / (double)fabsf(c.h->clip));
-    hipLaunchKernelGGL(k_flush, dim3(1), dim3(1024), 0, c.s, fa);
+    fa.perm_d = is_sites(c.m) ? c.m->d : 0;  // (the kernels' order inside the run, tree order out)
+    hipLaunchKernelGGL(k_flush, dim3(1), dim3(1024), fa.perm_d ? 3 * (size_t)c.P * sizeof(float) : 0, c.s, fa);
     return check_launch("k_flush");
 }
 
 // launch geometry of the step kernels for this model and batch source (no device memory involved)
-static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_source* src)
+static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_source* src, bool allow_tail)
 {
-    int rc = main_geometry(model, src->B, &c->g);
+    int rc = main_geometry(model, src->B, &c->g, true, allow_tail);
     if (rc) return rc;
     if (need_owned_list(src)) {
         // a rank processes ~B * (rows held / rows total) positions (Poisson: <= B valid ones): size the grid for
@@ -2254,8 +2361,11 @@ static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_
 
 static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
                     const d3p_dpsvi_state* state, const d3p_batch_source* src, void* workspace_dev,
-                    size_t workspace_bytes, uint32_t num_particles = 1)
+                    size_t workspace_bytes, uint32_t num_particles = 1, bool allow_sites = false)
 {
+    D3P_REQUIRE(model, "null argument struct");
+    if (is_sites(model) && !allow_sites)  // (before anything else: no entry point but the single-GPU runs reads a tree-order state)
+        return fail(D3P_E_UNSUPPORTED, "D3P_GUIDE_EXP_SITES (state in tree order) is run by the single-GPU runs only");
     int rc = validate(model, hyper, state, src);
     if (rc) return rc;
     D3P_REQUIRE(workspace_dev, "null workspace");
@@ -2702,12 +2812,25 @@ static int logreg_run_from_k(void* stream, const d3p_logreg_model* model, const 
     d3p_batch_source s2 = *src;
     if (s2.kind != D3P_BATCH_EXPLICIT && !s2.batch_index) s2.batch_index = reinterpret_cast<uint32_t*>(workspace_dev);  // placeholder for validate(); set below
     Ctx c;
-    int rc = make_ctx(&c, stream, model, hyper, state, &s2, workspace_dev, workspace_bytes, num_particles);
+    int rc = make_ctx(&c, stream, model, hyper, state, &s2, workspace_dev, workspace_bytes, num_particles, true);
     if (rc) return rc;
     D3P_REQUIRE(X_dev, "null data pointer");
-    if (int rcm = validate_model(model, y_dev, "d3p_dpvi_logreg_run_from")) return rcm;
+    if (int rcm = validate_model(model, y_dev, "d3p_dpvi_logreg_run_from", true)) return rcm;
     D3P_REQUIRE(src->row_lo == 0 && src->row_hi == src->n_rows, "d3p_dpvi_logreg_run_from is the single-GPU path");
     D3P_REQUIRE(state->key_slot == 0, "d3p_dpvi_logreg_run_from: state->key_slot must be 0");
+    if (is_sites(model) && !use_fused_step(c))  // (the two-kernel steps -- wide rows, K > 1 particles -- have no two-site form)
+        return fail(D3P_E_UNSUPPORTED, "d3p_dpvi_logreg_run_from: D3P_GUIDE_EXP_SITES runs the fused step only (d + 1 <= 1024, one particle)");
+    if (is_sites(model)) {  // the first kernel permutes `from` into `state`: element i reads element perm(i), so they must not overlap
+        const size_t pb = (size_t)c.P * sizeof(float);
+        const float* srcs[3] = {from->params, from->adam_m, from->adam_v};
+        const float* dsts[3] = {state->params, state->adam_m, state->adam_v};
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const char *s0 = (const char*)srcs[i], *d0 = (const char*)dsts[j];
+                D3P_REQUIRE(s0 + pb <= d0 || d0 + pb <= s0,
+                            "d3p_dpvi_logreg_run_from: D3P_GUIDE_EXP_SITES needs `state`'s arrays apart from `from`'s (use d3p_dpvi_logreg_run in place)");
+            }
+    }
     // the run's own batch-index word: a spare word of the workspace (k_run_init stores first_batch there, k_flush advances it)
     s2.batch_index = reinterpret_cast<uint32_t*>(c.ws.scratch_state + 3 * c.P + 2);
     if (!use_fused_step(c)) {  // two-kernel steps (wide rows, K > 1 particles, D3P_NO_FUSED_STEP): copy here, then the in-place run
@@ -2791,11 +2914,29 @@ static int logreg_run_k(void* stream, const d3p_logreg_model* model, const d3p_d
                         void* workspace_dev, size_t workspace_bytes, uint32_t num_particles)
 {
     Ctx c;
-    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes, num_particles);
+    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes, num_particles, true);
     if (rc) return rc;
     D3P_REQUIRE(X_dev, "null data pointer");
-    if (int rcm = validate_model(model, y_dev, "d3p_dpvi_logreg_run")) return rcm;
+    if (int rcm = validate_model(model, y_dev, "d3p_dpvi_logreg_run", true)) return rcm;
     D3P_REQUIRE(src->row_lo == 0 && src->row_hi == src->n_rows, "d3p_dpvi_logreg_run is the single-GPU path");
+    if (is_sites(model)) {
+        if (!use_fused_step(c))
+            return fail(D3P_E_UNSUPPORTED, "d3p_dpvi_logreg_run: D3P_GUIDE_EXP_SITES runs the fused step only (d + 1 <= 1024, one particle)");
+        if (num_steps > 0) {
+            // in place: the tree-order state goes to the workspace's spare state rows first, and the run starts from there (its first
+            // kernel permutes it into the caller's arrays, k_flush permutes it back)
+            hipStream_t hs = (hipStream_t)stream;
+            const size_t pb = (size_t)c.P * sizeof(float);
+            float* tmp = c.ws.scratch_state;
+            D3P_HIP_TRY(hipMemcpyAsync(tmp, state->params, pb, hipMemcpyDeviceToDevice, hs));
+            D3P_HIP_TRY(hipMemcpyAsync(tmp + c.P, state->adam_m, pb, hipMemcpyDeviceToDevice, hs));
+            D3P_HIP_TRY(hipMemcpyAsync(tmp + 2 * c.P, state->adam_v, pb, hipMemcpyDeviceToDevice, hs));
+            d3p_dpsvi_state from = *state;
+            from.params = tmp; from.adam_m = tmp + c.P; from.adam_v = tmp + 2 * c.P;
+            c.from = &from;
+            return run_fused_steps(c, X_dev, y_dev, num_steps, losses_dev);
+        }
+    }
     if (use_fused_step(c)) return run_fused_steps(c, X_dev, y_dev, num_steps, losses_dev);
     if ((rc = enqueue_sched_init(c))) return rc;
     D3P_HIP_TRY(reset_status_words(c));  // (no waits, no fixed-point sums: stays 0)

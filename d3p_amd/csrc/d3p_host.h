@@ -41,14 +41,21 @@ inline int check_launch(const char* what)
     } while (0)
 
 // model spec checks shared by every entry point that takes a d3p_logreg_model; labels are only read by
-// the Bernoulli family
-inline int validate_model(const d3p_logreg_model* m, const void* y_dev, const char* what)
+// the Bernoulli family.  allow_sites: the entry point runs D3P_GUIDE_EXP_SITES (the single-GPU runs); every other one refuses it.
+inline int validate_model(const d3p_logreg_model* m, const void* y_dev, const char* what, bool allow_sites = false)
 {
     if (!m) return fail(D3P_E_INVALID_ARG, "%s: null model", what);
     if (!(m->d >= 1 && m->prior_w > 0.f && m->prior_b > 0.f && m->inv_obs > 0.f))
         return fail(D3P_E_INVALID_ARG, "%s: bad model (d >= 1, prior scales > 0 and inv_obs > 0 are required)", what);
-    if (m->guide_transform != D3P_GUIDE_SOFTPLUS && m->guide_transform != D3P_GUIDE_EXP)
+    if (m->guide_transform == D3P_GUIDE_EXP_SITES) {
+        if (!allow_sites)
+            return fail(D3P_E_UNSUPPORTED, "%s: guide transform D3P_GUIDE_EXP_SITES (state in tree order) is run by the single-GPU "
+                        "runs only", what);
+        if (!(m->intercept && m->family == D3P_FAMILY_LOGREG))
+            return fail(D3P_E_INVALID_ARG, "%s: D3P_GUIDE_EXP_SITES needs logistic regression with an intercept", what);
+    } else if (m->guide_transform != D3P_GUIDE_SOFTPLUS && m->guide_transform != D3P_GUIDE_EXP) {
         return fail(D3P_E_INVALID_ARG, "%s: unknown guide transform %d", what, m->guide_transform);
+    }
     if (m->family == D3P_FAMILY_LOGREG) {
         if (!y_dev) return fail(D3P_E_INVALID_ARG, "%s: null label pointer", what);
     } else if (m->family == D3P_FAMILY_GAUSS_MEAN) {

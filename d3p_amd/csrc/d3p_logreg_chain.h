@@ -140,7 +140,10 @@ struct ChainArgs {
     StepSlot* chain_slots;       // slots of the NEXT batch (key chain), K_next of them
     int32_t* adam_step;
     uint32_t* batch_index;
-    unsigned long long* stamps;  // STAMPS
+    union {
+        unsigned long long* stamps;  // STAMPS
+        const float* ieps_base;      // SITES (never with STAMPS): K x B, the intercept site's eps per batch position (the sampler's)
+    };
     uint64_t row_lo;
     double sg, inv_sg;
     uint32_t B;
@@ -172,9 +175,16 @@ static inline size_t chain_lds_bytes(bool icpt, int W = D3P_CHAIN_W)
 // XCHG: the data-parallel form (a.x.world > 0) -- its own instantiation, so that the single-rank kernel does not carry the
 // exchange workgroup's registers (61 SGPRs / 77 VGPRs alone, 82 / 80 with it: 2-3 % of the single-rank step)
 // W_: waves per workgroup (8 or 16, see the header); RU: accumulator replicas in use (<= D3P_ACC_R; the others stay zero)
-template <bool PLIST, bool STAMPS, bool ICPT = false, bool XCHG = false, int W_ = D3P_CHAIN_W, int RU = D3P_ACC_R>
-__global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
+// SITES (with ICPT, the single-rank 16-wave form: k_logreg_chain_sites): the two sample sites of D3P_GUIDE_EXP_SITES.  The lanes keep
+// their columns; only the generator changes.  'w''s eps is normal(site key 0, (512,)), whose threefry calls pair words (j, j + 256):
+// call j = 4 lane + n gives the lane's first-half column j, and column j + 256 -- the lane's second-half element n - 1 for n > 0,
+// the previous lane's element 3 for n = 0, the tail column 256 for lane 0.  So every call yields two used words, one DPP shift moves
+// the n = 0 words one lane down, and the last element of lane 63 -- the intercept, column 512 -- takes the sampler's one-word draw of
+// site key 1 (a.ieps_base).
+template <bool PLIST, bool STAMPS, bool ICPT, bool XCHG, int W_, int RU, bool SITES>
+__device__ __forceinline__ void logreg_chain_body(ChainArgs a)
 {
+    static_assert(!SITES || (ICPT && !XCHG && !STAMPS && W_ == 16), "the two-site form is the single-rank 16-wave intercept form");
     static_assert(W_ == 8 || W_ == 16, "8- or 16-wave workgroups");
     static_assert(RU >= 1 && RU <= D3P_ACC_R, "replicas in use");
     constexpr bool W16 = W_ == 16;
@@ -308,6 +318,7 @@ __global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
     float4 xa0 = make_float4(0.f, 0.f, 0.f, 0.f), xa1 = xa0, xb0 = xa0, xb1 = xa0;
     float ya = 0.f, yb = 0.f, xta = 0.f, xtb = 0.f;  // xt*: ICPT, the tail feature
     uint32_t ka0 = 0, ka1 = 0, kb0 = 0, kb1 = 0;
+    float ia = 0.f, ib = 0.f;  // SITES: the intercept's eps of the two examples
     // features of one table row for this lane: first half 16-byte aligned; ICPT: the second half starts one float off
     // (scalar loads), its last element is the intercept's constant 1
     auto load_x = [&](const float* xr, float4& x0, float4& x1, float& xt) {
@@ -330,12 +341,14 @@ __global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
         row_a = (size_t)((uint64_t)idx[p] - a.row_lo);
         ka0 = skeys[2 * p];
         ka1 = skeys[2 * p + 1];
+        if (SITES) ia = a.ieps_base[(size_t)step_t * a.B + p];
     }
     if (live2) {
         const uint32_t p = PLIST ? (a.plist_base + (size_t)step_t * a.B)[k2] : k2;
         row_b = (size_t)((uint64_t)idx[p] - a.row_lo);
         kb0 = skeys[2 * p];
         kb1 = skeys[2 * p + 1];
+        if (SITES) ib = a.ieps_base[(size_t)step_t * a.B + p];
     }
     auto fetch_rows = [&]() {
         if (live1) { load_x(a.X + row_a * DF, xa0, xa1, xta); ya = a.y[row_a]; }
@@ -382,10 +395,35 @@ __global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
     float* er = red + (size_t)wave * 2 * DL;   // the wave's row of the reduction buffer (partial sums, phase 4)
     struct Eps { Quad v0, v1; float vt, e2; };  // v0 / v1: the lane's 4 + 4 elements; vt: ICPT, the tail latent's noise; e2: the lane's share of -0.5 |eps|^2
     // (e2: the log q term of the loss is parameter-independent, so it is summed here)
+    float gen_ie = 0.f;  // SITES: the intercept's eps of the example gen() is called for
     auto gen = [&](uint32_t k0, uint32_t k1_, auto&& halfway) {   // halfway(): called in front of the last of the four pairs
         const uint32_t s0 = __builtin_amdgcn_readfirstlane(k0), s1 = __builtin_amdgcn_readfirstlane(k1_);  // wave-uniform keys
         Eps o;
         float e2 = 0.f, w0[4], w1[4];
+        if constexpr (SITES) {
+            float hb[4];  // words j + 256 of the lane's four calls
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                if (n == 3) halfway();
+                uint32_t b0, b1;
+                threefry2x32(s0, s1, (uint32_t)(4 * lane + n), (uint32_t)(4 * lane + n + 256), b0, b1);
+                w0[n] = bits_to_normal_wu(b0);
+                hb[n] = bits_to_normal_wu(b1);
+            }
+            const float up = __shfl_down(hb[0], 1);  // lane + 1's word 4 (lane + 1) + 256 = this lane's column 260 + 4 lane
+            w1[0] = hb[1]; w1[1] = hb[2]; w1[2] = hb[3];
+            w1[3] = lane == 63 ? gen_ie : up;
+            o.vt = __shfl(hb[0], 0);                 // column 256, every lane
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                e2 = __fmaf_rn(w0[n], w0[n], e2);
+                e2 = __fmaf_rn(w1[n], w1[n], e2);
+            }
+            o.v0 = Quad{d3p_v2f{w0[0], w0[1]}, d3p_v2f{w0[2], w0[3]}};
+            o.v1 = Quad{d3p_v2f{w1[0], w1[1]}, d3p_v2f{w1[2], w1[3]}};
+            o.e2 = -0.5f * e2;
+            return o;
+        }
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             if (n == 3) halfway();
@@ -412,7 +450,9 @@ __global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
     // noise 6.98, three quarters through 6.90, HERE -- in front of the last of the eight pairs -- 6.87 - 6.91, behind all of it
     // 6.95 - 6.99: later, and the burst meets the other step's accumulator atomics instead)
     auto nothing = [] {};
+    if constexpr (SITES) gen_ie = ia;
     if (live1) epa = gen(ka0, ka1, nothing);
+    if constexpr (SITES) gen_ie = ib;
     if (live2) epb = gen(kb0, kb1, [&] { fetch_rows(); });
     else fetch_rows();
     // W = 16, a step with up to THREE items per wave (an owned-position list a little longer than 2 x 16 x nw: a Poisson batch
@@ -434,6 +474,7 @@ __global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
         float4 x30, x31;
         load_x(a.X + row3 * DF, x30, x31, xt3);
         y3 = a.y[row3];
+        if constexpr (SITES) gen_ie = a.ieps_base[(size_t)step_t * a.B + p3];
         const Eps e3 = gen(q0, q1, nothing);
         *reinterpret_cast<float4*>(er + 4 * lane) = make_float4(e3.v0.lo.x, e3.v0.lo.y, e3.v0.hi.x, e3.v0.hi.y);
         *reinterpret_cast<float4*>(er + C1 + 4 * lane) = make_float4(e3.v1.lo.x, e3.v1.lo.y, e3.v1.hi.x, e3.v1.hi.y);
@@ -866,10 +907,13 @@ __global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
             load_x(a.X + rowb * DF, xs0[1], xs1[1], xts[1]);
             ys[1] = a.y[rowb];
             const uint32_t r0 = skeys[2 * pb], r1 = skeys[2 * pb + 1];
+            if constexpr (SITES) gen_ie = a.ieps_base[(size_t)step_t * a.B + p];
             es[0] = gen(q0, q1, nothing);
+            if constexpr (SITES) gen_ie = a.ieps_base[(size_t)step_t * a.B + pb];
             es[1] = gen(r0, r1, nothing);
             examples(std::integral_constant<int, 2>{}, xs0, xs1, xts, ys, es);
         } else {
+            if constexpr (SITES) gen_ie = a.ieps_base[(size_t)step_t * a.B + p];
             es[0] = gen(q0, q1, nothing);
             examples(std::integral_constant<int, 1>{}, xs0, xs1, xts, ys, es);
         }
@@ -1193,6 +1237,18 @@ __global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
         chain_step_ll(a.chain_sched, ll, a.chain_slots + step_t, step_t, step_t == a.K_next - 1, a.status, abort_code(D3P_ABORT_KEY_CHAIN, step_t));
     }
 #undef D3P_CSTAMP
+}
+
+template <bool PLIST, bool STAMPS, bool ICPT = false, bool XCHG = false, int W_ = D3P_CHAIN_W, int RU = D3P_ACC_R>
+__global__ void __launch_bounds__(64 * W_) k_logreg_chain(ChainArgs a)
+{
+    logreg_chain_body<PLIST, STAMPS, ICPT, XCHG, W_, RU, false>(a);
+}
+
+template <bool PLIST>
+__global__ void __launch_bounds__(64 * 16) k_logreg_chain_sites(ChainArgs a)
+{
+    logreg_chain_body<PLIST, false, true, false, 16, D3P_ACC_R, true>(a);
 }
 
 }  // namespace d3p

@@ -460,7 +460,12 @@ struct ExLoad {
 
 // FULL: every lane's column pairs exist (D == 2 * 64 * V * NK, no intercept) -> no guards at all.
 // EPS: where the guide noise comes from: 0 = generated on chip (threefry + erf_inv), 1 = read from
-// a.eps_ext (parity mode), -1 = decided at run time.
+// a.eps_ext (parity mode), -1 = decided at run time, 2 = the two sample sites of D3P_GUIDE_EXP_SITES (below).
+// EPS == 2 (scalar-load form only): 'w' draws normal(site_key_0, (d,)) and 'intercept' normal(site_key_1, ()).  The lane pairs
+// follow w's stream -- half = ceil(d / 2), pairs (c, c + half), c < half, each ONE threefry call of site key 0 (a.skeys) with both
+// words used, the second one only where c + half < d --, and the intercept (column d) is the second column of the pair
+// c = d - half: the last pair for odd d (whose w word jax pads), one pair more for even d (whose first column is none).  Its eps
+// comes from the sampler (a.eps_ext: one float per batch position; in MODE 3 the base of the launch's K rows).
 // NK == 1 (d <= 512): 1024-thread workgroups (<= 128 VGPRs); wider rows keep more columns per lane in registers,
 // so NK == 2 is built for 512-thread workgroups (<= 256 VGPRs, at most 8 waves) and NK >= 4 for 256-thread workgroups
 // (one wave per SIMD: the whole 512-entry register file, AGPRs included, instead of scratch).
@@ -493,6 +498,7 @@ __global__ void __launch_bounds__(D3P_MAIN_MAX_THREADS(V, NK)) k_logreg_main(Mai
         a.idx = cf.idx_base ? cf.idx_base + (size_t)step_t * a_in.B : nullptr;
         a.counts = cf.slots[step_t].counts;
         a.skeys = cf.skeys_base + (size_t)step_t * 2 * a_in.B;
+        if constexpr (EPS == 2) a.eps_ext = a_in.eps_ext + (size_t)step_t * a_in.B;
         if (cf.plist_base) {  // Poisson padding / row-sharded ranks: the step's valid, owned positions
             a.plist = cf.plist_base + (size_t)step_t * a_in.B;
             a.n_list = &cf.slots[step_t].n_owned;
@@ -845,7 +851,7 @@ __global__ void __launch_bounds__(D3P_MAIN_MAX_THREADS(V, NK)) k_logreg_main(Mai
             c0[n] = 64 * V * k + V * lane + i;
             c1[n] = c0[n] + half;
             ok0[n] = FULL || (c0[n] < half);
-            ok1[n] = FULL || (ok0[n] && (c1[n] < D));
+            ok1[n] = EPS == 2 ? (c1[n] < D) : (FULL || (ok0[n] && (c1[n] < D)));
         }
 
     float accg0[NC], acch0[NC], accg1[NC], acch1[NC];
@@ -899,6 +905,7 @@ __global__ void __launch_bounds__(D3P_MAIN_MAX_THREADS(V, NK)) k_logreg_main(Mai
         if (!eps_from_mem) {
             L.k0 = a.skeys[2 * p];
             L.k1 = a.skeys[2 * p + 1];
+            if (EPS == 2) L.et = a.eps_ext[p];  // the intercept's eps
         } else {
             const float* er = a.eps_ext + (size_t)p * D;
             if (TAIL) L.et = er[half - 1];
@@ -1044,6 +1051,16 @@ __global__ void __launch_bounds__(D3P_MAIN_MAX_THREADS(V, NK)) k_logreg_main(Mai
                     }
 #pragma unroll
                     for (int n = 0; n < NC && n < 4; ++n) { e0[n] = t0[n]; e1[n] = t1[n]; }
+                } else if constexpr (EPS == 2) {
+#pragma unroll
+                    for (int n = 0; n < NC; ++n) {
+                        const bool w1 = c1[n] < a.d;
+                        uint32_t b0, b1;
+                        threefry2x32(cur.k0, cur.k1, (uint32_t)c0[n], w1 ? (uint32_t)c1[n] : 0u, b0, b1);
+                        const float v0 = bits_to_normal_wu(b0), v1 = bits_to_normal_wu(b1);
+                        e0[n] = ok0[n] ? v0 : 0.f;
+                        e1[n] = w1 ? v1 : (c1[n] == a.d ? cur.et : 0.f);
+                    }
                 } else {
 #pragma unroll
                     for (int n = 0; n < NC; ++n) {
@@ -1342,7 +1359,10 @@ static int main_geometry(const d3p_logreg_model* m, uint32_t B, MainGeom* g, boo
     g->full = vec && g->NK > 0 && (D == 2 * 64 * g->V * g->NK) && m->family == D3P_FAMILY_LOGREG;
     // full tile of features + intercept column (d = 512 or 1024 with an intercept: examples/logistic_regression.py)
     static const bool no_tail = getenv("D3P_NO_TAIL_TILE") != nullptr;  // developer switch: the scalar-load form instead
-    g->tail = allow_tail && !no_tail && m->intercept && (m->d == 512 || m->d == 1024) && m->family == D3P_FAMILY_LOGREG;
+    // (D3P_GUIDE_EXP_SITES: at d = 512 the tail geometry selects the lean chain kernel, which has a two-site form
+    // (k_logreg_chain_sites); k_logreg_main has none -- its forms take the scalar-load geometry there, see generic_geom)
+    g->tail = allow_tail && !no_tail && m->intercept && (m->d == 512 || m->d == 1024) && m->family == D3P_FAMILY_LOGREG &&
+              (m->guide_transform != D3P_GUIDE_EXP_SITES || m->d == 512);
     if (g->tail) {
         g->V = 4;
         g->NK = m->d / 512;
@@ -1422,6 +1442,18 @@ static int launch_main(hipStream_t s, const MainGeom& g, const MainArgs& a, hipE
     else                                                                                                                  \
         hipLaunchKernelGGL((k_logreg_main<4, NK_, MODE, true, E_, true>), dim3(g.blocks), dim3(64 * g.W), g.lds, s, a);     \
     return check_launch("k_logreg_main")
+    if (a.gexp == D3P_GUIDE_EXP_SITES) {  // two sample sites: the scalar-load form (main_geometry), the fused step modes only
+        if (MODE == 0 || MODE == 1 || g.V != 1 || g.tail || g.wide)
+            return fail(D3P_E_UNSUPPORTED, "logreg kernel: D3P_GUIDE_EXP_SITES runs the fused step of the scalar-load form only");
+        if constexpr (MODE == 2 || MODE == 3) {
+            switch (g.NK) {
+            case 1: D3P_LAUNCH_F(1, 1, false, 2);
+            case 2: D3P_LAUNCH_F(1, 2, false, 2);
+            case 4: D3P_LAUNCH_F(1, 4, false, 2);
+            default: D3P_LAUNCH_F(1, 8, false, 2);
+            }
+        }
+    }
     if constexpr (MODE == 3) {  // D3P_DBG=32: the stamped instantiation of the headline tile
         if ((a.dbg & 32) && a.stamps && g.V == 4 && g.full && !g.tail && g.NK == 1 && !a.eps_ext) {
             hipLaunchKernelGGL((k_logreg_main<4, 1, 3, true, 0, false, true>), dim3(g.blocks), dim3(64 * g.W), g.lds, s, a);
@@ -1478,7 +1510,7 @@ static void fill_model_scalars(const d3p_logreg_model* m, MainArgs* a)
     const int D = m->d + (m->intercept ? 1 : 0);
     a->d = m->d;
     a->D = D;
-    a->half = (D + 1) / 2;
+    a->half = m->guide_transform == D3P_GUIDE_EXP_SITES ? (m->d + 1) / 2 : (D + 1) / 2;  // (EPS == 2: the pairs of w's stream)
     a->icpt = m->intercept ? 1 : 0;
     a->A_scale = m->inv_obs * m->lik_scale;
     a->c1_w = m->inv_obs / (m->prior_w * m->prior_w);

@@ -154,16 +154,13 @@ __global__ void __launch_bounds__(256) k_px_eps_sites(EpsSitesArgs a)
     if (i >= a.B_local) return;
     const uint32_t p = a.pos0 + i, j0 = a.jax_key[0], j1 = a.jax_key[1];
     const uint32_t px0 = tf_iota_word(j0, j1, 2ull * a.B_total, 2ull * p), px1 = tf_iota_word(j0, j1, 2ull * a.B_total, 2ull * p + 1);
-    uint32_t t, r0, r1;
-    threefry2x32(px0, px1, 0u, 2u, t, r0);   // split(key, 2): counts [0, 1 | 2, 3]; key 1 = (y1(0, 2), y1(1, 3)), key 0 = (y0(0, 2), y0(1, 3))
-    threefry2x32(px0, px1, 1u, 3u, t, r1);   // (r0, r1) = the guide seed
+    uint32_t r0, r1;
+    px_guide_seed(px0, px1, r0, r1);
     float* row = a.eps + (size_t)i * a.row;
     int off = 0;
     for (int s = 0; s < a.n_sites; ++s) {
-        uint32_t c0, c1, k0, k1;
-        threefry2x32(r0, r1, 0u, 2u, c0, k0);
-        threefry2x32(r0, r1, 1u, 3u, c1, k1);
-        r0 = c0; r1 = c1;                    // the handler's key after this site
+        uint32_t k0, k1;
+        seed_next_site(r0, r1, k0, k1);
         const int n = a.size[s], half = (n + 1) >> 1;
         for (int j = threadIdx.x; j < half; j += blockDim.x) {
             const int j2 = j + half;

@@ -424,17 +424,14 @@ __global__ void __launch_bounds__(256) k_px_eps_sites_particles(EpsSitesParticle
 {
     const uint32_t i = blockIdx.x / a.K, q = blockIdx.x % a.K;
     if (i >= a.B_local) return;
-    uint32_t k0, k1, t, r0, r1;
+    uint32_t k0, k1, r0, r1;
     px_particle_key(a.jax_key[0], a.jax_key[1], a.B_total, a.pos0 + i, a.K, q, k0, k1);
-    threefry2x32(k0, k1, 0u, 2u, t, r0);   // guide seed = split(particle key)[1]
-    threefry2x32(k0, k1, 1u, 3u, t, r1);
+    px_guide_seed(k0, k1, r0, r1);          // guide seed = split(particle key)[1]
     float* row = a.eps + ((size_t)i * a.K + q) * a.row;
     int off = 0;
     for (int s = 0; s < a.n_sites; ++s) {
-        uint32_t c0, c1, s0, s1;
-        threefry2x32(r0, r1, 0u, 2u, c0, s0);   // rng, site_key = split(rng) at every sample statement
-        threefry2x32(r0, r1, 1u, 3u, c1, s1);
-        r0 = c0; r1 = c1;
+        uint32_t s0, s1;
+        seed_next_site(r0, r1, s0, s1);     // rng, site_key = split(rng) at every sample statement
         const int n = a.size[s], half = (n + 1) >> 1;
         for (int j = threadIdx.x; j < half; j += blockDim.x) {
             const int j2 = j + half;
@@ -756,6 +753,7 @@ int d3p_logreg_evaluate_sites_particles(void* stream, const d3p_logreg_model* mo
         return d3p_logreg_evaluate_sites(stream, model, params_dev, X_dev, y_dev, B, jax_key_dev, site_sizes_host, n_sites, loss_dev,
                                          workspace_dev, workspace_bytes);
     D3P_REQUIRE(model && jax_key_dev && loss_dev && workspace_dev, "d3p_logreg_evaluate_particles: null pointer");
+    if (int rc = validate_model(model, y_dev, "d3p_logreg_evaluate_particles")) return rc;   // (before the key split's launch)
     const size_t base = d3p_logreg_evaluate_workspace(model, B);
     if (workspace_bytes < d3p_logreg_evaluate_particles_workspace(model, B, num_particles))
         return fail(D3P_E_WORKSPACE, "d3p_logreg_evaluate_particles: workspace too small");

@@ -390,7 +390,9 @@ class DPSVI:
             return None
         return _batch_array(args[1]).to(torch.float32)
 
-    def _model_struct(self, d, kwargs, observation_scale):
+    def _model_struct(self, d, kwargs, observation_scale, sites=False):
+        """The C model struct; ``sites``: MeanFieldGuide in the native run loop (D3P_GUIDE_EXP_SITES: two sample sites, four leaves,
+        the state in tree order)."""
         kw = dict(self.static_kwargs)
         kw.update(kwargs)
         n_total = self.model.num_obs_total((), kw)
@@ -401,6 +403,7 @@ class DPSVI:
         return LogregModel(int(d), int(m.intercept), m.prior_scale, m.intercept_prior_scale,
                            float(lik_scale), 1.0 / float(observation_scale),
                            _lib.D3P_FAMILY_GAUSS_MEAN if gauss else _lib.D3P_FAMILY_LOGREG,
+                           _lib.D3P_GUIDE_EXP_SITES if sites else
                            _lib.D3P_GUIDE_EXP if self.guide.transform == "exp" else _lib.D3P_GUIDE_SOFTPLUS,
                            m.obs_scale if gauss else 0.0)
 
@@ -855,6 +858,11 @@ class DPSVI:
         return (isinstance(self.model, LogisticRegression) and isinstance(self.guide, MeanFieldGuide)
                 and isinstance(self.optim, Adam) and self._rng_suite is strong_rng)
 
+    def _sites_fusable(self):
+        """The example's guide in the native run loop (one particle): D3P_GUIDE_EXP_SITES, which takes the state in tree order and runs
+        the same steps as ``_update_leaves``."""
+        return self._leaves_fusable() and self._num_particles == 1
+
     def _update_leaves(self, svi_state, *args, mask=True, _grad_out=None, **kwargs):
         """DPSVI.update for the example's own guide (four parameter leaves, two sample sites) around the FUSED clipped sums: the step's
         keys and the parameters in the kernels' column order (d3p_dpvi_leaves_begin), every sample site's eps from its own key
@@ -1018,7 +1026,8 @@ class DPSVI:
                 # (float64 / integer-labelled / strided tables: the native loops read contiguous float32 rows in place; get_batch + update
                 #  gather and convert per step)
                 return self._run_steps_stepwise(svi_state, get_batch, batchifier_state, first_batch, num_steps, **kwargs)
-        if info is None or info.rng_suite is not strong_rng or not (self._gmm_fusable() or self._is_vae() or self._fusable()):
+        if info is None or info.rng_suite is not strong_rng or not (self._gmm_fusable() or self._is_vae() or self._fusable()
+                                                                     or self._sites_fusable()):
             # no native loop for this combination (sampling with replacement, split_batchify_data's epochs, another rng_suite,
             # the stage-wise optimisers): the same steps through the API-parity path -- get_batch + update, one call each,
             # still without a host synchronisation between them
@@ -1040,7 +1049,13 @@ class DPSVI:
             raise _lib.D3PError("run_steps: dataset arrays must be contiguous float32 CUDA tensors")
         N, d = X.shape
         dev = X.device
-        model = self._model_struct(d, kwargs, svi_state.observation_scale)
+        sites = self._sites_fusable()
+        model = self._model_struct(d, kwargs, svi_state.observation_scale, sites=sites)
+        if sites:
+            src0 = BatchSource(info.kind, info.batch_size, float(info.q), int(info.suppress), None, None, None, N, 0, N)
+            if not lib.d3p_dpvi_logreg_fused_step_supported(C.byref(model), C.byref(src0)):
+                # (rows too wide for the fused step: the two-kernel steps have no two-site form)
+                return self._run_steps_stepwise(svi_state, get_batch, batchifier_state, first_batch, num_steps, **kwargs)
         hyper = self._hyper()
         bkey = strong_rng._key(batchifier_state)          # (a 16-word CUDA key: anything else is a TypeError, not an address)
         step0, params0, m0, v0 = svi_state.optim_state

@@ -169,7 +169,13 @@ typedef struct {
                               *   (examples/simple_gaussian_posterior.py:51-65; y_dev unused, intercept must be 0) */
     int32_t guide_transform; /* D3P_GUIDE_SOFTPLUS: scale = softplus(u) (AutoDiagonalNormal);
                               * D3P_GUIDE_EXP: scale = exp(u) (the hand-written guides of the examples,
-                              *   examples/simple_gaussian_posterior.py:77-81: mu_loc, mu_std_log) */
+                              *   examples/simple_gaussian_posterior.py:77-81: mu_loc, mu_std_log);
+                              * D3P_GUIDE_EXP_SITES: scale = exp(u), two sample sites and four parameter leaves (the guide of
+                              *   examples/logistic_regression.py:67-86, intercept = 1): 'w' and 'intercept' draw their eps from
+                              *   their own site keys, the Gaussian mechanism draws one key per leaf, and params / adam_m / adam_v
+                              *   are in tree order [intercept_loc, intercept_std_log, w_loc (d), w_std_log (d)].  Accepted by the
+                              *   single-GPU runs only (d3p_dpvi_logreg_run, _run_from, _run_particles_from with one particle,
+                              *   _run_status); every other entry point refuses it before any launch. */
     float lik_sigma;         /* observation std of D3P_FAMILY_GAUSS_MEAN */
 } d3p_logreg_model;
 
@@ -177,6 +183,7 @@ typedef struct {
 #define D3P_FAMILY_GAUSS_MEAN 1
 #define D3P_GUIDE_SOFTPLUS 0
 #define D3P_GUIDE_EXP 1
+#define D3P_GUIDE_EXP_SITES 2
 
 /* _compute_per_example_gradients for the logistic-regression + AutoDiagonalNormal workload
  * (svi.py:238-308).  params_dev = [auto_loc (D) | auto_scale unconstrained (D)].

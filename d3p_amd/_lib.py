@@ -255,6 +255,7 @@ SIGNATURES = {
     "d3p_predict_vae": (C.c_int, [_V, _V, _V, _V, _U32, _V, _U32, _I32, _V, _V, _V, _V, _SZ]),
     # multi-particle ELBO (Trace_ELBO(num_particles=K)): added symbols, ABI 9 unchanged
     "d3p_logreg_px_grads_particles_workspace": (_SZ, [_PM, _U32, _U32]),
+    "d3p_logreg_particles_max_latent": (C.c_int, [C.c_int]),
     "d3p_logreg_px_grads_particles": (C.c_int, [_V, _PM, _V, _V, _V, _V, _U32, _U32, _V, _V, _V, _V, _V, _V, _SZ]),
     "d3p_dpvi_logreg_local_sums_particles": (C.c_int, [_V, _PM, _PH, _PS, _PB, _V, _V, _V, _U32, _V, _V, _SZ]),
     "d3p_dpvi_logreg_run_particles_from": (C.c_int, [_V, _PM, _PH, _PS, _PS, _PB, _U32, _V, _V, _U32, _U32, _V, _V, _SZ]),

@@ -946,12 +946,20 @@ k_reduce_partials(const float* __restrict__ parts, uint32_t nparts, uint32_t nco
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t col = blockIdx.x * 64 + lane;
     lds[wave][lane] = col < ncols ? strided_rows_sum(parts, nparts, ncols, col, wave) : 0.f;
+    // the last two columns (loss sum, count) in k_finalize's order -- lanes stride the rows -- so that the two-call form of a step
+    // (these sums + d3p_dpvi_logreg_finalize) and its run form (k_finalize) add the loss alike, bit for bit
+    float loss_sum = 0.f, n = 0.f;
+    const bool tail = ncols >= 2 && blockIdx.x * 64 + 64 > ncols - 2;  // (block-uniform)
+    if (wave == 0 && tail) {
+        loss_sum = wave_column_sum(parts, nparts, ncols, ncols - 2, lane);
+        n = wave_column_sum(parts, nparts, ncols, ncols - 1, lane);
+    }
     __syncthreads();
     if (wave == 0 && col < ncols) {
         float tot = 0.f;
 #pragma unroll
         for (int w = 0; w < D3P_FIN_W; ++w) tot += lds[w][lane];
-        sums[col] = tot;
+        sums[col] = col == ncols - 2 ? loss_sum : col == ncols - 1 ? n : tot;
     }
 }
 
@@ -1120,7 +1128,8 @@ struct Ctx {
     uint32_t K = 1;  // ELBO particles per example: K > 1 runs k_logreg_particles in two-kernel steps (main + k_finalize)
 };
 
-static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_source* src, bool allow_tail = true);
+static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_source* src, bool allow_tail = true,
+                         bool particles = false);
 
 // The geometry of k_logreg_main's step forms.  D3P_GUIDE_EXP_SITES at d = 512 has the tail geometry, which selects the lean chain
 // kernel (k_logreg_chain_sites); the generic kernel has no two-site tail form, so its launches there -- one launch per step, the
@@ -2337,9 +2346,9 @@ static int run_fused_steps(const Ctx& c, const float* X, const float* y, uint32_
 }
 
 // launch geometry of the step kernels for this model and batch source (no device memory involved)
-static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_source* src, bool allow_tail)
+static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_source* src, bool allow_tail, bool particles)
 {
-    int rc = main_geometry(model, src->B, &c->g, true, allow_tail);
+    int rc = main_geometry(model, src->B, &c->g, true, allow_tail, particles);
     if (rc) return rc;
     if (need_owned_list(src)) {
         // a rank processes ~B * (rows held / rows total) positions (Poisson: <= B valid ones): size the grid for
@@ -2361,7 +2370,7 @@ static int fill_geometry(Ctx* c, const d3p_logreg_model* model, const d3p_batch_
 
 static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d3p_dpsvi_hyper* hyper,
                     const d3p_dpsvi_state* state, const d3p_batch_source* src, void* workspace_dev,
-                    size_t workspace_bytes, uint32_t num_particles = 1, bool allow_sites = false)
+                    size_t workspace_bytes, uint32_t num_particles = 1, bool allow_sites = false, bool no_main = false)
 {
     D3P_REQUIRE(model, "null argument struct");
     if (is_sites(model) && !allow_sites)  // (before anything else: no entry point but the single-GPU runs reads a tree-order state)
@@ -2372,7 +2381,9 @@ static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d
     const size_t need = carve(model, src, nullptr, nullptr);
     if (workspace_bytes < need) return fail(D3P_E_WORKSPACE, "workspace too small (%zu < %zu)", workspace_bytes, need);
     carve(model, src, (char*)workspace_dev, &c->ws, &c->ws2);
-    rc = fill_geometry(c, model, src);
+    // (K > 1: rows wider than every single-particle form still run, up to the particle kernel's own limit below; no_main: the
+    //  caller launches no main kernel -- finalize reads the sums -- so no main-kernel form has to hold the rows)
+    rc = fill_geometry(c, model, src, true, num_particles > 1 || no_main);
     if (rc) return rc;
     c->s = (hipStream_t)stream;
     c->m = model;
@@ -2383,7 +2394,9 @@ static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d
     c->P = 2 * c->D;
     c->K = num_particles;
     if (num_particles > 1) {  // the step's partial rows come from k_logreg_particles (its own workgroup count)
-        D3P_REQUIRE(particles_waves(c->D, false) > 0, "num_particles > 1: the latent dimension is too large for the particle kernel");
+        if (particles_waves(c->D, false) == 0)
+            return fail(D3P_E_UNSUPPORTED, "num_particles > 1: d + intercept = %d latent columns exceed the particle kernel's limit of %d "
+                        "(clip-and-accumulate stage)", c->D, particles_max_latent(false));
         c->g.blocks = particles_blocks(c->D, false, c->items_expected);
     }
     return D3P_OK;
@@ -2453,7 +2466,8 @@ int d3p_dpvi_logreg_finalize(void* stream, const d3p_logreg_model* model, const 
                              float* loss_dev, float* grad_out_dev, void* workspace_dev, size_t workspace_bytes)
 {
     Ctx c;
-    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes);
+    // (the sums may come from d3p_dpvi_logreg_local_sums_particles: rows as wide as the particle kernel takes)
+    int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes, 1u, false, true);
     if (rc) return rc;
     D3P_REQUIRE(sums_dev, "null sums pointer");
     if ((rc = enqueue_finalize(c, 0, sums_dev, 1u, loss_dev, grad_out_dev))) return rc;

@@ -1341,7 +1341,10 @@ struct MainGeom {
 // allow_wide: the caller launches the clip-and-accumulate stage (MODE 0) and may be given the column-chunked geometry; the
 // materialising stage (MODE 1) always uses the register-tiled kernel
 // allow_tail: the caller launches a stage that has the TAIL form (MODE 0 / 2 / 3; the materialising stage has not)
-static int main_geometry(const d3p_logreg_model* m, uint32_t B, MainGeom* g, bool allow_wide = true, bool allow_tail = true)
+// particles: the caller's main kernel is k_logreg_particles (K > 1), which sizes itself: rows of any width take the column-chunked
+// geometry as a placeholder for the rest of the step (the particle kernel's own limit is particles_max_latent)
+static int main_geometry(const d3p_logreg_model* m, uint32_t B, MainGeom* g, bool allow_wide = true, bool allow_tail = true,
+                         bool particles = false)
 {
     const int D = m->d + (m->intercept ? 1 : 0), half = (D + 1) / 2, P = 2 * D;
     // V = 4: a lane owns 4 adjacent columns of each half and fetches them with 16-byte loads -- needs both halves of a row
@@ -1370,7 +1373,7 @@ static int main_geometry(const d3p_logreg_model* m, uint32_t B, MainGeom* g, boo
     }
     // rows too wide for the register-tiled kernel (NK == 0), or its spilling NK == 8 form: the column-chunked kernel of
     // d3p_logreg_wide.h takes them when the caller runs the clip-and-accumulate stage and its 4 accumulator rows fit the LDS
-    const bool wide_ok = allow_wide && (size_t)(4 * P + 8) * sizeof(float) <= 160 * 1024 && getenv("D3P_NO_WIDE_KERNEL") == nullptr;
+    const bool wide_ok = particles || (allow_wide && (size_t)(4 * P + 8) * sizeof(float) <= 160 * 1024 && getenv("D3P_NO_WIDE_KERNEL") == nullptr);
     if (g->NK == 0 && !wide_ok)
         return fail(D3P_E_UNSUPPORTED, "step kernel: latent dimension %d: the register-tiled kernel holds at most %d columns for rows of this "
                     "alignment%s", D, 2 * 64 * g->V * 8, allow_wide ? " and the column-chunked kernel's accumulator rows do not fit the LDS" : "");

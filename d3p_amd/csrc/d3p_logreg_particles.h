@@ -41,6 +41,14 @@ static inline int particles_waves(int D, bool pxg)
     return 0;
 }
 
+// the largest D (d + intercept) a stage runs at one wavefront per workgroup: 8178 (clip-and-accumulate), 13630 (materialising)
+static inline int particles_max_latent(bool pxg)
+{
+    int D = (int)(D3P_PART_LDS_MAX / sizeof(float)) / (pxg ? 3 : 5) + 1;
+    while (D > 0 && particles_waves(D, pxg) == 0) --D;
+    return D;
+}
+
 template <bool PXG>
 __global__ void __launch_bounds__(256) k_logreg_particles(ParticleArgs pa)
 {
@@ -228,7 +236,9 @@ static int launch_particles(hipStream_t s, const ParticleArgs& pa, uint32_t bloc
 {
     const int D = pa.a.D;
     const int W = particles_waves(D, PXG);
-    if (W == 0) return fail(D3P_E_UNSUPPORTED, "k_logreg_particles: rows of %d latent columns do not fit the LDS", D);
+    if (W == 0)
+        return fail(D3P_E_UNSUPPORTED, "k_logreg_particles: rows of %d latent columns do not fit the LDS (at most %d)", D,
+                    particles_max_latent(PXG));
     if (pa.K < 2u) return fail(D3P_E_INVALID_ARG, "k_logreg_particles: K = 1 runs on the single-particle kernels");
     const size_t lds = particles_lds_bytes(D, W, PXG);
     // (the attribute is per function and device: set on every launch that needs it -- only rows of more than ~1600 columns do)

@@ -522,6 +522,12 @@ size_t d3p_logreg_px_grads_particles_workspace(const d3p_logreg_model* model, ui
     return model ? px_ws_bytes(model, B) : 0;
 }
 
+// The largest d + intercept the K > 1 kernel runs: materialising != 0 -> d3p_logreg_px_grads_particles, else the clipped sums and runs
+int d3p_logreg_particles_max_latent(int materialising)
+{
+    return particles_max_latent(materialising != 0);
+}
+
 // d3p_logreg_px_grads with num_particles ELBO particles per example: rows and losses are the means over the particles (eps_dev,
 // if given, is (B, K, D)).  K == 1: exactly d3p_logreg_px_grads.
 int d3p_logreg_px_grads_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
@@ -543,6 +549,9 @@ int d3p_logreg_px_grads_particles(void* stream, const d3p_logreg_model* model, c
                     px_ws_bytes(model, B));
     hipStream_t s = (hipStream_t)stream;
     const int D = model->d + (model->intercept ? 1 : 0);
+    if (particles_waves(D, true) == 0)  // (before the first launch: the caller's outputs stay untouched)
+        return fail(D3P_E_UNSUPPORTED, "d3p_logreg_px_grads_particles: d + intercept = %d latent columns exceed the particle kernel's "
+                    "limit of %d (materialising stage)", D, particles_max_latent(true));
     float* pack = (float*)workspace_dev;
     hipLaunchKernelGGL(k_pack, dim3(cdiv(D, 256)), dim3(256), 0, s, *model, params_dev, pack);
     hipLaunchKernelGGL(k_mask_meta, dim3(1), dim3(256), 0, s, mask_dev, B, meta_dev);

@@ -536,6 +536,8 @@ class DPSVI:
         if self._is_gmm():
             return self._compute_per_example_gradients_gmm(dp_svi_state, step_rng_key, *args, mask=mask, **kwargs)
         self._require_logreg()
+        if args:
+            self._require_particle_rows(np.shape(args[0])[-1], True)
         _lib.require_device()
         lib = _lib.load()
         X = _batch_array(args[0])
@@ -818,6 +820,25 @@ class DPSVI:
         if y is not None and B is not None and y.numel() != int(B):
             raise ValueError(f"labels: {y.numel()} entries for a batch of {int(B)} examples")
 
+    def _require_particle_rows(self, d, materialising):
+        """K > 1: the particle kernel keeps an example's rows in LDS, so d + intercept has a ceiling per stage (d3p_logreg_particles_max_latent:
+        8178 for the clipped sums of update / run_steps, 13630 for the materialised per-example rows).  Checked before anything is
+        enqueued, so the caller's state and outputs stay as they were."""
+        K = self._num_particles
+        if K <= 1 or not isinstance(self.model, (LogisticRegression, GaussianMean)):
+            return
+        D = self.model.latent_dim(int(d))
+        limit = int(_lib.load().d3p_logreg_particles_max_latent(int(bool(materialising))))
+        if D > limit:
+            stage = "per-example gradient rows" if materialising else "clipped gradient sums"
+            raise _lib.D3PError(f"Trace_ELBO(num_particles={K}): the {stage} run at most {limit} latent columns (d + intercept), "
+                                f"this model has {D}")
+
+    def _particle_route_materialises(self, kwargs):
+        """Whether update's route for this configuration materialises per-example rows (the staged composition) rather than
+        clipping into sums (_update_fused, _update_leaves)."""
+        return not (self._fusable() or (self._leaves_fusable() and "_eps" not in kwargs))
+
     @staticmethod
     def _require_device_state(svi_state):
         """The state's key and flat optimiser arrays are handed to kernels by address: they must be device tensors (a state that was
@@ -831,6 +852,8 @@ class DPSVI:
     def update(self, svi_state, *args, mask=True, **kwargs):
         """One DP-VI step on a batch; returns ``(new_state, loss)`` (svi.py:395-434)."""
         self._require_device_state(svi_state)
+        if self._num_particles > 1 and args:   # (before any launch of any route)
+            self._require_particle_rows(np.shape(args[0])[-1], self._particle_route_materialises(kwargs))
         if self._gmm_fusable():
             return self._update_gmm_fused(svi_state, *args, mask=mask, **kwargs)
         if self._is_vae():
@@ -1019,6 +1042,8 @@ class DPSVI:
         info = getattr(get_batch, "source", None)
         if info is not None and info.kind == _lib.D3P_BATCH_POISSON and int(info.batch_size) > example_count(info.dataset[0]):
             raise AssertionError("poisson_batchify_data: max_batch_size exceeds the number of records")   # (as get_batch, minibatch.py:116)
+        if self._num_particles > 1 and info is not None:   # (before the first batch is drawn; other batchifiers: at update)
+            self._require_particle_rows(np.shape(info.dataset[0])[-1], self._particle_route_materialises(kwargs))
         if info is not None:
             if any(not (isinstance(a, torch.Tensor) and a.is_cuda) for a in info.dataset):
                 raise _lib.D3PError("run_steps: the batchifier's dataset arrays must be CUDA tensors")

@@ -331,7 +331,8 @@ int d3p_dpvi_logreg_local_sums(void* stream, const d3p_logreg_model* model,
 
 /* Phase 2 (replicated): mean, Gaussian mechanism (noise added ONCE, after any all-reduce of
  * sums_dev), rescale, Adam, advance keys/counters.  loss_dev[0] receives the batch loss
- * (svi.py:342, :306); grad_out_dev (P, optional) the perturbed gradient. */
+ * (svi.py:342, :306); grad_out_dev (P, optional) the perturbed gradient.  It launches no per-example kernel, so it takes the
+ * sums of d3p_dpvi_logreg_local_sums_particles at every width that entry runs. */
 int d3p_dpvi_logreg_finalize(void* stream, const d3p_logreg_model* model,
                              const d3p_dpsvi_hyper* hyper, const d3p_dpsvi_state* state,
                              const d3p_batch_source* src, const float* sums_dev, float* loss_dev,
@@ -780,6 +781,10 @@ int d3p_predict_vae(void* stream, const d3p_vae_model* model, const float* param
  * (k_logreg_particles + finalize) on one GPU: the data-parallel, chained and persistent forms are not reached. */
 /* d3p_logreg_px_grads, averaged over the particles; eps_dev (optional) is B x K x D. */
 size_t d3p_logreg_px_grads_particles_workspace(const d3p_logreg_model* model, uint32_t B, uint32_t num_particles);
+/* The largest d + intercept that K > 1 runs (host only, no device call): materialising != 0 -> d3p_logreg_px_grads_particles (13630),
+ * else d3p_dpvi_logreg_local_sums_particles / d3p_dpvi_logreg_run_particles_from (8178).  Beyond it those entries return
+ * D3P_E_UNSUPPORTED before any launch. */
+int d3p_logreg_particles_max_latent(int materialising);
 int d3p_logreg_px_grads_particles(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev,
                                   const float* y_dev, const uint8_t* mask_dev, uint32_t B, uint32_t num_particles, const float* eps_dev,
                                   const uint32_t* jax_key_dev, float* px_loss_dev, float* px_grads_dev, float* meta_dev,

@@ -9,7 +9,11 @@ restatement of d3p/svi.py:395-434 driven by the oracle's own samplers: state key
 losses and parameters (empty batches: svi.py:305, :365), final parameters
 (rtol 5e-4, atol 5e-5 of the largest) and step counter.
 
-    python tests/fuzz_vs_oracle.py [update|big|stepwise|staged|gmm|vae|rng|batches|shards|posshards|predict] [first_seed=0] [count=40] [out.jsonl]
+    python tests/fuzz_vs_oracle.py [update|big|stepwise|staged|gmm|vae|rng|batches|shards|posshards|predict|particles|staged_particles] [first_seed=0] [count=40] [out.jsonl]
+
+`particles`: the update family with Trace_ELBO(num_particles=K) (k_logreg_particles: update, Feistel and Poisson runs, MeanFieldGuide)
+against tests/particles_ref.py, d up to the particle kernel's limit and batches past its grid-stride boundary; `staged_particles`: the
+staged family with K particles.
 
 `gmm`: the mixture model's update (explicit batches with masks, Feistel runs; half the cases from a live state: random Adam moments and
 step counter) vs the oracle's stage composition; `rng`: split / fold_in /
@@ -106,7 +110,8 @@ def run_case(c, O, dump=False):
         model = LogisticRegression(d, prior_scale=pw, intercept=icpt, intercept_prior_scale=pb)
         guide = MeanFieldGuide(model) if c["guide"] == "meanfield" else AutoDiagonalNormal(model)
         spec = O.logreg_spec(d, icpt, pw, pb, lik_scale=N, obs_scale=obs, guide_exp=c["guide"] == "meanfield")
-    svi = DPSVI(model, guide, Adam(c["lr"]), Trace_ELBO(), c["clip"], c["sigma"], num_obs_total=N,
+    K = c.get("K", 1)
+    svi = DPSVI(model, guide, Adam(c["lr"]), Trace_ELBO(num_particles=K), c["clip"], c["sigma"], num_obs_total=N,
                 clip_unscaled_observations=c.get("unscale", True), **({"d": d} if gauss else {}))
     hy = O.Hyper(c["clip"], c["sigma"], c["lr"], 0.9, 0.999, 1e-8)
     meanfield = c["guide"] == "meanfield"
@@ -129,6 +134,11 @@ def run_case(c, O, dump=False):
     if float(svi.init(rng.PRNGKey(1), *(a[:max(B, 1)] for a in table)).observation_scale) != obs:
         raise AssertionError("observation scale of init")
     upd = O.meanfield_logreg_update if meanfield else O.logreg_update
+    if K > 1:   # (the particle comparator; one-site eps of large batches from the device's draws, see _particle_eps_fn)
+        from tests import particles_ref as R
+        eps_fn = _particle_eps_fn(K, D) if not meanfield and B * K > 4000 else None
+        upd = ((lambda sp, hy_, st_, Xb, yb, mask=None: R.meanfield_update(O, sp, hy_, st_, Xb, yb, K, mask)) if meanfield else
+               (lambda sp, hy_, st_, Xb, yb, mask=None: R.update(O, sp, hy_, st_, Xb, yb, K, mask, eps_fn=eps_fn)))
     el = []
     t0 = time.time()
     if c["source"] == "explicit":
@@ -230,7 +240,11 @@ def run_case(c, O, dump=False):
             spec_e = O.gauss_mean_spec(d, prior=pw, lik_sigma=ls, lik_scale=N, obs_scale=1.0, guide_exp=c["guide"] != "auto")
         else:
             spec_e = O.logreg_spec(d, icpt, pw, pb, lik_scale=N, obs_scale=1.0, guide_exp=meanfield)
-        if meanfield:
+        if K > 1 and meanfield:
+            want_e = R.meanfield_evaluate(O, spec_e, got_p, X[idx], y[idx], jk, K)
+        elif K > 1:
+            want_e = R.evaluate(O, spec_e, got_p[:D], got_p[D:], X[idx], None if gauss else y[idx], jk, K)
+        elif meanfield:
             want_e = O.meanfield_logreg_evaluate(spec_e, got_p, X[idx], y[idx], jk)
         else:
             want_e = O.logreg_evaluate(spec_e, got_p[:D], got_p[D:], X[idx], None if gauss else y[idx], jk)
@@ -242,6 +256,53 @@ def run_case(c, O, dump=False):
         c["mask_sum"] = int(mask.sum()) if c["source"] != "feistel" else None
     c["ok"], c["why"] = not why, "; ".join(why)
     c["final_loss"] = float(want_l[-1]) if len(want_l) else None
+    return c
+
+
+# ------------------------------------------------------------------ Trace_ELBO(num_particles=K): k_logreg_particles on every route
+PARTICLE_DIMS = DIMS + [819, 1365, 2044, 2045, 3407, 4088, 4089, 6000, 8177, 8178]
+
+
+def _particle_eps_fn(K, D):
+    """(B, K, D) one-site guide noise from d3p_px_eps_sites_particles: the key rule at these sizes is pinned against the restated rule
+    by tests/test_gpu_particles.py::test_eps_sites_particles_vs_comparator; restating it in Python would dominate a large case."""
+    import ctypes as C
+    import torch
+    import d3p_amd._lib as L
+    from d3p_amd._lib import check, ptr, stream_ptr
+
+    def fn(jax_key, B):
+        jk = torch.tensor(np.asarray(jax_key, np.uint32).view(np.int32)).cuda()
+        eps = torch.empty((B, K, D), dtype=torch.float32, device="cuda")
+        check(L.load().d3p_px_eps_sites_particles(stream_ptr(), ptr(jk), B, 0, B, K, (C.c_int32 * 1)(D), 1, ptr(eps)))
+        return eps.cpu().numpy()
+    return fn
+
+
+def draw_particles_case(seed):
+    """draw_case with K particles (2 .. 8, sometimes 16), d up to the clip stage's limit (8178) and the same batch sources, guides and
+    fields; the expected trajectory is tests/particles_ref.py's.  The oracle's work B * d * K * steps is bounded."""
+    c = draw_case(104_729 * seed + 29)
+    c["seed"], c["family_name"] = int(seed), "particles"
+    r = np.random.default_rng(1_300_021 * seed + 83)
+    c["K"] = 16 if r.random() < 0.1 else int(r.integers(2, 9))
+    c["d"] = int(r.choice(PARTICLE_DIMS))
+    if c["family"] == "logreg_icpt":
+        c["d"] = min(c["d"], 8177)
+    c["B"] = int(r.choice(BATCHES))
+    while c["B"] * c["d"] * c["K"] > 2e7 and c["B"] > 1:
+        c["B"] = max(c["B"] // 2, 1)
+    if c["guide"] == "meanfield":     # (the two-site eps are restated in Python: ~80 us per particle)
+        while c["B"] * c["K"] > 4000:
+            c["B"] = max(c["B"] // 2, 1)
+    budget = 3e7 / (c["B"] * c["d"] * c["K"])
+    c["steps"] = int(r.choice([s for s in (1, 2, 5, 20) if s <= max(budget, 1)]))
+    if c["guide"] == "meanfield":
+        while c["steps"] > 1 and c["B"] * c["K"] * c["steps"] > 8000:
+            c["steps"] //= 2
+    c["N"] = int(min(max(c["B"] * float(r.choice([1.0, 1.5, 10.0])), c["B"]), 2e7 / c["d"]))
+    c["N"] = max(c["N"], c["B"])
+    c["split_at"] = int(r.integers(1, c["steps"])) if (c["steps"] > 1 and r.random() < 0.5) else 0
     return c
 
 
@@ -298,6 +359,18 @@ def draw_staged_case(seed):
     return c
 
 
+def draw_staged_particles_case(seed):
+    """draw_staged_case with K particles (the materialising particle kernel under SGD / ADADP), on seeds of its own: the staged
+    family's seeds keep their one-particle cases."""
+    c = draw_staged_case(1_000_000 + seed)
+    c["seed"], c["family_name"] = int(seed), "staged_particles"
+    r2 = np.random.default_rng(900_007 * seed + 59)
+    c["K"] = int(r2.choice([2, 3, 5, 9]))
+    while c["B"] * c["K"] > 4000:
+        c["B"] = max(c["B"] // 2, 1)
+    return c
+
+
 def run_staged_case(c, O, dump=False):
     """DPSVI.update with SGD (the reference's tests' optimiser): per-example gradients -> clip -> mean -> one noise key per site -> step,
     every stage a materialised tensor (d3p_logreg_px_grads incl. its column-chunked form, d3p_clip_rows, d3p_combine, d3p_perturb_apply,
@@ -327,7 +400,8 @@ def run_staged_case(c, O, dump=False):
         mk_spec = lambda obs: O.logreg_spec(d, icpt, 1.0, 2.0, lik_scale=N, obs_scale=obs)
     spec = mk_spec(N)
     optim = ADADP(c["lr"], tol=c["tol"], stability_check=c["stability"]) if adadp else SGD(c["lr"])
-    svi = DPSVI(model, guide, optim, Trace_ELBO(), c["clip"], c["sigma"], num_obs_total=N, **({"d": d} if gauss else {}))
+    K = c.get("K", 1)
+    svi = DPSVI(model, guide, optim, Trace_ELBO(num_particles=K), c["clip"], c["sigma"], num_obs_total=N, **({"d": d} if gauss else {}))
     loc = (r.normal(size=D) * c["init_scale"]).astype(np.float32)
     unc = (r.normal(size=D) * c["init_scale"] - 2.0).astype(np.float32)
     x = np.concatenate([loc, unc])
@@ -345,9 +419,15 @@ def run_staged_case(c, O, dump=False):
         st, loss = svi.update(st, *args, mask=torch.tensor(mask).cuda() if use_mask else True)
         got_l.append(float(loss))
         ks = O.split(key, 3)
-        eps = O.px_eps(O.convert_to_jax_rng_key(ks[1]), B, D)
         with np.errstate(all="ignore"):
-            L, G, n, f = O.logreg_px_grads(spec, x[:D], x[D:], X[idx], None if gauss else y[idx], eps, mask.astype(np.float32) if use_mask else None)
+            if K > 1:
+                from tests import particles_ref as R
+                eps = R.px_eps(O, O.convert_to_jax_rng_key(ks[1]), B, D, K)
+                L, G, n, f = R.px_grads(O, spec, x[:D], x[D:], X[idx], None if gauss else y[idx], eps,
+                                        mask.astype(np.float32) if use_mask else None)
+            else:
+                eps = O.px_eps(O.convert_to_jax_rng_key(ks[1]), B, D)
+                L, G, n, f = O.logreg_px_grads(spec, x[:D], x[D:], X[idx], None if gauss else y[idx], eps, mask.astype(np.float32) if use_mask else None)
             eloss, avg = O.combine(O.clip_rows(G, c["clip"]), L)
             g = O.perturb(ks[2], avg, [D, D], c["sigma"], c["clip"], n, N, f)
             if adadp:
@@ -397,8 +477,12 @@ def run_staged_case(c, O, dump=False):
             idx = (np.arange(B) * 3 + 1) % N
             args = (Xd[idx],) if gauss else (Xd[idx], yd[idx])
             got_e = float(svi.evaluate(st, *args))
-            want_e = O.logreg_evaluate(mk_spec(1.0), got_p[:D], got_p[D:], X[idx], None if gauss else y[idx],
-                                       O.convert_to_jax_rng_key(O.split(key, 1)[0]))
+            jk = O.convert_to_jax_rng_key(O.split(key, 1)[0])
+            if K > 1:
+                from tests import particles_ref as R
+                want_e = R.evaluate(O, mk_spec(1.0), got_p[:D], got_p[D:], X[idx], None if gauss else y[idx], jk, K)
+            else:
+                want_e = O.logreg_evaluate(mk_spec(1.0), got_p[:D], got_p[D:], X[idx], None if gauss else y[idx], jk)
             if not (got_e == want_e or abs(got_e - want_e) <= LOSS_RTOL * abs(want_e) + 1e-6 * (D + N) or (np.isnan(got_e) and np.isnan(want_e))):
                 why.append(f"evaluate: {got_e!r} vs {want_e!r}")
     c["ok"], c["why"] = not why, "; ".join(why)
@@ -1191,7 +1275,8 @@ def run_predict_case(c, O, dump=False):
 FAMILIES = {"big": (draw_big_case, None), "stepwise": (draw_stepwise_case, None), "batches": (draw_batches_case, run_batches_case), "shards": (draw_shards_case, run_shards_case),
             "posshards": (draw_posshards_case, run_posshards_case), "update": (draw_case, None), "staged": (draw_staged_case, run_staged_case), "gmm": (draw_gmm_case, run_gmm_case),
             "vae": (draw_vae_case, run_vae_case),
-            "rng": (draw_rng_case, run_rng_case), "predict": (draw_predict_case, run_predict_case)}
+            "rng": (draw_rng_case, run_rng_case), "predict": (draw_predict_case, run_predict_case),
+            "particles": (draw_particles_case, None), "staged_particles": (draw_staged_particles_case, run_staged_case)}
 
 
 def main():

@@ -76,6 +76,21 @@ def test_random_large_batch_case_vs_oracle(gpu, O, seed):
     assert c["ok"], c
 
 
+# (the stage composition with K particles: the materialising particle kernel under SGD / ADADP, vs tests/particles_ref.py)
+@pytest.mark.parametrize("seed", list(range(16)))
+def test_random_stage_composition_particles_case_vs_oracle(gpu, O, seed):
+    c = F.run_staged_case(F.draw_staged_particles_case(seed), O)
+    assert c["ok"], c
+
+
+# (Trace_ELBO(num_particles=K): k_logreg_particles through update, Feistel and Poisson runs and MeanFieldGuide, d up to 8178, batches
+#  past the kernel's grid-stride boundary, vs tests/particles_ref.py)
+@pytest.mark.parametrize("seed", list(range(24)))
+def test_random_particles_case_vs_oracle(gpu, O, seed):
+    c = F.run_case(F.draw_particles_case(seed), O)
+    assert c["ok"], c
+
+
 # (run_steps over the batchifiers that have no native loop: sampling with replacement, the epoch split)
 @pytest.mark.parametrize("seed", list(range(16)))
 def test_random_stepwise_batchifier_case_vs_oracle(gpu, O, seed):

@@ -93,7 +93,9 @@ def _px_case(O, B, d, icpt, gauss, guide, K, seed, onchip):
 
 
 # ---------------------------------------------------------------- keys and eps, bit for bit
-@pytest.mark.parametrize("B,K,sizes", [(5, 3, [7, 1]), (4, 2, [513, 1]), (3, 8, [9]), (6, 1, [4, 1])])
+# (B up to ~300 and K past 8: the key rule at the sizes where the trajectory tests take eps from d3p_px_eps_sites_particles)
+@pytest.mark.parametrize("B,K,sizes", [(5, 3, [7, 1]), (4, 2, [513, 1]), (3, 8, [9]), (6, 1, [4, 1]), (300, 9, [37, 1]), (257, 16, [8]),
+                                       (64, 33, [13, 1]), (151, 33, [2]), (96, 16, [6, 1]), (299, 9, [4])])
 def test_eps_sites_particles_vs_comparator(gpu, O, B, K, sizes):
     import ctypes as C
     import d3p_amd._lib as L

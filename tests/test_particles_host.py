@@ -132,3 +132,120 @@ def test_comparator_update_at_one_particle_is_the_oracles(O):
         np.testing.assert_allclose(gb, ga, rtol=1e-5, atol=1e-7 * np.abs(ga).max())
         assert np.array_equal(a.key, b.key)
     np.testing.assert_allclose(b.params, a.params, rtol=1e-5, atol=1e-7)
+
+
+# ---------------------------------------------------------------- the K > 1 size limit (k_logreg_particles keeps the rows in LDS)
+def _lds_limit(materialising):
+    """The LDS arithmetic of csrc/d3p_logreg_particles.h restated: per wavefront (2 + 1 (+ 2 without materialising)) x D floats rounded
+    down to a multiple of 4, plus 2 floats, at least one wavefront within 160 KB less 256 bytes."""
+    def fits(D):
+        wave = ((3 if materialising else 5) * D + 3) & ~3
+        return (wave + 2) * 4 <= 160 * 1024 - 256
+    D = 1
+    while fits(D + 1):
+        D += 1
+    return D
+
+
+def test_particle_limits_pinned_at_both_boundaries():
+    import d3p_amd._lib as L
+    lib = L.load()
+    assert lib.d3p_logreg_particles_max_latent(0) == _lds_limit(False) == 8178
+    assert lib.d3p_logreg_particles_max_latent(1) == _lds_limit(True) == 13630
+
+
+def _model(L, D, icpt, N=100):
+    return L.LogregModel(D - int(icpt), int(icpt), 1.0, 2.0, float(N), 1.0 / N, L.D3P_FAMILY_LOGREG, L.D3P_GUIDE_SOFTPLUS, 0.0)
+
+
+def _scratch(nbytes):
+    """(keep-alive, base address) of nbytes zeroed bytes: device memory where a device is visible (so that an entry which failed to
+    refuse would run its kernels on real buffers, not fault on host addresses), else host memory (a launch then fails with D3P_E_HIP)."""
+    import ctypes
+    import torch
+    if torch.cuda.is_available():
+        t = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        return t, t.data_ptr()
+    host = (ctypes.c_uint8 * nbytes)()
+    return host, ctypes.addressof(host)
+
+
+@pytest.mark.parametrize("icpt", [False, True])
+def test_c_entries_refuse_the_first_unsupported_size_before_any_launch(icpt):
+    """At D = limit + 1 every K > 1 entry returns D3P_E_UNSUPPORTED naming the limit, before any launch.  Every pointer names its own
+    1 MiB region of one zeroed buffer (larger than any array of these shapes) and the workspace its full size."""
+    import ctypes
+    import d3p_amd._lib as L
+    lib = L.load()
+    B = ctypes.byref
+    h = L.DpsviHyper(1.0, 0.5, 1e-2, 0.9, 0.999, 1e-8)
+    src = L.BatchSource(L.D3P_BATCH_EXPLICIT, 3, 0.0, 0, None, None, None, 3, 0, 3)
+    m = _model(L, 8179, icpt)
+    ws = lib.d3p_dpvi_logreg_workspace(B(m), B(src))
+    keep, base = _scratch(ws + (16 << 20))
+    r = [base + ws + (i << 20) for i in range(16)]   # regions after the workspace
+    st = L.DpsviState(r[0], 0, r[1], r[2], r[3], r[4])
+    rc = lib.d3p_dpvi_logreg_local_sums_particles(None, B(m), B(h), B(st), B(src), r[5], r[6], None, 2, r[7], base, ws)
+    assert rc == -3 and b"8178" in lib.d3p_last_error(), lib.d3p_last_error()
+    st2 = L.DpsviState(r[8], 0, r[9], r[10], r[11], r[12])
+    rc = lib.d3p_dpvi_logreg_run_particles_from(None, B(m), B(h), B(st2), B(st), B(src), 0, r[5], r[6], 1, 3, r[7], base, ws)
+    assert rc == -3 and b"8178" in lib.d3p_last_error(), lib.d3p_last_error()
+    m = _model(L, 13631, icpt)
+    ws2 = lib.d3p_logreg_px_grads_particles_workspace(B(m), 3, 2)
+    assert ws2 <= ws
+    rc = lib.d3p_logreg_px_grads_particles(None, B(m), r[1], r[5], r[6], None, 3, 2, None, r[0], r[7], r[8], r[9], base, ws2)
+    assert rc == -3 and b"13630" in lib.d3p_last_error(), lib.d3p_last_error()
+    del keep
+
+
+def test_finalize_takes_the_sums_of_rows_wider_than_the_single_particle_forms():
+    """d3p_dpvi_logreg_finalize launches no per-example kernel: at D = 6000 (the particle kernel's one-wavefront form; no single-particle
+    form holds the rows) it does not refuse -- it runs on a device, and without one only the launch itself fails."""
+    import ctypes
+    import torch
+    import d3p_amd._lib as L
+    lib = L.load()
+    B = ctypes.byref
+    h = L.DpsviHyper(1.0, 0.5, 1e-2, 0.9, 0.999, 1e-8)
+    src = L.BatchSource(L.D3P_BATCH_EXPLICIT, 3, 0.0, 0, None, None, None, 3, 0, 3)
+    m = _model(L, 6000, False)
+    ws = lib.d3p_dpvi_logreg_workspace(B(m), B(src))
+    keep, base = _scratch(ws + (8 << 20))
+    r = [base + ws + (i << 20) for i in range(8)]
+    st = L.DpsviState(r[0], 0, r[1], r[2], r[3], r[4])
+    rc = lib.d3p_dpvi_logreg_finalize(None, B(m), B(h), B(st), B(src), r[5], r[6], None, base, ws)
+    assert b"latent dimension" not in lib.d3p_last_error()
+    if torch.cuda.is_available():
+        assert rc == 0, lib.d3p_last_error()
+        torch.cuda.synchronize()
+    else:
+        assert rc == -2, (rc, lib.d3p_last_error())   # D3P_E_HIP: the launch
+    del keep
+
+
+@pytest.mark.parametrize("guide", ["auto", "meanfield", "sgd"])
+def test_python_refusal_boundaries(monkeypatch, guide):
+    """DPSVI._require_particle_rows: the last supported D passes, the next raises naming the limit; the stage follows the route
+    (the staged composition -- here SGD -- materialises rows, the fused routes clip into sums).  No device is touched."""
+    import d3p_amd._lib as L
+    from d3p_amd.models import SGD, Adam, AutoDiagonalNormal, LogisticRegression, MeanFieldGuide, Trace_ELBO
+    from d3p_amd.svi import DPSVI
+
+    def no_device(*a, **k):
+        raise AssertionError("a device call was made")
+    monkeypatch.setattr(L, "require_device", no_device)
+    icpt = guide == "meanfield"
+    for K in (1, 2, 5):
+        model = LogisticRegression(8, intercept=icpt)
+        g = MeanFieldGuide(model) if guide == "meanfield" else AutoDiagonalNormal(model)
+        svi = DPSVI(model, g, SGD(1e-3) if guide == "sgd" else Adam(1e-3), Trace_ELBO(num_particles=K), 1.0, 1.0, N=100)
+        materialising = svi._particle_route_materialises({})
+        assert materialising == (guide == "sgd")
+        limit = 13630 if materialising else 8178
+        for stage, lim in ((materialising, limit), (True, 13630)):
+            svi._require_particle_rows(lim - int(icpt), stage)
+            if K == 1:
+                svi._require_particle_rows(lim + 100, stage)      # one particle: no limit
+                continue
+            with pytest.raises(L.D3PError, match=str(lim)):
+                svi._require_particle_rows(lim + 1 - int(icpt), stage)

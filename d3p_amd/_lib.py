@@ -15,7 +15,7 @@ _DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_ho
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
 D3P_BATCH_EXPLICIT, D3P_BATCH_FEISTEL, D3P_BATCH_POISSON = 0, 1, 2
-D3P_FAMILY_LOGREG, D3P_FAMILY_GAUSS_MEAN = 0, 1
+D3P_FAMILY_LOGREG, D3P_FAMILY_GAUSS_MEAN, D3P_FAMILY_LINREG, D3P_FAMILY_POISSON = 0, 1, 2, 3
 D3P_GUIDE_SOFTPLUS, D3P_GUIDE_EXP, D3P_GUIDE_EXP_SITES = 0, 1, 2
 
 

@@ -1316,6 +1316,19 @@ static int enqueue_main(const Ctx& c, int t, const float* X, const float* y, con
         pa.K = c.K;
         return launch_particles<false>(c.s, pa, c.g.blocks, e0, e1);
     }
+#define D3P_LAUNCH_WIDE_GLM(G_)                                                                                                     \
+    {                                                                                                                               \
+        if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(k_logreg_wide<false, G_>), 160 * 1024, "k_logreg_wide"))   \
+            return rc_;                                                                                                             \
+        if (e0)                                                                                                                     \
+            hipExtLaunchKernelGGL((k_logreg_wide<false, G_>), dim3(c.g.blocks), dim3(64 * D3P_WIDE_W), c.g.lds, c.s, e0, e1, 0, a); \
+        else                                                                                                                        \
+            hipLaunchKernelGGL((k_logreg_wide<false, G_>), dim3(c.g.blocks), dim3(64 * D3P_WIDE_W), c.g.lds, c.s, a);               \
+        return check_launch("k_logreg_wide");                                                                                       \
+    }
+    if (c.g.wide && c.m->family == D3P_FAMILY_LINREG) D3P_LAUNCH_WIDE_GLM(D3P_FAMILY_LINREG)   // (their instantiations of the same kernel)
+    if (c.g.wide && c.m->family == D3P_FAMILY_POISSON) D3P_LAUNCH_WIDE_GLM(D3P_FAMILY_POISSON)
+#undef D3P_LAUNCH_WIDE_GLM
     if (c.g.wide) {  // wide rows: column-chunked kernel, same partial-row output
         if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(k_logreg_wide<false>), 160 * 1024, "k_logreg_wide")) return rc_;
         if (e0)
@@ -2373,6 +2386,7 @@ static int make_ctx(Ctx* c, void* stream, const d3p_logreg_model* model, const d
                     size_t workspace_bytes, uint32_t num_particles = 1, bool allow_sites = false, bool no_main = false)
 {
     D3P_REQUIRE(model, "null argument struct");
+    if (int rg = refuse_glm_shards(model, src, false, "d3p_dpvi_logreg")) return rg;
     if (is_sites(model) && !allow_sites)  // (before anything else: no entry point but the single-GPU runs reads a tree-order state)
         return fail(D3P_E_UNSUPPORTED, "D3P_GUIDE_EXP_SITES (state in tree order) is run by the single-GPU runs only");
     int rc = validate(model, hyper, state, src);
@@ -2778,6 +2792,7 @@ int d3p_dpvi_logreg_run_xchg(void* stream, void* xchg, const d3p_logreg_model* m
                              const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev, const float* y_dev,
                              uint32_t num_steps, float* losses_dev, void* workspace_dev, size_t workspace_bytes)
 {
+    if (int rg = refuse_glm_shards(model, src, true, "d3p_dpvi_logreg_run_xchg")) return rg;
     Ctx c;
     int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes);
     if (rc) return rc;
@@ -2795,6 +2810,7 @@ int d3p_dpvi_logreg_run_dist(void* stream, void* comm, const d3p_logreg_model* m
                              const d3p_dpsvi_state* state, const d3p_batch_source* src, const float* X_dev, const float* y_dev,
                              uint32_t num_steps, float* losses_dev, void* workspace_dev, size_t workspace_bytes)
 {
+    if (int rg = refuse_glm_shards(model, src, true, "d3p_dpvi_logreg_run_dist")) return rg;
     Ctx c;
     int rc = make_ctx(&c, stream, model, hyper, state, src, workspace_dev, workspace_bytes);
     if (rc) return rc;
@@ -2900,6 +2916,7 @@ int d3p_dpvi_logreg_run_dist_from(void* stream, void* comm, void* xchg, const d3
     D3P_REQUIRE(from && from->rng_key && from->params && from->adam_m && from->adam_v && from->step, "d3p_dpvi_logreg_run_dist_from: null source state");
     D3P_REQUIRE(src && workspace_dev, "d3p_dpvi_logreg_run_dist_from: null pointer");
     D3P_REQUIRE(!(comm && xchg), "d3p_dpvi_logreg_run_dist_from: give one of comm / xchg");
+    if (int rg = refuse_glm_shards(model, src, true, "d3p_dpvi_logreg_run_dist_from")) return rg;
     d3p_batch_source s2 = *src;
     if (s2.kind != D3P_BATCH_EXPLICIT && !s2.batch_index) s2.batch_index = reinterpret_cast<uint32_t*>(workspace_dev);  // placeholder for validate(); set below
     Ctx c;

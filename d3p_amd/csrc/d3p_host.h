@@ -40,8 +40,20 @@ inline int check_launch(const char* what)
         if (!(cond)) return d3p::fail(D3P_E_INVALID_ARG, "%s", msg);   \
     } while (0)
 
-// model spec checks shared by every entry point that takes a d3p_logreg_model; labels are only read by
-// the Bernoulli family.  allow_sites: the entry point runs D3P_GUIDE_EXP_SITES (the single-GPU runs); every other one refuses it.
+// the generalised linear models that share the logistic regression's kernels through glm_link (d3p_logreg_kernel.h)
+inline bool is_glm(const d3p_logreg_model* m) { return m->family == D3P_FAMILY_LINREG || m->family == D3P_FAMILY_POISSON; }
+
+// Those two families run on one GPU: an entry point of the data-parallel loops (a communicator, an exchange, or a row range that is
+// not the whole table) refuses them before any launch.
+inline int refuse_glm_shards(const d3p_logreg_model* m, const d3p_batch_source* src, bool data_parallel_entry, const char* what)
+{
+    if (m && is_glm(m) && (data_parallel_entry || (src && !(src->row_lo == 0 && src->row_hi == src->n_rows))))
+        return fail(D3P_E_UNSUPPORTED, "%s: linear / Poisson regression run on one GPU (the whole table: row_lo = 0, row_hi = n_rows)", what);
+    return D3P_OK;
+}
+
+// model spec checks shared by every entry point that takes a d3p_logreg_model; labels are read by
+// every family but the Gaussian mean.  allow_sites: the entry point runs D3P_GUIDE_EXP_SITES (the single-GPU runs); every other one refuses it.
 inline int validate_model(const d3p_logreg_model* m, const void* y_dev, const char* what, bool allow_sites = false)
 {
     if (!m) return fail(D3P_E_INVALID_ARG, "%s: null model", what);
@@ -51,6 +63,9 @@ inline int validate_model(const d3p_logreg_model* m, const void* y_dev, const ch
         if (!allow_sites)
             return fail(D3P_E_UNSUPPORTED, "%s: guide transform D3P_GUIDE_EXP_SITES (state in tree order) is run by the single-GPU "
                         "runs only", what);
+        if (is_glm(m))
+            return fail(D3P_E_UNSUPPORTED, "%s: D3P_GUIDE_EXP_SITES is built for logistic regression only (linear / Poisson regression: "
+                        "D3P_GUIDE_SOFTPLUS or D3P_GUIDE_EXP)", what);
         if (!(m->intercept && m->family == D3P_FAMILY_LOGREG))
             return fail(D3P_E_INVALID_ARG, "%s: D3P_GUIDE_EXP_SITES needs logistic regression with an intercept", what);
     } else if (m->guide_transform != D3P_GUIDE_SOFTPLUS && m->guide_transform != D3P_GUIDE_EXP) {
@@ -61,6 +76,10 @@ inline int validate_model(const d3p_logreg_model* m, const void* y_dev, const ch
     } else if (m->family == D3P_FAMILY_GAUSS_MEAN) {
         if (m->intercept) return fail(D3P_E_INVALID_ARG, "%s: the Gaussian-mean family has no intercept", what);
         if (!(m->lik_sigma > 0.f)) return fail(D3P_E_INVALID_ARG, "%s: lik_sigma must be > 0", what);
+    } else if (is_glm(m)) {
+        if (!y_dev) return fail(D3P_E_INVALID_ARG, "%s: null label pointer", what);
+        if (m->family == D3P_FAMILY_LINREG && !(m->lik_sigma > 0.f && std::isfinite(m->lik_sigma)))
+            return fail(D3P_E_INVALID_ARG, "%s: lik_sigma must be finite and > 0", what);
     } else {
         return fail(D3P_E_INVALID_ARG, "%s: unknown likelihood family %d", what, m->family);
     }

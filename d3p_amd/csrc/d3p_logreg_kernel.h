@@ -42,6 +42,46 @@ __device__ __forceinline__ void guide_scale(int gexp, float u, float& s, float& 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// likelihood link of the regression families: with t = x . z (+ b) the linear predictor of one example,
+//   dl = d(-log p(y | t)) / dt   and   ll = log p(y | t)        (glm_link returns A = A_scale * dl and ll)
+//   LOGREG : dl = sigmoid(t) - y        ll = y t - softplus(t)
+//   LINREG : dl = (t - y) / sigma^2     ll = -0.5 (t - y)^2 / sigma^2 - (log sigma + log(2 pi) / 2)
+//   POISSON: dl = exp(t) - y            ll = y t - exp(t) - lgamma(y + 1)
+// nh = -0.5 / sigma^2 (LINREG).  c is the term of ll that no parameter reaches: log sigma + log(2 pi) / 2 (LINREG), or
+// lgamma(y + 1) (POISSON, glm_label_const: once per example, whatever the number of particles).
+// No clamps: exp(t) = inf gives dl = inf, an infinite row norm, clip factor 0 (the example leaves the clipped sum) and ll = -inf,
+// what float32 jax computes.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float glm_label_const(int family, float y, float ll_const)
+{
+    if (family == D3P_FAMILY_POISSON) return lgammaf(y + 1.0f);
+    return ll_const;
+}
+
+// A_scale: the factor of dl in the per-column gradient (inv_obs * lik_scale): A = A_scale * dl is what the kernels use.
+__device__ __forceinline__ void glm_link(int family, float t, float y, float A_scale, float nh, float c, float& A, float& ll)
+{
+    if (family == D3P_FAMILY_LINREG) {
+        // every product and sum below is rounded on its own (no contraction): r = fl(t - y); dl = fl(r / sigma^2) with
+        // 1 / sigma^2 = -2 nh (exact doubling); A = fl(A_scale dl); ll = fl(fl(fl(nh r) r) - c)
+#pragma clang fp contract(off)
+        const float r = t - y;
+        A = A_scale * ((-2.0f * nh) * r);
+        ll = (nh * r) * r - c;
+    } else if (family == D3P_FAMILY_POISSON) {
+        // mu = expf(t) (not __expf: exp2(t log2 e) carries |t| ulp of relative error, and mu IS the gradient); then
+        // dl = fl(mu - y), A = fl(A_scale dl), ll = fl(fl(fl(y t) - mu) - c): each rounded on its own
+#pragma clang fp contract(off)
+        const float mu = expf(t);
+        A = A_scale * (mu - y);
+        ll = (y * t - mu) - c;
+    } else {  // (the two statements the logistic kernels have always had, in their order, left to the compiler's contraction as they were)
+        A = A_scale * (sigmoid_f(t) - y);
+        ll = y * t - softplus_f(t);
+    }
+}
+
 __device__ __forceinline__ void pack_column(const d3p_logreg_model& m, int D, int e, float loc, float u,
                                             float* __restrict__ pack)
 {
@@ -438,7 +478,7 @@ struct MainArgs {
     int dbg;  // developer ablation switches (0 in production)
     unsigned long long* stamps;  // nullable: per-workgroup {start, end} wall_clock64 (timing entry point)
     int family, gexp;            // likelihood family (non-FULL kernels only), guide transform
-    float nh_inv_var, ll_const;  // Gaussian family: -0.5 / sigma^2,  D * (log sigma + log(2 pi) / 2)
+    float nh_inv_var, ll_const;  // Gaussian families: -0.5 / sigma^2,  n * (log sigma + log(2 pi) / 2), n = D (mean) or 1 (regression)
     StepFuse fuse;               // MODE 2 / 3
     ChainFuse chain;             // MODE 3 only
 };
@@ -478,7 +518,10 @@ struct ExLoad {
 // (the scalar-load form needs fewer registers per tile slot: V = 1, NK = 2 fits 16 waves -- 114 VGPRs --, V = 1, NK = 4 eight -- 174)
 #define D3P_MAIN_MAX_THREADS(V, NK) ((NK) == 1 ? 1024 : (NK) == 2 ? ((V) == 1 ? 1024 : 512) : ((NK) == 4 && (V) == 1) ? 512 : 256)
 #define D3P_MAIN_MAX_WAVES(V, NK) (D3P_MAIN_MAX_THREADS(V, NK) / 64)
-template <int V, int NK, int MODE, bool FULL, int EPS, bool TAIL = false, bool STAMPS = false>
+// GLM: 0, or the family (D3P_FAMILY_LINREG / D3P_FAMILY_POISSON) of an instantiation of that regression: the link is a compile-time
+// choice in every instantiation, so linear regression carries neither expf nor lgammaf.  Every other
+// instantiation keeps the logistic link as a compile-time constant, so the new families cost it no register and no instruction.
+template <int V, int NK, int MODE, bool FULL, int EPS, bool TAIL = false, bool STAMPS = false, int GLM = 0>
 __global__ void __launch_bounds__(D3P_MAIN_MAX_THREADS(V, NK)) k_logreg_main(MainArgs a_in)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -840,7 +883,8 @@ __global__ void __launch_bounds__(D3P_MAIN_MAX_THREADS(V, NK)) k_logreg_main(Mai
     // 2.4-3.5 us later -- it waits for the 12 other waves, whose noise generation starts behind their index -> key load chain --
     // then dot / gradient / reduction 2.0 us, atomics + arrival 2.15 us.  Generating every wave's noise BEFORE the prologue
     // inside ONE workgroup does not help (12.2 -> 18.4 us per step); starting it a whole step earlier does: `pregen` below.)
-    const bool gauss = !FULL && a.family == D3P_FAMILY_GAUSS_MEAN;
+    const bool gauss = !FULL && !GLM && a.family == D3P_FAMILY_GAUSS_MEAN;
+    constexpr int glm_family = GLM ? GLM : D3P_FAMILY_LOGREG;  // the regression families' link (glm_link)
     int c0[NC], c1[NC];
     bool ok0[NC], ok1[NC];
 #pragma unroll
@@ -1118,9 +1162,8 @@ __global__ void __launch_bounds__(D3P_MAIN_MAX_THREADS(V, NK)) k_logreg_main(Mai
             if (gauss) {
                 A = 2.0f * a.A_scale * a.nh_inv_var;
                 loglik = __fmaf_rn(a.nh_inv_var, t, -a.ll_const);
-            } else {
-                A = a.A_scale * (sigmoid_f(t) - cur.y);
-                loglik = cur.y * t - softplus_f(t);
+            } else {  // (the logistic link at compile time unless GLM)
+                glm_link(glm_family, t, cur.y, a.A_scale, a.nh_inv_var, glm_label_const(glm_family, cur.y, a.ll_const), A, loglik);
             }
 
             // ---- per-example gradient, its squared norm and the latent part of the loss
@@ -1430,14 +1473,33 @@ static int launch_main(hipStream_t s, const MainGeom& g, const MainArgs& a, hipE
                        hipEvent_t e1 = nullptr)
 {
     // hipExtLaunchKernelGGL records e0/e1 tightly around the kernel (used by the timing entry point)
-#define D3P_LAUNCH_F(V_, NK_, F_, E_)                                                                                     \
-    if (e0)                                                                                                               \
-        hipExtLaunchKernelGGL((k_logreg_main<V_, NK_, MODE, F_, E_>), dim3(g.blocks), dim3(64 * g.W), g.lds, s, e0, e1, 0, \
-                              a);                                                                                         \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((k_logreg_main<V_, NK_, MODE, F_, E_>), dim3(g.blocks), dim3(64 * g.W), g.lds, s, a);          \
+    // (G_: the GLM template value -- 0, or the family of a linear / Poisson regression instantiation)
+#define D3P_LAUNCH_FG(V_, NK_, F_, E_, G_)                                                                                      \
+    if (e0)                                                                                                                     \
+        hipExtLaunchKernelGGL((k_logreg_main<V_, NK_, MODE, F_, E_, false, false, G_>), dim3(g.blocks), dim3(64 * g.W), g.lds, \
+                              s, e0, e1, 0, a);                                                                                 \
+    else                                                                                                                        \
+        hipLaunchKernelGGL((k_logreg_main<V_, NK_, MODE, F_, E_, false, false, G_>), dim3(g.blocks), dim3(64 * g.W), g.lds, s, \
+                           a);                                                                                                  \
     return check_launch("k_logreg_main")
-#define D3P_LAUNCH(V_, NK_) D3P_LAUNCH_F(V_, NK_, false, -1)
+#define D3P_LAUNCH_F(V_, NK_, F_, E_) D3P_LAUNCH_FG(V_, NK_, F_, E_, 0)
+    // the runtime-family (partly predicated) form of every tile: g.V x g.NK
+#define D3P_LAUNCH_TILE(G_)                                \
+    if (g.V == 4) {                                        \
+        switch (g.NK) {                                    \
+        case 1: D3P_LAUNCH_FG(4, 1, false, -1, G_);        \
+        case 2: D3P_LAUNCH_FG(4, 2, false, -1, G_);        \
+        case 4: D3P_LAUNCH_FG(4, 4, false, -1, G_);        \
+        default: D3P_LAUNCH_FG(4, 8, false, -1, G_);       \
+        }                                                  \
+    } else {                                               \
+        switch (g.NK) {                                    \
+        case 1: D3P_LAUNCH_FG(1, 1, false, -1, G_);        \
+        case 2: D3P_LAUNCH_FG(1, 2, false, -1, G_);        \
+        case 4: D3P_LAUNCH_FG(1, 4, false, -1, G_);        \
+        default: D3P_LAUNCH_FG(1, 8, false, -1, G_);       \
+        }                                                  \
+    }
 #define D3P_LAUNCH_T(NK_, E_)                                                                                               \
     if (e0)                                                                                                               \
         hipExtLaunchKernelGGL((k_logreg_main<4, NK_, MODE, true, E_, true>), dim3(g.blocks), dim3(64 * g.W), g.lds, s, e0,  \
@@ -1445,6 +1507,11 @@ static int launch_main(hipStream_t s, const MainGeom& g, const MainArgs& a, hipE
     else                                                                                                                  \
         hipLaunchKernelGGL((k_logreg_main<4, NK_, MODE, true, E_, true>), dim3(g.blocks), dim3(64 * g.W), g.lds, s, a);     \
     return check_launch("k_logreg_main")
+    if (a.family == D3P_FAMILY_LINREG || a.family == D3P_FAMILY_POISSON) {  // each in instantiations of its own (GLM = the family)
+        if (a.gexp == D3P_GUIDE_EXP_SITES || g.tail || g.full || g.wide)
+            return fail(D3P_E_UNSUPPORTED, "logreg kernel: linear / Poisson regression run the one-site, partly predicated forms only");
+        if (a.family == D3P_FAMILY_LINREG) { D3P_LAUNCH_TILE(D3P_FAMILY_LINREG) } else { D3P_LAUNCH_TILE(D3P_FAMILY_POISSON) }
+    }
     if (a.gexp == D3P_GUIDE_EXP_SITES) {  // two sample sites: the scalar-load form (main_geometry), the fused step modes only
         if (MODE == 0 || MODE == 1 || g.V != 1 || g.tail || g.wide)
             return fail(D3P_E_UNSUPPORTED, "logreg kernel: D3P_GUIDE_EXP_SITES runs the fused step of the scalar-load form only");
@@ -1488,24 +1555,11 @@ static int launch_main(hipStream_t s, const MainGeom& g, const MainArgs& a, hipE
             }
         }
     }
-    if (g.V == 4) {
-        switch (g.NK) {
-        case 1: D3P_LAUNCH(4, 1);
-        case 2: D3P_LAUNCH(4, 2);
-        case 4: D3P_LAUNCH(4, 4);
-        default: D3P_LAUNCH(4, 8);
-        }
-    } else {
-        switch (g.NK) {
-        case 1: D3P_LAUNCH(1, 1);
-        case 2: D3P_LAUNCH(1, 2);
-        case 4: D3P_LAUNCH(1, 4);
-        default: D3P_LAUNCH(1, 8);
-        }
-    }
+    D3P_LAUNCH_TILE(0)
+#undef D3P_LAUNCH_TILE
 #undef D3P_LAUNCH_F
+#undef D3P_LAUNCH_FG
 #undef D3P_LAUNCH_T
-#undef D3P_LAUNCH
 }
 
 static void fill_model_scalars(const d3p_logreg_model* m, MainArgs* a)
@@ -1525,8 +1579,10 @@ static void fill_model_scalars(const d3p_logreg_model* m, MainArgs* a)
     a->obs_scale = 1.0f / m->inv_obs;
     a->family = m->family;
     a->gexp = m->guide_transform;
-    a->nh_inv_var = m->family == D3P_FAMILY_GAUSS_MEAN ? -0.5f / (m->lik_sigma * m->lik_sigma) : 0.f;
-    a->ll_const = m->family == D3P_FAMILY_GAUSS_MEAN ? (float)D * (logf(m->lik_sigma) + 0.91893853320467267f) : 0.f;
+    const bool sigma = m->family == D3P_FAMILY_GAUSS_MEAN || m->family == D3P_FAMILY_LINREG;
+    a->nh_inv_var = sigma ? -0.5f / (m->lik_sigma * m->lik_sigma) : 0.f;
+    // (Gaussian mean: an event of D coordinates per example; linear regression: one scalar response)
+    a->ll_const = sigma ? (float)(m->family == D3P_FAMILY_LINREG ? 1 : D) * (logf(m->lik_sigma) + 0.91893853320467267f) : 0.f;
 }
 
 }  // namespace d3p

@@ -49,7 +49,8 @@ static inline int particles_max_latent(bool pxg)
     return D;
 }
 
-template <bool PXG>
+// GLM: 0, or the family of a linear / Poisson regression instantiation (as k_logreg_main's): the link is a compile-time choice.
+template <bool PXG, int GLM = 0>
 __global__ void __launch_bounds__(256) k_logreg_particles(ParticleArgs pa)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -66,7 +67,8 @@ __global__ void __launch_bounds__(256) k_logreg_particles(ParticleArgs pa)
     float* tail = lds + (size_t)W * particles_wave_floats(D, PXG);
     const float* pk = a.pack;  // [loc | s | sg | q | lc] x D
     const bool eps_from_mem = a.eps_ext != nullptr;
-    const bool gauss = a.family == D3P_FAMILY_GAUSS_MEAN;
+    const bool gauss = !GLM && a.family == D3P_FAMILY_GAUSS_MEAN;
+    constexpr int glm_family = GLM ? GLM : D3P_FAMILY_LOGREG;
     const uint32_t j0 = eps_from_mem ? 0u : pa.jax_key[0], j1 = eps_from_mem ? 0u : pa.jax_key[1];
     if (!PXG) {
         for (int c = lane; c < P; c += 64) acc[c] = 0.f;
@@ -102,6 +104,7 @@ __global__ void __launch_bounds__(256) k_logreg_particles(ParticleArgs pa)
         const size_t row = (size_t)((uint64_t)row_g - a.row_lo);
         const float* xrow = a.X + row * (size_t)d;
         const float yv = a.y ? a.y[row] : 0.f;
+        const float label_c = glm_label_const(glm_family, yv, a.ll_const);  // (once per example: no particle's parameters reach it)
         auto feat = [&](int c) { return c < d ? xrow[c] : 1.0f; };  // column d = intercept
         float Lsum = 0.f;
         for (uint32_t q = 0; q < K; ++q) {
@@ -143,8 +146,13 @@ __global__ void __launch_bounds__(256) k_logreg_particles(ParticleArgs pa)
             }
             const float t = wave_sum(tp);
             lp = wave_sum(lp);
-            const float A = gauss ? 2.0f * a.A_scale * a.nh_inv_var : a.A_scale * (sigmoid_f(t) - yv);
-            const float loglik = gauss ? __fmaf_rn(a.nh_inv_var, t, -a.ll_const) : yv * t - softplus_f(t);
+            float A, loglik;
+            if (gauss) {
+                A = 2.0f * a.A_scale * a.nh_inv_var;
+                loglik = __fmaf_rn(a.nh_inv_var, t, -a.ll_const);
+            } else {  // the regression families' link
+                glm_link(glm_family, t, yv, a.A_scale, a.nh_inv_var, label_c, A, loglik);
+            }
             Lsum += a.inv_obs * (lp - a.lik_scale * loglik);  // svi.py:278-281
 
             // ---- pass 2: the particle's gradient entries into the sum row
@@ -231,9 +239,11 @@ static inline uint32_t particles_blocks(int D, bool pxg, uint64_t items)
     return (uint32_t)(blocks > D3P_PART_MAX_BLOCKS ? D3P_PART_MAX_BLOCKS : blocks);
 }
 
-template <bool PXG>
+template <bool PXG, int GLM = 0>
 static int launch_particles(hipStream_t s, const ParticleArgs& pa, uint32_t blocks, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
+    if (!GLM && pa.a.family == D3P_FAMILY_LINREG) return launch_particles<PXG, D3P_FAMILY_LINREG>(s, pa, blocks, e0, e1);
+    if (!GLM && pa.a.family == D3P_FAMILY_POISSON) return launch_particles<PXG, D3P_FAMILY_POISSON>(s, pa, blocks, e0, e1);
     const int D = pa.a.D;
     const int W = particles_waves(D, PXG);
     if (W == 0)
@@ -242,15 +252,15 @@ static int launch_particles(hipStream_t s, const ParticleArgs& pa, uint32_t bloc
     if (pa.K < 2u) return fail(D3P_E_INVALID_ARG, "k_logreg_particles: K = 1 runs on the single-particle kernels");
     const size_t lds = particles_lds_bytes(D, W, PXG);
     // (the attribute is per function and device: set on every launch that needs it -- only rows of more than ~1600 columns do)
-    if (lds > 64u * 1024u && hipFuncSetAttribute(reinterpret_cast<const void*>(k_logreg_particles<PXG>),
+    if (lds > 64u * 1024u && hipFuncSetAttribute(reinterpret_cast<const void*>(k_logreg_particles<PXG, GLM>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)D3P_PART_LDS_MAX) != hipSuccess) {
         (void)hipGetLastError();
         return fail(D3P_E_HIP, "k_logreg_particles: hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed", lds);
     }
     if (e0)
-        hipExtLaunchKernelGGL(k_logreg_particles<PXG>, dim3(blocks), dim3(64 * W), lds, s, e0, e1, 0, pa);
+        hipExtLaunchKernelGGL((k_logreg_particles<PXG, GLM>), dim3(blocks), dim3(64 * W), lds, s, e0, e1, 0, pa);
     else
-        hipLaunchKernelGGL(k_logreg_particles<PXG>, dim3(blocks), dim3(64 * W), lds, s, pa);
+        hipLaunchKernelGGL((k_logreg_particles<PXG, GLM>), dim3(blocks), dim3(64 * W), lds, s, pa);
     return check_launch("k_logreg_particles");
 }
 

@@ -21,7 +21,8 @@ static inline size_t wide_lds_bytes(int P) { return (size_t)(D3P_WIDE_W * P + 2 
 
 // PXG: the materialising stage instead (MODE 1 of k_logreg_main, d3p_logreg_px_grads): pass 1, then one pass that writes
 // the example's unclipped gradient row and loss (zeros for masked-out positions); no accumulator rows, no partial rows.
-template <bool PXG>
+// GLM: 0, or the family of a linear / Poisson regression instantiation (as k_logreg_main's): the link is a compile-time choice.
+template <bool PXG, int GLM = 0>
 __global__ void __launch_bounds__(64 * D3P_WIDE_W) k_logreg_wide(MainArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -38,7 +39,8 @@ __global__ void __launch_bounds__(64 * D3P_WIDE_W) k_logreg_wide(MainArgs a)
     float* mine = acc + (size_t)wave * P;
     const float* pk = a.pack;         // [loc | s | sg | q | lc] x D
     const bool eps_from_mem = a.eps_ext != nullptr;
-    const bool gauss = a.family == D3P_FAMILY_GAUSS_MEAN;
+    const bool gauss = !GLM && a.family == D3P_FAMILY_GAUSS_MEAN;
+    constexpr int glm_family = GLM ? GLM : D3P_FAMILY_LOGREG;
     const bool vec_ok = !a.icpt && (d & 3) == 0 && (half & 3) == 0 && D == 2 * half &&
                         ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(pk) |
                           reinterpret_cast<uintptr_t>(a.eps_ext)) & 15u) == 0;
@@ -167,8 +169,13 @@ __global__ void __launch_bounds__(64 * D3P_WIDE_W) k_logreg_wide(MainArgs a)
         }
         const float t = wave_sum(tp);
         lp = wave_sum(lp);
-        const float A = gauss ? 2.0f * a.A_scale * a.nh_inv_var : a.A_scale * (sigmoid_f(t) - yv);
-        const float loglik = gauss ? __fmaf_rn(a.nh_inv_var, t, -a.ll_const) : yv * t - softplus_f(t);
+        float A, loglik;
+        if (gauss) {
+            A = 2.0f * a.A_scale * a.nh_inv_var;
+            loglik = __fmaf_rn(a.nh_inv_var, t, -a.ll_const);
+        } else {  // the regression families' link
+            glm_link(glm_family, t, yv, a.A_scale, a.nh_inv_var, glm_label_const(glm_family, yv, a.ll_const), A, loglik);
+        }
         const float L = a.inv_obs * (lp - a.lik_scale * loglik);  // svi.py:278-281
 
         if (PXG) {

@@ -291,7 +291,16 @@ __global__ void k_eval_loglik(d3p_logreg_model m, const float* __restrict__ X, c
     for (int c = lane; c < m.d; c += 64) tp = __fmaf_rn(X[(size_t)i * m.d + c], z[c], tp);
     float t = wave_sum(tp);
     if (m.intercept) t += z[m.d];
-    if (lane == 0) ll[i] = y[i] * t - softplus_f(t);
+    if (lane == 0) {
+        if (m.family == D3P_FAMILY_LOGREG) {
+            ll[i] = y[i] * t - softplus_f(t);
+        } else {  // linear / Poisson regression: the same link as the step kernels
+            const float c = glm_label_const(m.family, y[i], logf(m.lik_sigma) + 0.91893853320467267f);
+            float A, v;
+            glm_link(m.family, t, y[i], 1.0f, -0.5f / (m.lik_sigma * m.lik_sigma), c, A, v);
+            ll[i] = v;
+        }
+    }
 }
 
 __global__ void __launch_bounds__(256) k_eval_finish(d3p_logreg_model m, const float* __restrict__ ll, uint32_t B,
@@ -510,7 +519,12 @@ int d3p_logreg_px_grads(void* stream, const d3p_logreg_model* model, const float
     a.row_hi = B;
     a.clip = 1.0f;
     if (g.wide) {
-        hipLaunchKernelGGL(k_logreg_wide<true>, dim3(g.blocks), dim3(64 * D3P_WIDE_W), 0, s, a);
+        if (model->family == D3P_FAMILY_LINREG)
+            hipLaunchKernelGGL((k_logreg_wide<true, D3P_FAMILY_LINREG>), dim3(g.blocks), dim3(64 * D3P_WIDE_W), 0, s, a);
+        else if (model->family == D3P_FAMILY_POISSON)
+            hipLaunchKernelGGL((k_logreg_wide<true, D3P_FAMILY_POISSON>), dim3(g.blocks), dim3(64 * D3P_WIDE_W), 0, s, a);
+        else
+            hipLaunchKernelGGL(k_logreg_wide<true>, dim3(g.blocks), dim3(64 * D3P_WIDE_W), 0, s, a);
         return check_launch("k_logreg_wide");
     }
     return launch_main<1>(s, g, a);

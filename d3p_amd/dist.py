@@ -96,12 +96,20 @@ def _refuse_particles(svi, who):
                                   "(one particle only); run it on one GPU through DPSVI")
 
 
+def _refuse_glm(svi, who):
+    """Linear and Poisson regression run on one GPU: the data-parallel engines refuse them before anything touches a device."""
+    name = type(getattr(svi, "model", None)).__name__
+    if name in ("LinearRegression", "PoissonRegression"):
+        raise NotImplementedError(f"{who}: {name} is not supported by the data-parallel engines; run it on one GPU through DPSVI")
+
+
 class HipEngine:
     """local_sums / finalize through libd3p_hip.so for one rank's shard."""
 
     def __init__(self, svi, X_local, y_local, n_rows_global, row_lo, row_hi, kind, batch_size, q=0.0,
                  suppress=False, **model_kwargs):
         _refuse_particles(svi, type(self).__name__)
+        _refuse_glm(svi, type(self).__name__)
         _lib.require_device()
         self.svi, self.X, self.y = svi, _device_shard(X_local, "HipEngine: X"), _device_shard(y_local, "HipEngine: y")
         assert self.X.shape[0] == row_hi - row_lo
@@ -629,6 +637,7 @@ class VaeHipEngine:
 
     def __init__(self, svi, **model_kwargs):
         _refuse_particles(svi, "VaeHipEngine")
+        _refuse_glm(svi, "VaeHipEngine")
         _lib.require_device()
         if not svi._is_vae():
             raise _lib.D3PError("VaeHipEngine: the DPSVI object must hold a VAEModel / VAEGuide pair")
@@ -727,6 +736,7 @@ class GmmHipEngine:
 
     def __init__(self, svi, **model_kwargs):
         _refuse_particles(svi, "GmmHipEngine")
+        _refuse_glm(svi, "GmmHipEngine")
         _lib.require_device()
         if not svi._is_gmm():
             raise _lib.D3PError("GmmHipEngine: the DPSVI object must hold a GaussianMixtureModel / GaussianMixtureGuide pair")

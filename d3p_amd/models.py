@@ -47,6 +47,56 @@ class LogisticRegression:
         return None
 
 
+class LinearRegression:
+    """w ~ Normal(0, prior_scale)^d [, intercept ~ Normal(0, intercept_prior_scale)];
+    ys ~ Normal(xs @ w + intercept, obs_scale) inside ``plate('batch', N, batch_size)``.  ``obs_scale`` is a fixed standard
+    deviation (finite, > 0).  Same call signature, latent layout and site names as ``LogisticRegression``."""
+
+    has_labels = True
+
+    def __init__(self, d=None, prior_scale=1.0, intercept=False, intercept_prior_scale=1.0, obs_scale=1.0):
+        self.d = d
+        self.prior_scale = float(prior_scale)
+        self.intercept = bool(intercept)
+        self.intercept_prior_scale = float(intercept_prior_scale)
+        self.obs_scale = float(obs_scale)
+        if not (math.isfinite(self.obs_scale) and self.obs_scale > 0.0):
+            raise ValueError(f"LinearRegression: obs_scale must be finite and > 0 (got {obs_scale!r})")
+
+    latent_dim = LogisticRegression.latent_dim
+    site_names = LogisticRegression.site_names
+    num_obs_total = staticmethod(LogisticRegression.num_obs_total)
+
+
+class PoissonRegression:
+    """w ~ Normal(0, prior_scale)^d [, intercept ~ Normal(0, intercept_prior_scale)];
+    ys ~ Poisson(rate = exp(xs @ w + intercept)) inside ``plate('batch', N, batch_size)``.  Labels are counts held as floats.
+    ``validate_args=True`` checks the labels DPSVI is given (>= 0 and integral, else ``ValueError``; a host synchronisation per
+    call); the default leaves them to the caller, like numpyro with ``validate_args`` off.  Same call signature, latent layout and
+    site names as ``LogisticRegression``."""
+
+    has_labels = True
+
+    def __init__(self, d=None, prior_scale=1.0, intercept=False, intercept_prior_scale=1.0, validate_args=False):
+        self.d = d
+        self.prior_scale = float(prior_scale)
+        self.intercept = bool(intercept)
+        self.intercept_prior_scale = float(intercept_prior_scale)
+        self.validate_args = bool(validate_args)
+
+    latent_dim = LogisticRegression.latent_dim
+    site_names = LogisticRegression.site_names
+    num_obs_total = staticmethod(LogisticRegression.num_obs_total)
+
+    def check_labels(self, y):
+        """``validate_args=True``: raise ValueError unless every label is a count."""
+        if not self.validate_args or y is None:
+            return
+        y = torch.as_tensor(y)
+        if y.numel() and not bool(((y >= 0) & (y == torch.floor(y))).all()):
+            raise ValueError("PoissonRegression: labels must be integers >= 0 (validate_args=True)")
+
+
 class GaussianMean:
     """mu ~ Normal(0, prior_scale)^d;  obs ~ Normal(mu, obs_scale).to_event(1) inside
     ``plate('batch', num_obs_total, batch_size)`` (examples/simple_gaussian_posterior.py:51-65; the example

@@ -22,7 +22,7 @@ the intercept FIRST, while this build's kernels keep it as the last latent colum
 ``jax.random.normal(key, (D,))`` (UNPINNED -- DESIGN.md section 2 -- until the capture script has been run)."""
 from . import _lib
 from .models import (AutoDiagonalNormal, DiagonalNormalGuide, GaussianMean, GaussianMixtureGuide,
-                     GaussianMixtureModel, LogisticRegression, MeanFieldGuide)
+                     GaussianMixtureModel, LinearRegression, LogisticRegression, MeanFieldGuide, PoissonRegression)
 
 
 class FlatLayout:
@@ -113,22 +113,35 @@ def spec_from_sites(records):
     def normal_zero(r):
         return r["dist"] == "Normal" and r["params"].get("loc", None) in (0.0, None) and "scale" in r["params"]
 
-    # ---- Bayesian logistic regression (README.md:89-99; examples/logistic_regression.py:49-66)
-    if obs["dist"] in ("Bernoulli", "BernoulliLogits", "BernoulliProbs") and 1 <= len(latent) <= 2:
+    # ---- Gaussian observations with a latent mean (examples/simple_gaussian_posterior.py:51-65): an observed site whose rows have
+    #      the latent's shape (before the regression rule; a 1-D site of scalar events under a plate is a regression's response)
+    if obs["dist"] == "Normal" and len(latent) == 1 and normal_zero(latent[0]) and len(latent[0]["shape"]) == 1 \
+            and obs["shape"][-1:] == latent[0]["shape"] and "scale" in obs["params"] \
+            and (len(obs["shape"]) >= 2 or obs.get("event_dim", 0) >= 1 or not obs["plate_sizes"]):
+        mu = latent[0]
+        spec = GaussianMean(d=mu["shape"][0], prior_scale=mu["params"]["scale"], obs_scale=obs["params"]["scale"])
+        return spec, FlatLayout([(mu["name"], mu["shape"][0])], [mu["name"]]), n_total
+    # ---- regressions on a linear predictor xs @ w (+ intercept): one zero-mean Normal vector site, at most one zero-mean Normal
+    #      scalar site, nothing else latent (checked FIRST: another latent structure under one of these likelihoods is refused below).
+    #      Bernoulli: README.md:89-99, examples/logistic_regression.py:49-66; 1-D Normal with a constant scale: linear regression;
+    #      Poisson: count regression with the log link.
+    if 1 <= len(latent) <= 2:
         vec = [r for r in latent if len(r["shape"]) == 1 and r["shape"][0] >= 1 and normal_zero(r)]
         sca = [r for r in latent if r["shape"] == () and normal_zero(r)]
         if len(vec) == 1 and len(vec) + len(sca) == len(latent):
             w = vec[0]
-            spec = LogisticRegression(d=w["shape"][0], prior_scale=w["params"]["scale"], intercept=bool(sca),
-                                      intercept_prior_scale=sca[0]["params"]["scale"] if sca else 1.0)
-            build = [w["name"]] + ([sca[0]["name"]] if sca else [])        # this build: features first, intercept last
-            return spec, FlatLayout([(n, _numel(by_name[n]["shape"])) for n in names], build), n_total
-    # ---- Gaussian observations with a latent mean (examples/simple_gaussian_posterior.py:51-65)
-    if obs["dist"] == "Normal" and len(latent) == 1 and normal_zero(latent[0]) and len(latent[0]["shape"]) == 1 \
-            and obs["shape"][-1:] == latent[0]["shape"] and "scale" in obs["params"]:
-        mu = latent[0]
-        spec = GaussianMean(d=mu["shape"][0], prior_scale=mu["params"]["scale"], obs_scale=obs["params"]["scale"])
-        return spec, FlatLayout([(mu["name"], mu["shape"][0])], [mu["name"]]), n_total
+            common = dict(d=w["shape"][0], prior_scale=w["params"]["scale"], intercept=bool(sca),
+                          intercept_prior_scale=sca[0]["params"]["scale"] if sca else 1.0)
+            spec = None
+            if obs["dist"] in ("Bernoulli", "BernoulliLogits", "BernoulliProbs"):
+                spec = LogisticRegression(**common)
+            elif obs["dist"] == "Normal" and len(obs["shape"]) == 1 and "scale" in obs["params"]:
+                spec = LinearRegression(obs_scale=obs["params"]["scale"], **common)
+            elif obs["dist"] == "Poisson" and len(obs["shape"]) == 1:
+                spec = PoissonRegression(**common)
+            if spec is not None:
+                build = [w["name"]] + ([sca[0]["name"]] if sca else [])        # this build: features first, intercept last
+                return spec, FlatLayout([(n, _numel(by_name[n]["shape"])) for n in names], build), n_total
     # ---- mixture model of examples/gaussian_mixture_model.py:51-68
     if obs["dist"] == "GaussianMixture" and set(names) == {"pis", "mus", "sigs"} and by_name["pis"]["dist"] == "Dirichlet" \
             and by_name["sigs"]["dist"] == "InverseGamma" and normal_zero(by_name["mus"]):
@@ -136,7 +149,7 @@ def spec_from_sites(records):
         spec = GaussianMixtureModel(k=k, d=d, prior_mu_scale=by_name["mus"]["params"]["scale"])
         return spec, FlatLayout([(n, _numel(by_name[n]["shape"])) for n in names], ["pis", "mus", "sigs"]), n_total
     raise _lib.D3PError("numpyro adapter: the traced model is none of the families this build has kernels for "
-                        "(logistic regression, Gaussian mean, Gaussian mixture; the VAE is declared with VAEModel); "
+                        "(logistic / linear / Poisson regression, Gaussian mean, Gaussian mixture; the VAE is declared with VAEModel); "
                         f"latent sites {[(r['name'], r['dist'], r['shape']) for r in latent]}, observed "
                         f"{(obs['name'], obs['dist'], obs['shape'])}")
 

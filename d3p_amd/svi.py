@@ -18,11 +18,16 @@ from . import random as strong_rng
 from ._lib import BatchSource, DpsviHyper, DpsviState, GmmModel, LogregModel, VaeModel, check, ptr, stream_ptr
 from .optimizers import ADADP
 from .models import (SGD, Adam, AutoDiagonalNormal, DiagonalNormalGuide, GaussianMean, GaussianMixtureGuide, MeanFieldGuide,
-                     GaussianMixtureModel, LogisticRegression, VAEGuide, VAEModel,
+                     GaussianMixtureModel, LinearRegression, LogisticRegression, PoissonRegression, VAEGuide, VAEModel,
                      init_to_uniform, init_to_value)
 from .util import example_count
 
 PRNGState = Any
+
+# the families whose latent is one vector [w | intercept] (or mu) run by the logreg kernels, and their C family constants
+_FAMILY_OF = {LogisticRegression: _lib.D3P_FAMILY_LOGREG, GaussianMean: _lib.D3P_FAMILY_GAUSS_MEAN,
+              LinearRegression: _lib.D3P_FAMILY_LINREG, PoissonRegression: _lib.D3P_FAMILY_POISSON}
+_LATENT_VECTOR_MODELS = tuple(_FAMILY_OF)
 
 
 def _fresh_optim_state(optim_state):
@@ -237,8 +242,12 @@ class DPSVI:
         # Trace_ELBO(num_particles=K): every example's loss and gradient are means over K guide draws (clipped after the mean)
         self._num_particles = int(getattr(per_example_loss, "num_particles", 1))
         if self._num_particles > 1 and isinstance(model, (GaussianMixtureModel, VAEModel)):
-            raise NotImplementedError(f"DPSVI: Trace_ELBO(num_particles={self._num_particles}) is supported for the logistic-regression "
-                                      "and Gaussian-mean models only")
+            raise NotImplementedError(f"DPSVI: Trace_ELBO(num_particles={self._num_particles}) is supported for the logistic-, linear- and "
+                                      "Poisson-regression and Gaussian-mean models only")
+        if isinstance(model, (LinearRegression, PoissonRegression)) and isinstance(guide, MeanFieldGuide):
+            # (its native loop, D3P_GUIDE_EXP_SITES, is built for the logistic family only)
+            raise _lib.D3PError(f"DPSVI: MeanFieldGuide is built for LogisticRegression only; use AutoDiagonalNormal or "
+                                f"DiagonalNormalGuide with {type(model).__name__}")
 
     # ---------------------------------------------------------------- state helpers (svi.py:192-211)
     @staticmethod
@@ -379,16 +388,19 @@ class DPSVI:
                         1.0 / float(observation_scale))
 
     def _require_logreg(self):
-        if (not isinstance(self.model, (LogisticRegression, GaussianMean))
+        if (not isinstance(self.model, _LATENT_VECTOR_MODELS)
                 or not isinstance(self.guide, (AutoDiagonalNormal, DiagonalNormalGuide, MeanFieldGuide))):
-            raise _lib.D3PError("DPSVI: model must be d3p_amd.models.LogisticRegression or GaussianMean with an "
+            raise _lib.D3PError("DPSVI: model must be d3p_amd.models.LogisticRegression, LinearRegression, PoissonRegression or GaussianMean with an "
                                 "AutoDiagonalNormal, DiagonalNormalGuide or MeanFieldGuide guide (the model families built so far)")
 
     def _labels(self, args):
         """The label vector of the batch, or None for families without labels (GaussianMean)."""
         if not self.model.has_labels:
             return None
-        return _batch_array(args[1]).to(torch.float32)
+        y = _batch_array(args[1]).to(torch.float32)
+        if isinstance(self.model, PoissonRegression):
+            self.model.check_labels(y)     # (validate_args=True only)
+        return y
 
     def _model_struct(self, d, kwargs, observation_scale, sites=False):
         """The C model struct; ``sites``: MeanFieldGuide in the native run loop (D3P_GUIDE_EXP_SITES: two sample sites, four leaves,
@@ -399,10 +411,9 @@ class DPSVI:
         # a per-example batch has size 1, so plate(N, 1) scales the likelihood by N (svi.py:277)
         lik_scale = 1.0 if n_total is None else n_total
         m = self.model
-        gauss = isinstance(m, GaussianMean)
+        gauss = isinstance(m, (GaussianMean, LinearRegression))    # the families with an observation scale
         return LogregModel(int(d), int(m.intercept), m.prior_scale, m.intercept_prior_scale,
-                           float(lik_scale), 1.0 / float(observation_scale),
-                           _lib.D3P_FAMILY_GAUSS_MEAN if gauss else _lib.D3P_FAMILY_LOGREG,
+                           float(lik_scale), 1.0 / float(observation_scale), _FAMILY_OF[type(m)],
                            _lib.D3P_GUIDE_EXP_SITES if sites else
                            _lib.D3P_GUIDE_EXP if self.guide.transform == "exp" else _lib.D3P_GUIDE_SOFTPLUS,
                            m.obs_scale if gauss else 0.0)
@@ -709,7 +720,7 @@ class DPSVI:
 
     # ---------------------------------------------------------------- update (svi.py:395-434)
     def _fusable(self):
-        return (isinstance(self.model, (LogisticRegression, GaussianMean))
+        return (isinstance(self.model, _LATENT_VECTOR_MODELS)
                 and isinstance(self.guide, (AutoDiagonalNormal, DiagonalNormalGuide))
                 and isinstance(self.optim, Adam) and self._rng_suite is strong_rng)
 
@@ -825,7 +836,7 @@ class DPSVI:
         8178 for the clipped sums of update / run_steps, 13630 for the materialised per-example rows).  Checked before anything is
         enqueued, so the caller's state and outputs stay as they were."""
         K = self._num_particles
-        if K <= 1 or not isinstance(self.model, (LogisticRegression, GaussianMean)):
+        if K <= 1 or not isinstance(self.model, _LATENT_VECTOR_MODELS):
             return
         D = self.model.latent_dim(int(d))
         limit = int(_lib.load().d3p_logreg_particles_max_latent(int(bool(materialising))))
@@ -1069,6 +1080,8 @@ class DPSVI:
         lib = _lib.load()
         X = info.dataset[0]
         y = info.dataset[1] if self.model.has_labels else None
+        if isinstance(self.model, PoissonRegression):
+            self.model.check_labels(y)     # (validate_args=True only)
         if not (X.is_cuda and X.is_contiguous() and X.dtype == torch.float32
                 and (y is None or (y.is_cuda and y.is_contiguous() and y.dtype == torch.float32))):
             raise _lib.D3PError("run_steps: dataset arrays must be contiguous float32 CUDA tensors")

@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""Poisson (count) regression with DP-VI on MI355X: toy data generated on the device, the declared model PoissonRegression
+with AutoDiagonalNormal, training with the device-resident loop (`run_steps`), then the loss and the distance of the posterior mean
+from the weights that generated the data.
+
+    w ~ Normal(0, 1)^d, intercept ~ Normal(0, 1);  ys ~ Poisson(rate = exp(xs @ w + intercept))
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+import d3p_amd._lib as L  # noqa: E402
+import d3p_amd.random as rng_suite  # noqa: E402
+from d3p_amd.minibatch import subsample_batchify_data  # noqa: E402
+from d3p_amd.models import Adam, AutoDiagonalNormal, PoissonRegression, Trace_ELBO  # noqa: E402
+from d3p_amd.svi import DPSVI  # noqa: E402
+
+
+def create_toy_data(N, d, seed=123):
+    """w_true ~ N(0, 1 / d), X ~ N(0, 1), y ~ Poisson(exp(X w_true)), on the device with a fixed seed."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    w_true = torch.randn(d, generator=g, device="cuda") / d ** 0.5
+    X = torch.randn(N, d, generator=g, device="cuda")
+    y = torch.poisson(torch.exp(X @ w_true), generator=g)
+    return X.contiguous(), y.to(torch.float32).contiguous(), w_true
+
+
+def main(args):
+    L.require_device()
+    N, d = args.num_samples, args.dimensions
+    X, y, w_true = create_toy_data(N, d)
+    model = PoissonRegression(d, prior_scale=1.0, intercept=True)
+    svi = DPSVI(model, AutoDiagonalNormal(model), Adam(args.learning_rate), Trace_ELBO(), dp_scale=args.sigma,
+                clipping_threshold=args.clip_threshold, num_obs_total=N, rng_suite=rng_suite)
+    key, init_key, batch_key = rng_suite.split(rng_suite.PRNGKey(0), 3)
+    init, get_batch = subsample_batchify_data((X, y), args.batch_size, rng_suite=rng_suite)
+    _, batchifier_state = init(rng_key=batch_key)
+    state = svi.init(init_key, *get_batch(0, batchifier_state))
+    err0 = float((svi.get_params(state)["auto_loc"][:d] - w_true).norm())
+    state, losses = svi.run_steps(state, get_batch, batchifier_state, 0, args.num_steps)
+    torch.cuda.synchronize()
+    k = max(1, args.num_steps // 10)
+    first, last = float(losses[:k].mean()) / N, float(losses[-k:].mean()) / N
+    err = float((svi.get_params(state)["auto_loc"][:d] - w_true).norm())
+    print("loss per example: first {:.4f} -> last {:.4f};  |loc - w_true|: {:.4f} -> {:.4f}".format(first, last, err0, err))
+    return first, last, err0, err
+
+
+if __name__ == "__main__":
+    parser = argparse.ArgumentParser(description="parse args")
+    parser.add_argument('--sigma', default=0.5, type=float, help='dp_scale of the Gaussian mechanism')
+    parser.add_argument('--clip-threshold', default=1.0, type=float, help='clipping threshold of the per-example gradients')
+    parser.add_argument('-n', '--num-steps', default=2000, type=int, help='number of training steps')
+    parser.add_argument('-lr', '--learning-rate', default=2.0e-2, type=float, help='learning rate')
+    parser.add_argument('-batch-size', default=200, type=int, help='batch size')
+    parser.add_argument('-d', '--dimensions', default=4, type=int, help='data dimension')
+    parser.add_argument('-N', '--num-samples', default=10000, type=int, help='data samples count')
+    main(parser.parse_args())

@@ -176,11 +176,17 @@ typedef struct {
                               *   are in tree order [intercept_loc, intercept_std_log, w_loc (d), w_std_log (d)].  Accepted by the
                               *   single-GPU runs only (d3p_dpvi_logreg_run, _run_from, _run_particles_from with one particle,
                               *   _run_status); every other entry point refuses it before any launch. */
-    float lik_sigma;         /* observation std of D3P_FAMILY_GAUSS_MEAN */
+    float lik_sigma;         /* observation std of D3P_FAMILY_GAUSS_MEAN and D3P_FAMILY_LINREG */
 } d3p_logreg_model;
 
 #define D3P_FAMILY_LOGREG 0
 #define D3P_FAMILY_GAUSS_MEAN 1
+/* Generalised linear models on the logistic regression's kernels (same latent layout, labels required).  They run wherever
+ * D3P_FAMILY_GAUSS_MEAN runs, on one GPU: the staged per-example rows, the fused update, d3p_dpvi_logreg_run / _run_from (Feistel
+ * and Poisson batches), rows wider than 2048 columns, d3p_logreg_evaluate and the *_particles entries.  Refused with
+ * D3P_E_UNSUPPORTED before any launch: a row range that is not the whole table (data-parallel shards) and D3P_GUIDE_EXP_SITES. */
+#define D3P_FAMILY_LINREG 2  /* ys ~ Normal(xs.w + b, lik_sigma); lik_sigma finite and > 0 */
+#define D3P_FAMILY_POISSON 3 /* ys ~ Poisson(rate = exp(xs.w + b)); labels are counts stored as floats (not checked) */
 #define D3P_GUIDE_SOFTPLUS 0
 #define D3P_GUIDE_EXP 1
 #define D3P_GUIDE_EXP_SITES 2

@@ -6,3 +6,13 @@ and drives hand-written gfx950 kernels through the C-ABI of ``libd3p_hip.so`` (i
 PyTorch is used for device memory, streams and torch.distributed only.
 """
 from .version import __version__  # noqa: F401
+
+__all__ = ["infer_util"]
+
+
+def __getattr__(name):
+    # d3p_amd.infer_util (log_likelihood, log predictive densities) without making `import d3p_amd` import torch
+    if name == "infer_util":
+        import importlib
+        return importlib.import_module(".infer_util", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -86,6 +86,18 @@ inline int validate_model(const d3p_logreg_model* m, const void* y_dev, const ch
     return D3P_OK;
 }
 
+// device (or managed) memory of this process: a host pointer must never reach a kernel
+inline bool is_device_ptr(const void* p)
+{
+    if (!p) return false;
+    hipPointerAttribute_t at;
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    (void)hipGetLastError();   // an unregistered host pointer leaves an error behind; it must not be reported by a later launch check
+    return e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+}
+
+#define D3P_REQUIRE_DEV(p, msg) D3P_REQUIRE(d3p::is_device_ptr(p), msg)
+
 inline unsigned cdiv(unsigned long long a, unsigned long long b) { return (unsigned)((a + b - 1) / b); }
 
 // in-place sum-all-reduce of `count` floats over the ranks of a d3p_comm_* communicator (RCCL, resolved at run time: d3p_dpvi.hip)

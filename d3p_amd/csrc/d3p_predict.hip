@@ -264,18 +264,7 @@ __global__ void __launch_bounds__(256) k_predict_vae_obs(const float* __restrict
     if (j2 < size) obs[base + j2] = bernoulli_draw(wb, sigmoid_probs(logits[base + j2]));
 }
 
-// device (or managed) memory of this process: a host pointer must never reach a kernel
-static bool is_device_ptr(const void* p)
-{
-    if (!p) return false;
-    hipPointerAttribute_t at;
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    (void)hipGetLastError();   // an unregistered host pointer leaves an error behind; it must not be reported by a later launch check
-    return e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
-}
-
-#define D3P_REQUIRE_DEV(p, msg) D3P_REQUIRE(is_device_ptr(p), msg)
-
+// (is_device_ptr / D3P_REQUIRE_DEV: d3p_host.h)
 static int draws_validate(uint32_t n, int32_t posterior, const d3p_predict_site* sites, int32_t n_sites, int32_t obs_chain, int32_t obs_index,
                           const float* latent, int64_t ld, const uint32_t* obs_keys, const char* what)
 {

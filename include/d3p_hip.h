@@ -779,6 +779,21 @@ size_t d3p_predict_vae_workspace(const d3p_vae_model* model, uint32_t B, uint32_
 int d3p_predict_vae(void* stream, const d3p_vae_model* model, const float* params_dev, const float* X_dev, uint32_t B, const uint32_t* key_dev,
                     uint32_t n, int32_t multi, const float* z_subst_dev, float* z_dev, int32_t* obs_dev, void* workspace_dev, size_t workspace_bytes);
 
+/* Pointwise log-likelihoods over given posterior draws (numpyro.infer.util.log_likelihood; d3p_amd/infer_util.py); added symbols,
+ * ABI 9 and d3p_logreg_model unchanged.  With t[s, r] = X[r] . latent[s, w_off .. w_off + d) + latent[s, b_col] (b_col = -1: no intercept;
+ * the layout of d3p_predict_logreg) and ll[s, r] = log p(y_r | t[s, r]) of model->family -- UNSCALED: model->lik_scale and inv_obs are
+ * not applied, lik_sigma is (D3P_FAMILY_LINREG) -- in float32, no clamps (Poisson: exp(t) = inf gives -inf):
+ *   d3p_loglik_rows   out_dev[s, r] = ll[s, r]                                   (n x rows floats)
+ *   d3p_loglik_lppd   out_rows_dev[r] = logsumexp_s ll[s, r] - log n             (rows floats; no n x rows intermediate; a row whose
+ *                     every draw is -inf gives -inf; deterministic)
+ * D3P_E_UNSUPPORTED before any launch: D3P_FAMILY_GAUSS_MEAN and D3P_GUIDE_EXP_SITES (the guide transform is not read otherwise).
+ * D3P_E_INVALID_ARG: a null X / y / latent / out, n < 1, d < 1, b_col >= 0 without model->intercept (or the reverse).  rows == 0: D3P_OK,
+ * no launch. */
+int d3p_loglik_rows(void* stream, const d3p_logreg_model* model, const float* X_dev, const float* y_dev, uint64_t rows, const float* latent_dev,
+                    int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, float* out_dev);
+int d3p_loglik_lppd(void* stream, const d3p_logreg_model* model, const float* X_dev, const float* y_dev, uint64_t rows, const float* latent_dev,
+                    int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, float* out_rows_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

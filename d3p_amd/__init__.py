@@ -7,12 +7,13 @@ PyTorch is used for device memory, streams and torch.distributed only.
 """
 from .version import __version__  # noqa: F401
 
-__all__ = ["infer_util"]
+__all__ = ["infer_util", "prediction"]
 
 
 def __getattr__(name):
-    # d3p_amd.infer_util (log_likelihood, log predictive densities) without making `import d3p_amd` import torch
-    if name == "infer_util":
+    # d3p_amd.infer_util (log_likelihood, log predictive densities) and d3p_amd.prediction (posterior predictive mean and variance)
+    # without making `import d3p_amd` import torch
+    if name in ("infer_util", "prediction"):
         import importlib
-        return importlib.import_module(".infer_util", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

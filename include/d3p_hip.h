@@ -794,6 +794,19 @@ int d3p_loglik_rows(void* stream, const d3p_logreg_model* model, const float* X_
 int d3p_loglik_lppd(void* stream, const d3p_logreg_model* model, const float* X_dev, const float* y_dev, uint64_t rows, const float* latent_dev,
                     int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, float* out_rows_dev);
 
+/* Posterior predictive mean and variance of the observed site over given posterior draws (d3p_amd/prediction.py); added symbol, ABI 9
+ * and d3p_logreg_model unchanged.  With t[s, r] as above, mu = E[y | t] = sigmoid(t) | t | exp(t) and v = Var[y | t] = mu (1 - mu) |
+ * lik_sigma^2 | mu (D3P_FAMILY_LOGREG | LINREG | POISSON):
+ *   mean_rows_dev[r] = (1/n) sum_s mu[s, r]
+ *   var_rows_dev[r]  = (1/n) sum_s v[s, r] + (1/n) sum_s (mu[s, r] - mean[r])^2        (law of total variance, population form)
+ * float32 links without clamps, float64 accumulation in draw order, one rounding to float32; no n x rows intermediate; deterministic.
+ * A NaN t makes the row NaN; otherwise a +inf mu (Poisson: exp(t) overflows) makes the row (+inf, +inf), never NaN.  There are no
+ * labels.  Arguments, limits and errors are d3p_loglik_lppd's: D3P_E_UNSUPPORTED before any launch for D3P_FAMILY_GAUSS_MEAN and
+ * D3P_GUIDE_EXP_SITES; D3P_E_INVALID_ARG for a null X / latent / mean / var, n < 1, d < 1, a latent layout that does not fit, b_col >= 0
+ * without model->intercept (or the reverse), a D3P_FAMILY_LINREG lik_sigma that is not finite and > 0; rows == 0: D3P_OK, no launch. */
+int d3p_predict_moments(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, const float* latent_dev,
+                        int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, float* mean_rows_dev, float* var_rows_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

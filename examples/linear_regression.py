@@ -47,6 +47,12 @@ def main(args):
     first, last = float(losses[:k].mean()) / N, float(losses[-k:].mean()) / N
     err = float((svi.get_params(state)["auto_loc"][:d] - w_true).norm())
     print("loss per example: first {:.4f} -> last {:.4f};  |loc - w_true|: {:.4f} -> {:.4f}".format(first, last, err0, err))
+    # posterior predictive check: the observed outcomes against 100 draws of `obs` at the trained parameters
+    from d3p_amd.predictive import posterior_predictive_samples
+    import d3p_amd.random.debug as jax_random
+    pred = posterior_predictive_samples(jax_random.PRNGKey(1), 100, model, (X,), svi.guide, svi.get_params(state))["obs"].double()
+    print("posterior predictive check (100 draws): observed mean {:.4f}, variance {:.4f};  predictive mean {:.4f}, variance {:.4f}".format(
+        float(y.mean()), float(y.var()), float(pred.mean()), float(pred.var(dim=1).mean())))
     return first, last, err0, err
 
 

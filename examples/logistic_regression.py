@@ -96,6 +96,10 @@ def main(args):
         import d3p_amd.random.debug as jax_random
         acc_post = estimate_accuracy(test[0], test[1], model, guide, svi.get_params(svi_state), jax_random.PRNGKey(1), 100)
         print("avg accuracy on test set with found posterior (100 posterior-predictive draws): {:.4f}".format(acc_post))
+        from d3p_amd.predictive import posterior_predictive_samples   # the regression family's sampler: modelling's draws for this model
+        pred = posterior_predictive_samples(jax_random.PRNGKey(1), 100, model, (test[0],), guide, svi.get_params(svi_state))["obs"]
+        print("posterior predictive check (100 draws): observed mean {:.4f}, predictive mean {:.4f}".format(
+            float(test[1].mean()), float(pred.float().mean())))
     return accs, train_losses
 
 

@@ -807,6 +807,19 @@ int d3p_loglik_lppd(void* stream, const d3p_logreg_model* model, const float* X_
 int d3p_predict_moments(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, const float* latent_dev,
                         int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, float* mean_rows_dev, float* var_rows_dev);
 
+/* Predictive sampling of the linear and Poisson regression families (d3p_amd/predictive.py); added symbol, ABI 9 and d3p_logreg_model
+ * unchanged.  With t[s, r] as above (d3p_predict_logreg's layout, tile and grid) and obs_keys_dev as d3p_predict_draws returns them:
+ *   D3P_FAMILY_LINREG    obs_dev[s, r] = fl(t + fl(normal(obs_keys[s], (rows,))[r] * lik_sigma))        n x rows float32
+ *   D3P_FAMILY_POISSON   obs_dev[s, r] = a Poisson(exp(t)) draw by the project's own rule (d3p_predict_glm.hip, DESIGN.md 4b / 4e:
+ *                        inversion below a rate of 10, Hoermann's PTRS from there, on the uniforms of fold_in(obs_keys[s], j); NaN t:
+ *                        -1, rate 0: 0, rate +inf or a draw above 2^31 - 1: 2147483647)                 n x rows int32
+ * t, the normals and the uniforms never reach memory; deterministic.  Arguments, limits and errors are d3p_predict_logreg's, plus:
+ * D3P_E_UNSUPPORTED before any launch for every other family and for D3P_GUIDE_EXP_SITES; D3P_E_INVALID_ARG for d != model->d, a
+ * D3P_FAMILY_LINREG lik_sigma that is not finite and > 0, b_col >= 0 without model->intercept (or the reverse), and 2 rows >= 2^32 for
+ * D3P_FAMILY_POISSON; rows == 0: D3P_OK, no launch. */
+int d3p_predict_glm(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, int32_t d, const float* latent_dev,
+                    int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, const uint32_t* obs_keys_dev, void* obs_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

@@ -820,6 +820,31 @@ int d3p_predict_moments(void* stream, const d3p_logreg_model* model, const float
 int d3p_predict_glm(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, int32_t d, const float* latent_dev,
                     int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, const uint32_t* obs_keys_dev, void* obs_dev);
 
+/* Predictive sampling and cluster assignment of the Gaussian mixture model (d3p_amd/mixture.py, d3p_predict_gmm.hip);
+ * added symbols, ABI 9 and d3p_gmm_model unchanged.  Limits of all three: k <= 16 with d <= 256 or k <= 32 with d <= 128, otherwise
+ * D3P_E_UNSUPPORTED before any launch; k < 1, d < 1, a null required pointer or one not aligned to 4 bytes: D3P_E_INVALID_ARG.
+ *
+ * d3p_predict_gmm_draws   one launch writes latent_dev, n rows [pis (k) | mus (k d) | sigs (k d)], and obs_keys_dev, n threefry keys.
+ *   Draw i runs on split(key, n)[i] (multi == 0: n == 1, the key itself); the prior (posterior == 0) seeds the model's chain with that
+ *   key, the posterior splits it into (model, guide); the sites take `chain, site_key = split(chain)` in program order pis, mus, sigs,
+ *   then obs on the model's chain.  A site whose *_value_dev is given (prior only) is copied into every draw and takes no key.
+ *   pis = g / sum g with g_j the project's own Gamma(alpha_j, 1) draw in float64 (alpha_j = exp(alpha_log_j), prior: 1); mus =
+ *   fl(loc + fl(normal scale)) with (loc, scale) = (mus_loc, 1) or (0, prior_mu_scale); sigs = 1 / -logf(u).  n >= 1.
+ * d3p_predict_gmm_obs     obs_dev[s, r, c] = fl(mus[z, c] + fl(sigs[z, c] eps)) of draw s's latent row, with component_key, samples_key
+ *   = split(obs_keys[s]), z = min(#{j : cum_j < uniform(component_key, (rows, 1))[r]}, k - 1), cum the float32 running sum of pis
+ *   left to right, eps = normal(samples_key, (rows, d))[r, c]; zs_out_dev (n x rows int32, nullable) receives z.  latent_ld >= k + 2 k d;
+ *   rows d < 2^32, otherwise D3P_E_UNSUPPORTED; n >= 1 (65535 draws per launch, more in several); rows == 0: D3P_OK, no launch.
+ * d3p_gmm_assign          a_out_dev[r, j] = log pis_j + sum_c log N(obs[r, c]; mus[j, c], sigs[j, c]) (rows x k float32, nullable) and
+ *   argmax_out_dev[r] = argmax_j of that row, the first maximum on ties (rows int32, nullable; a is not written for it); at least one
+ *   of the two.  A NaN in a row of a makes the whole row NaN and its argmax -1.  rows d < 2^32; rows == 0: D3P_OK, no launch. */
+int d3p_predict_gmm_draws(void* stream, const uint32_t* key_dev, uint32_t n, int32_t multi, int32_t posterior, int32_t k, int32_t d,
+                          const float* alpha_log_dev, const float* mus_loc_dev, float prior_mu_scale, const float* pis_value_dev,
+                          const float* mus_value_dev, const float* sigs_value_dev, float* latent_dev, uint32_t* obs_keys_dev);
+int d3p_predict_gmm_obs(void* stream, const float* latent_dev, int64_t latent_ld, int32_t k, int32_t d, uint64_t rows, uint32_t n,
+                        const uint32_t* obs_keys_dev, float* obs_dev, int32_t* zs_out_dev);
+int d3p_gmm_assign(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* mus_dev, const float* sigs_dev,
+                   const float* pis_dev, int32_t k, float* a_out_dev, int32_t* argmax_out_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

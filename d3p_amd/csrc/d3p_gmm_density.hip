@@ -1,0 +1,303 @@
+// Held-out log predictive density and responsibilities of the Gaussian mixture model over n posterior draws
+// (d3p_amd/mixture_density.py).  The latents are the packed rows d3p_predict_gmm_draws writes: draw s is
+// [pis (k) | mus (k d) | sigs (k d)] at latent + s latent_ld.  With
+//   a[s, r, j] = log pis[s, j] + sum_c ( -((x[r, c] - mus[s, j, c]) / sigs[s, j, c])^2 / 2 - log sigs[s, j, c] - log(2 pi) / 2 )
+// the outputs are
+//   rows form     ll[s, r]   = logsumexp_j a[s, r, j]                                 (n x rows)
+//   reduced form  lppd[r]    = logsumexp_s ll[s, r] - log n                           (rows)
+//                 resp[r, j] = (1 / n) sum_s exp(a[s, r, j] - ll[s, r])               (rows x k)
+// The reduced form writes neither a nor ll to memory.
+//
+// Geometry.  A workgroup owns D3P_GD_ROW_TILE = 64 rows, staged once in LDS with an odd stride (d | 1: the 32 lanes of a bank group
+// read 32 different banks), and walks all n draws: obs is read from memory once.  Lane l of every wave owns row l.  The workgroup's W
+// waves split the draws: wave w takes the draws s = w, w + W, w + 2 W, ... in that order.  W = D3P_GD_DRAW_TILE = 4; only where the
+// staged latents of four draws do not fit beside the row tile (k d > 3584 or so: the two largest shapes) W = 2.  W depends on (k, d)
+// alone, never on rows, n or the grid.
+//
+// Per draw a wave stages its own copy of the draw in LDS as pairs (mus, 1 / sigs) -- the reciprocal is formed ONCE per draw, a term is
+// t = x - mu; z = t rinv; q += z z -- and hoists, per component, C_j = (logf(pis_j) - H_j) - fl(d) log(2 pi) / 2 with H_j = sum_c
+// logf(sigs_jc) taken in index order in float32 (the logs go through LDS transposed, so that lane j sums component j without a bank
+// conflict).  Then a_j = -0.5 q_j + C_j, every operation rounded on its own (fp contract off): tests/mixture_density_ref.py restates
+// exactly this order.  The DIRECT form, as k_gmm_assign's comment explains: vector float32, not a matrix product.  The pair reads are
+// wave-uniform addresses (LDS broadcasts, one ds_read_b64 per term); a lane's sum over c runs in index order with no cross-lane step.
+//
+// ll = m + logf(sum_j expf(a_j - m)), m = max_j a_j, the sum in index order; a draw's responsibility of j is expf(a_j - m) * (1 / sum).
+// Per row a wave keeps a running (max, sum) of ll exactly as k_loglik's lppd form does (one expf per draw, the sum in float64) and k
+// float64 responsibility sums in registers (KMAX = 4 / 16 / 32).  At the end the waves hand their accumulators to wave 0 through LDS,
+// wave 1 first, then 2, then 3: a fixed order, no atomics, bit-identical between calls.
+//
+// Special values: pis_j = 0 gives a_j = -inf, which adds nothing; a draw whose every a_j is -inf has ll = -inf (never NaN) and
+// contributes NaN (0 / 0) to the row's resp; every draw -inf gives lppd = -inf.  A NaN in a row of obs or in a draw's latents makes
+// every a_j of that (draw, row) NaN in effect: ll is NaN and so is every responsibility, as d3p_gmm_assign makes the whole row NaN.
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "d3p_device.h"
+#include "d3p_host.h"
+
+namespace d3p {
+
+#define D3P_GD_ROW_TILE 64
+#define D3P_GD_DRAW_TILE 4
+#define D3P_GD_LDS_MAX 163840   // 160 KiB: a compute unit's LDS
+
+struct GmmDensityArgs {
+    const float* obs;
+    const float* lat;
+    int64_t ld;
+    uint32_t rows, n;
+    int k, d;
+    float* ll;     // rows form
+    float* lppd;   // reduced form, nullable
+    float* resp;   // reduced form, nullable
+};
+
+// floats of LDS in front of the waves' latent copies (the row tile, rounded up to a float2 boundary) and per wave
+__host__ __device__ inline int gd_tile_floats(int d) { return (D3P_GD_ROW_TILE * (d | 1) + 1) & ~1; }
+__host__ __device__ inline int gd_wave_floats(int k, int d) { return 2 * k * d + ((k + 1) & ~1); }
+
+template <int KMAX, int REDUCE>
+__global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
+{
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = (int)(blockDim.x >> 6);
+    const int k = g.k, d = g.d, kd = k * d, ldx = d | 1;
+    float* xs = lds;
+    float* mine = lds + gd_tile_floats(d) + wave * gd_wave_floats(k, d);
+    float2* st = reinterpret_cast<float2*>(mine);   // [j d + c] = (mus, 1 / sigs)
+    float* lg = mine;                               // [c k + j] = logf(sigs): the same floats, before the pairs are written
+    float* cj = mine + 2 * kd;                      // [j] = C_j
+    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_GD_ROW_TILE;
+    const uint32_t left = g.rows - (uint32_t)r0;
+    const uint32_t total = (left < D3P_GD_ROW_TILE ? left : D3P_GD_ROW_TILE) * (uint32_t)d;
+    for (uint32_t e = tid; e < (uint32_t)(D3P_GD_ROW_TILE * d); e += blockDim.x) {
+        const uint32_t row = e / (uint32_t)d, c = e - row * (uint32_t)d;
+        xs[row * ldx + c] = e < total ? g.obs[r0 * (uint64_t)d + e] : 0.f;   // (rows past the end: zeros, never written out)
+    }
+    const bool live = r0 + lane < g.rows;
+    const float* xrow = xs + lane * ldx;
+    float run_m = -INFINITY;
+    double run_s = 0.0;
+    double racc[KMAX];
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) racc[j] = 0.0;
+    // every wave runs the same number of passes (the barriers are workgroup-wide); a wave without a draw in the last pass idles
+    const uint32_t passes = (g.n + (uint32_t)W - 1) / (uint32_t)W;
+    for (uint32_t it = 0; it < passes; ++it) {
+        const uint32_t s = it * (uint32_t)W + (uint32_t)wave;
+        const bool active = s < g.n;
+        const float* row = g.lat + (size_t)s * (size_t)g.ld;
+        __syncthreads();   // the previous draw's pairs are read (first pass: the row tile is staged)
+        if (active)
+            for (int j = 0; j < k; ++j)
+                for (int c = lane; c < d; c += 64) lg[c * k + j] = logf(row[k + kd + j * d + c]);
+        __syncthreads();
+        float C = 0.f;
+        if (active && lane < k) {
+            float H = 0.f;
+            for (int c = 0; c < d; ++c) H = H + lg[c * k + lane];   // index order
+            C = (logf(row[lane]) - H) - (float)d * D3P_HALF_LOG_2PI;
+        }
+        __syncthreads();   // the logs are read before the pairs overwrite them
+        if (active) {
+            if (lane < k) cj[lane] = C;
+            for (int j = 0; j < k; ++j)
+                for (int c = lane; c < d; c += 64) st[j * d + c] = make_float2(row[k + j * d + c], 1.0f / row[k + kd + j * d + c]);
+        }
+        __syncthreads();
+        if (!(active && live)) continue;   // (no barrier below this line inside the loop)
+        float q[KMAX];
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) q[j] = 0.f;
+        for (int c = 0; c < d; ++c) {
+            const float xv = xrow[c];
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) {
+                if (j < k) {
+                    const float2 p = st[j * d + c];
+                    const float t = xv - p.x;
+                    const float z = t * p.y;
+                    q[j] = q[j] + z * z;
+                }
+            }
+        }
+        float m = -INFINITY;
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) {
+            if (j < k) {
+                const float a = -0.5f * q[j] + cj[j];
+                q[j] = a;
+                nan |= a != a;
+                m = a > m ? a : m;
+            }
+        }
+        float ll, rinv;
+        if (nan || m == -INFINITY) {
+            // a NaN anywhere: the whole (draw, row) is NaN; every component -inf: ll = -inf and the responsibilities are 0 / 0
+            ll = nan ? __builtin_nanf("") : -INFINITY;
+            rinv = __builtin_nanf("");
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) q[j] = 1.f;
+        } else {
+            float sum = 0.f;
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) {
+                if (j < k) {
+                    const float e = expf(q[j] - m);
+                    q[j] = e;
+                    sum = sum + e;   // index order
+                }
+            }
+            ll = m + logf(sum);
+            rinv = 1.0f / sum;
+        }
+        if (!REDUCE) {
+            g.ll[(size_t)s * g.rows + (r0 + lane)] = ll;
+        } else {
+            // k_loglik's running (max, sum): one expf per draw, the sum in float64
+            if (ll > run_m) {
+                run_s = run_s * (double)expf(run_m - ll) + 1.0;
+                run_m = ll;
+            } else if (ll != -INFINITY) {   // (a NaN ll makes the sum NaN)
+                run_s += (double)expf(ll - run_m);
+            }
+            if (g.resp) {
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j)
+                    if (j < k) racc[j] += (double)(q[j] * rinv);
+            }
+        }
+    }
+    if (REDUCE) {
+        // waves 1 .. W - 1 hand their accumulators to wave 0, one after the other; the row tile and the latents are no longer needed
+        double* Rs = reinterpret_cast<double*>(lds);   // [j][lane]
+        double* Ss = Rs + (size_t)k * 64;              // [lane]
+        float* Ms = reinterpret_cast<float*>(Ss + 64);  // [lane]
+        __syncthreads();
+        for (int w = 1; w < W; ++w) {
+            if (wave == w) {
+                Ss[lane] = run_s;
+                Ms[lane] = run_m;
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j)
+                    if (j < k) Rs[j * 64 + lane] = racc[j];
+            }
+            __syncthreads();
+            if (wave == 0) {
+                const double s1 = Ss[lane];
+                const float m1 = Ms[lane];
+                const float mm = fmaxf(run_m, m1);
+                // a wave that saw no finite value has sum 0 -- or NaN, if a NaN came by: it is taken as it is, so a NaN stays
+                const double a0 = run_m == -INFINITY ? run_s : run_s * exp((double)run_m - (double)mm);
+                const double a1 = m1 == -INFINITY ? s1 : s1 * exp((double)m1 - (double)mm);
+                run_s = a0 + a1;
+                run_m = mm;
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j)
+                    if (j < k) racc[j] += Rs[j * 64 + lane];
+            }
+            __syncthreads();
+        }
+        if (wave == 0 && live) {
+            const uint64_t r = r0 + lane;
+            if (g.lppd)
+                g.lppd[r] = (run_m == -INFINITY && run_s == 0.0) ? -INFINITY : (float)(((double)run_m + log(run_s)) - log((double)g.n));
+            if (g.resp) {
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j)
+                    if (j < k) g.resp[r * (uint64_t)k + j] = (float)(racc[j] / (double)g.n);
+            }
+        }
+    }
+}
+
+static inline bool gd_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+// the attribute is per function and per device (d3p_dpvi.hip's ensure_dynamic_lds, restated: that file's text is pinned)
+static int gd_dynamic_lds(const void* fn, const char* what)
+{
+    static std::mutex mu;
+    static std::vector<std::pair<const void*, int>> done;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    std::lock_guard<std::mutex> lock(mu);
+    for (const auto& e : done)
+        if (e.first == fn && e.second == dev) return D3P_OK;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)D3P_GD_LDS_MAX);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(D3P_E_HIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize, %d) on device %d: %s", what, (int)D3P_GD_LDS_MAX, dev, hipGetErrorString(e));
+    }
+    done.emplace_back(fn, dev);
+    return D3P_OK;
+}
+
+template <int KMAX, int REDUCE>
+static int gd_launch(const char* what, hipStream_t s, const GmmDensityArgs& g, int W, size_t lds)
+{
+    const void* fn = reinterpret_cast<const void*>(&k_gmm_density<KMAX, REDUCE>);
+    if (int rc = gd_dynamic_lds(fn, what)) return rc;
+    hipLaunchKernelGGL((k_gmm_density<KMAX, REDUCE>), dim3(cdiv(g.rows, D3P_GD_ROW_TILE)), dim3(64 * W), lds, s, g);
+    return check_launch(what);
+}
+
+template <int REDUCE>
+static int gd_entry(const char* what, void* stream, const float* obs, uint64_t rows, int32_t d, const float* latent, int64_t ld, int32_t k,
+                    uint32_t n, float* ll, float* lppd, float* resp)
+{
+    if (!obs || !latent) return fail(D3P_E_INVALID_ARG, "%s: null obs / latent pointer", what);
+    if (REDUCE ? (!lppd && !resp) : !ll)
+        return fail(D3P_E_INVALID_ARG, REDUCE ? "%s: at least one of the two outputs is required" : "%s: null output pointer", what);
+    if (!gd_aligned(obs) || !gd_aligned(latent) || !gd_aligned(ll) || !gd_aligned(lppd) || !gd_aligned(resp))
+        return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
+    if (k < 1 || d < 1) return fail(D3P_E_INVALID_ARG, "%s: k and d must be >= 1 (k = %d, d = %d)", what, k, d);
+    if (k > 32 || d > 256 || (k > 16 && d > 128))
+        return fail(D3P_E_UNSUPPORTED, "%s: supported shapes are k <= 16 with d <= 256 and k <= 32 with d <= 128 (k = %d, d = %d)", what, k, d);
+    if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
+    if (n > 0x7fffffffu) return fail(D3P_E_UNSUPPORTED, "%s: n <= 2^31 - 1", what);
+    if (ld < (int64_t)k + 2 * (int64_t)k * d) return fail(D3P_E_INVALID_ARG, "%s: a latent row holds k + 2 k d values", what);
+    if (rows > 0xFFFFFFFFull || rows * (uint64_t)d > 0xFFFFFFFFull) return fail(D3P_E_UNSUPPORTED, "%s: rows d < 2^32", what);
+    if (rows == 0) return D3P_OK;
+    if (!is_device_ptr(obs) || !is_device_ptr(latent) || (ll && !is_device_ptr(ll)) || (lppd && !is_device_ptr(lppd)) ||
+        (resp && !is_device_ptr(resp)))
+        return fail(D3P_E_INVALID_ARG, "%s: every pointer must be device memory", what);
+    GmmDensityArgs g;
+    g.obs = obs; g.lat = latent; g.ld = ld; g.rows = (uint32_t)rows; g.n = n; g.k = k; g.d = d; g.ll = ll; g.lppd = lppd; g.resp = resp;
+    // four waves split the draws where their four latent copies fit beside the row tile, otherwise two: a function of (k, d) alone
+    const size_t combine = REDUCE ? (size_t)64 * 8 * (k + 1) + 64 * 4 : 0;
+    int W = D3P_GD_DRAW_TILE;
+    size_t lds = sizeof(float) * ((size_t)gd_tile_floats(d) + (size_t)W * gd_wave_floats(k, d));
+    if (lds > D3P_GD_LDS_MAX) {
+        W = 2;
+        lds = sizeof(float) * ((size_t)gd_tile_floats(d) + (size_t)W * gd_wave_floats(k, d));
+    }
+    if (lds < combine) lds = combine;
+    if (lds > D3P_GD_LDS_MAX) return fail(D3P_E_UNSUPPORTED, "%s: %zu bytes of LDS needed (k = %d, d = %d)", what, lds, k, d);
+    hipStream_t s = (hipStream_t)stream;
+    if (k <= 4) return gd_launch<4, REDUCE>(what, s, g, W, lds);
+    if (k <= 16) return gd_launch<16, REDUCE>(what, s, g, W, lds);
+    return gd_launch<32, REDUCE>(what, s, g, W, lds);
+}
+
+}  // namespace d3p
+
+using namespace d3p;
+
+extern "C" {
+
+int d3p_gmm_loglik_rows(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld, int32_t k,
+                        uint32_t n, float* ll_out_dev)
+{
+    return gd_entry<0>("d3p_gmm_loglik_rows", stream, obs_dev, rows, d, latent_dev, latent_ld, k, n, ll_out_dev, nullptr, nullptr);
+}
+
+int d3p_gmm_loglik_reduce(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld, int32_t k,
+                          uint32_t n, float* lppd_out_dev, float* resp_out_dev)
+{
+    return gd_entry<1>("d3p_gmm_loglik_reduce", stream, obs_dev, rows, d, latent_dev, latent_ld, k, n, nullptr, lppd_out_dev, resp_out_dev);
+}
+
+}  // extern "C"

@@ -13,6 +13,10 @@ Two opt-in flags follow the reference where the defaults deviate from it (d3p_am
 the reference does, with the prior predictive and the three latent sites substituted (:87-108); --assignment posterior scores with
 the reference's compute_assignment_accuracy on the per-component log-posterior -- unit scales, the learned weights, the inverse mode
 map (:113-161) -- instead of the closest mode.
+
+--held-out-density (off by default; d3p_amd.mixture_density) adds two lines after training: the mean log predictive density of the
+test split under --posterior-draws draws from the fitted guide, and the accuracy of the argmax of the responsibilities averaged over
+the same draws, beside the assignment accuracy above.
 """
 import argparse
 import itertools
@@ -70,6 +74,24 @@ def assignment_accuracy(X_test, z_test, true_mus, modes):
             mapped[c] = j
         best = max(best, float((mapped[assign] == z_test).float().mean()))
     return best
+
+
+def held_out_density(X_test, z_test, params, k, num_draws, seed=4321):
+    """(mean log predictive density of X_test, accuracy of the argmax of the posterior-averaged responsibilities under the best map
+    of learned components to true ones) under num_draws draws from the guide at params -- one pass over the draws."""
+    from d3p_amd import mixture_density
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    out = mixture_density.posterior_summary(threefry.PRNGKey(seed), num_draws, model, (k, X_test), GaussianMixtureGuide(model), params)
+    soft = out["responsibilities"].argmax(dim=1)
+    n_true = int(z_test.max()) + 1
+    best = 0.0
+    for perm in itertools.permutations(range(k), n_true):
+        mapped = torch.full((k,), -1, device=soft.device, dtype=torch.long)
+        for j, c in enumerate(perm):
+            mapped[c] = j
+        best = max(best, float((mapped[soft] == z_test).float().mean()))
+    return float(out["log_predictive_density"].mean()), best
 
 
 def main(args):
@@ -132,6 +154,11 @@ def main(args):
     else:
         acc = assignment_accuracy(X_test, z_test, true_mus, modes)
     print("assignment accuracy: {:.4f}".format(acc))
+    if getattr(args, "held_out_density", False):
+        lppd, soft_acc = held_out_density(X_test, z_test, params, k, args.posterior_draws)
+        print("held-out log predictive density (mean over {} points, {} posterior draws): {:.4f}".format(
+            X_test.shape[0], args.posterior_draws, lppd))
+        print("assignment accuracy (argmax of posterior responsibilities): {:.4f}".format(soft_acc))
     return acc, pis, modes
 
 
@@ -149,6 +176,9 @@ def parse_args(argv=None):
                         help="'predictive': make the data with the prior predictive, as the reference does")
     parser.add_argument('--assignment', default='modes', choices=['modes', 'posterior'],
                         help="'posterior': score with the per-component log-posterior, as the reference does")
+    parser.add_argument('--held-out-density', action='store_true',
+                        help='report the held-out log predictive density and the soft-assignment accuracy under the fitted posterior')
+    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --held-out-density')
     return parser.parse_args(argv)
 
 

@@ -845,6 +845,23 @@ int d3p_predict_gmm_obs(void* stream, const float* latent_dev, int64_t latent_ld
 int d3p_gmm_assign(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* mus_dev, const float* sigs_dev,
                    const float* pis_dev, int32_t k, float* a_out_dev, int32_t* argmax_out_dev);
 
+/* Held-out log predictive density and responsibilities of the Gaussian mixture model over n posterior draws
+ * (d3p_amd/mixture_density.py, d3p_gmm_density.hip); added symbols, ABI 9 unchanged.  latent_dev holds n rows
+ * [pis (k) | mus (k d) | sigs (k d)] at a leading dimension latent_ld >= k + 2 k d, as d3p_predict_gmm_draws writes them.  With
+ *   a[s, r, j] = log pis[s, j] + sum_c log N(obs[r, c]; mus[s, j, c], sigs[s, j, c])            (direct form, float32)
+ * d3p_gmm_loglik_rows     ll_out_dev[s, r] = logsumexp_j a[s, r, j]                                               n x rows float32
+ * d3p_gmm_loglik_reduce   lppd_out_dev[r] = logsumexp_s ll[s, r] - log n (rows float32, nullable) and resp_out_dev[r, j] = (1 / n)
+ *   sum_s exp(a[s, r, j] - ll[s, r]) (rows x k float32, nullable); at least one of the two.  Neither a nor ll reaches memory; obs is
+ *   read once; the sums over the draws run in float64 in a fixed order (no atomics, bit-identical between calls).
+ * pis[s, j] == 0: the component adds nothing; every component of a draw -inf: ll = -inf (not NaN) and that draw contributes NaN to the
+ * row's resp; every draw -inf: lppd = -inf.  A NaN in a row of obs or in a draw's latents makes that row's / that draw's outputs NaN.
+ * Limits and errors are d3p_gmm_assign's (k <= 16 with d <= 256 or k <= 32 with d <= 128; rows d < 2^32: D3P_E_UNSUPPORTED), plus
+ * 1 <= n <= 2^31 - 1 and latent_ld >= k + 2 k d; every refusal comes before any launch; rows == 0: D3P_OK, no launch. */
+int d3p_gmm_loglik_rows(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
+                        int32_t k, uint32_t n, float* ll_out_dev);
+int d3p_gmm_loglik_reduce(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
+                          int32_t k, uint32_t n, float* lppd_out_dev, float* resp_out_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

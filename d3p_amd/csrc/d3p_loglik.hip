@@ -4,11 +4,8 @@
 //   lppd form   out[r]    = logsumexp_s ll[s, r] - log n                                                       (rows)
 // UNSCALED log-probabilities: no plate factor, no 1 / observation_scale (numpyro's log_likelihood returns fn.log_prob(value)).
 //
-// The product is the tile of k_predict_logreg (d3p_predict.hip): 128 draws x 128 rows per workgroup, 4 wavefronts (2 x 2: wm = draw
-// half, wn = row half) of 64 x 64, K in slices of 32 staged through LDS, v_mfma_f32_32x32x2_f32 (exact float32 products), D[i][j]
-// with j = l % 32, i = 8 (v / 4) + 4 (l / 32) + v % 4, A = the draws' weights (i = draw), B = X^T (j = row).  It is a SECOND COPY of
-// that loop: moved into a function shared by both kernels, k_predict_logreg's generated code changed (register allocation and
-// instruction order), so the predictive kernel keeps its own text.
+// The product is the shared tile (d3p_glm_tile.h): 128 draws x 128 rows per workgroup, 4 wavefronts (2 x 2: wm = draw half, wn = row
+// half) of 64 x 64.
 //
 // Epilogue, per half of a wave's 64 draws as in the predictive kernel: the accumulators go through LDS so that lane l owns row l
 // and walks 32 draws; a rows-form store is 64 consecutive floats.  The lppd form's grid runs over row tiles only: a workgroup walks
@@ -19,15 +16,10 @@
 // never NaN; a NaN stays a NaN.  The two wm waves that share a row block are combined once at the end, wm = 0 then wm = 1, by the
 // wm = 0 wave: deterministic, no atomics, no n x rows intermediate.
 #include "d3p_device.h"
+#include "d3p_glm_tile.h"
 #include "d3p_host.h"
 
 namespace d3p {
-
-#define D3P_LL_TM 128
-#define D3P_LL_TN 128
-#define D3P_LL_TK 32
-#define D3P_LL_LD (D3P_LL_TN + 4)
-typedef float loglik_f16v __attribute__((ext_vector_type(16)));
 
 struct LoglikArgs {
     const float* X;
@@ -70,13 +62,10 @@ template <int FAMILY, int LPPD>
 __global__ void __launch_bounds__(256, LPPD ? 1 : 2) k_loglik(LoglikArgs g)
 {
     // [k][draw] | [k][row] during the product; afterwards the same bytes hold each wave's t, half a tile at a time (4 x 32 x 65 floats)
-    __shared__ __attribute__((aligned(16))) float smem[2 * D3P_LL_TK * D3P_LL_LD];
-    float (*As)[D3P_LL_LD] = reinterpret_cast<float (*)[D3P_LL_LD]>(smem);
-    float (*Bs)[D3P_LL_LD] = reinterpret_cast<float (*)[D3P_LL_LD]>(smem + D3P_LL_TK * D3P_LL_LD);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ __attribute__((aligned(16))) float smem[D3P_TILE_SMEM];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_LL_TN;
-    const int d = g.d;
+    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_TILE_N;
     // lane l owns row r in the epilogue: its label and the label's constant, once per row
     const uint64_t r = r0 + wn * 64 + lane;
     const bool live = r < g.rows;
@@ -84,56 +73,14 @@ __global__ void __launch_bounds__(256, LPPD ? 1 : 2) k_loglik(LoglikArgs g)
     const float c = FAMILY == D3P_FAMILY_POISSON ? lgammaf(y + 1.0f) : g.ll_const;
     float run_m = -INFINITY;
     double run_s = 0.0;
-    uint32_t s0 = LPPD ? 0u : blockIdx.y * D3P_LL_TM;   // rows form: the grid's y runs over the draw tiles; lppd form: the loop does
+    uint32_t s0 = LPPD ? 0u : blockIdx.y * D3P_TILE_M;   // rows form: the grid's y runs over the draw tiles; lppd form: the loop does
     do {
-        loglik_f16v acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-        // staging: element e = tid + 256 q of a slice -> (tile row e / 32, k e % 32): 32 consecutive threads read 128 contiguous bytes
-        float ra[16], rb[16];
-        auto fetch = [&](int kc) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int e = tid + 256 * q, row = e >> 5, k = kc + (e & 31);
-                const uint32_t s = s0 + row;
-                const uint64_t rr = r0 + row;
-                ra[q] = (s < g.n && k < d) ? g.lat[(size_t)s * g.ld + g.w_off + k] : 0.f;
-                rb[q] = (rr < g.rows && k < d) ? g.X[rr * (uint64_t)d + k] : 0.f;
-            }
-        };
-        fetch(0);
-        for (int kc = 0; kc < d; kc += D3P_LL_TK) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int e = tid + 256 * q;
-                As[e & 31][e >> 5] = ra[q];
-                Bs[e & 31][e >> 5] = rb[q];
-            }
-            __syncthreads();
-            if (kc + D3P_LL_TK < d) fetch(kc + D3P_LL_TK);   // next slice in flight while this one multiplies
-#pragma unroll
-            for (int kk = 0; kk < D3P_LL_TK; kk += 2) {
-                const int k = kk + (lane >> 5), cc = lane & 31;
-                const float a0 = As[k][wm * 64 + cc], a1 = As[k][wm * 64 + 32 + cc];
-                const float b0 = Bs[k][wn * 64 + cc], b1 = Bs[k][wn * 64 + 32 + cc];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-        float* L = smem + wave * (32 * 65);   // [draw 0..31][row 0..63], rows padded to 65 floats
+        tile_f16v acc[2][2];
+        tile_product(smem, g, r0, s0, acc);
+        float* L = tile_block(smem);
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) L[(8 * (v >> 2) + 4 * (lane >> 5) + (v & 3)) * 65 + nb * 32 + (lane & 31)] = acc[mb][nb][v];
+            tile_scatter(L, acc[mb][0], acc[mb][1]);
             __syncthreads();
             if (live) {
                 for (int i = 0; i < 32; ++i) {
@@ -154,12 +101,12 @@ __global__ void __launch_bounds__(256, LPPD ? 1 : 2) k_loglik(LoglikArgs g)
             }
             __syncthreads();
         }
-        s0 += D3P_LL_TM;
+        s0 += D3P_TILE_M;
     } while (LPPD && s0 < g.n);
     if (LPPD) {
         // the two waves of a row block: wm = 1 hands its (max, sum) over, wm = 0 merges (its own first) and finishes in float64
         double* Ss = reinterpret_cast<double*>(smem);   // [128] sums, then [128] maxima behind them
-        float* Ms = smem + 2 * D3P_LL_TN;
+        float* Ms = smem + 2 * D3P_TILE_N;
         if (wm == 1) { Ss[wn * 64 + lane] = run_s; Ms[wn * 64 + lane] = run_m; }
         __syncthreads();
         if (wm == 0 && live) {
@@ -180,26 +127,16 @@ static int loglik_entry(const char* what, void* stream, const d3p_logreg_model* 
                         int64_t ld, int32_t w_off, int32_t b_col, uint32_t n, float* out)
 {
     if (int rc = validate_model(m, y, what)) return rc;   // D3P_GUIDE_EXP_SITES: D3P_E_UNSUPPORTED (neither form reads the guide transform otherwise)
-    if (m->family == D3P_FAMILY_GAUSS_MEAN)
-        return fail(D3P_E_UNSUPPORTED, "%s: the Gaussian-mean family has no per-row linear predictor (logistic, linear and Poisson regression only)", what);
-    if (!X || !y || !latent || !out) return fail(D3P_E_INVALID_ARG, "%s: null X / y / latent / out pointer", what);
-    if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
-    const int d = m->d;
-    if (!(w_off >= 0 && (int64_t)w_off + d <= ld && b_col < ld && b_col >= -1 && !(b_col >= w_off && b_col < w_off + d)))
-        return fail(D3P_E_INVALID_ARG, "%s: the weights [w_off, w_off + d) and the intercept column must lie in a latent row, apart", what);
-    if ((m->intercept != 0) != (b_col >= 0)) return fail(D3P_E_INVALID_ARG, "%s: b_col must be given exactly when the model has an intercept", what);
-    if (rows > 0xFFFFFFFFull || cdiv(rows, D3P_LL_TN) > 0x7fffffffu || cdiv(n, D3P_LL_TM) > 65535u)
-        return fail(D3P_E_INVALID_ARG, "%s: rows <= 2^32 - 1 and n <= 128 x 65535", what);
-    if (rows == 0) return D3P_OK;
-    if (!is_device_ptr(X) || !is_device_ptr(y) || !is_device_ptr(latent) || !is_device_ptr(out))
-        return fail(D3P_E_INVALID_ARG, "%s: X, y, latent and out must be device memory", what);
+    bool launch;
+    if (int rc = glm_tile_check(what, m, rows, ld, w_off, b_col, n, {X, y, latent, out}, "X / y / latent / out", "X, y, latent and out", &launch); rc || !launch)
+        return rc;
     LoglikArgs g;
-    g.X = X; g.y = y; g.rows = rows; g.d = d; g.w_off = w_off; g.b_col = b_col; g.lat = latent; g.ld = ld; g.n = n; g.out = out;
+    g.X = X; g.y = y; g.rows = rows; g.d = m->d; g.w_off = w_off; g.b_col = b_col; g.lat = latent; g.ld = ld; g.n = n; g.out = out;
     // as the training kernels' arguments (d3p_dpvi.hip: nh_inv_var, ll_const)
     const bool sigma = m->family == D3P_FAMILY_LINREG;
     g.nh = sigma ? -0.5f / (m->lik_sigma * m->lik_sigma) : 0.f;
     g.ll_const = sigma ? logf(m->lik_sigma) + 0.91893853320467267f : 0.f;
-    const dim3 grid(cdiv(rows, D3P_LL_TN), LPPD ? 1u : cdiv(n, D3P_LL_TM));
+    const dim3 grid(cdiv(rows, D3P_TILE_N), LPPD ? 1u : cdiv(n, D3P_TILE_M));
     hipStream_t s = (hipStream_t)stream;
     if (m->family == D3P_FAMILY_LINREG) hipLaunchKernelGGL((k_loglik<D3P_FAMILY_LINREG, LPPD>), grid, dim3(256), 0, s, g);
     else if (m->family == D3P_FAMILY_POISSON) hipLaunchKernelGGL((k_loglik<D3P_FAMILY_POISSON, LPPD>), grid, dim3(256), 0, s, g);

@@ -6,11 +6,9 @@
 //   mean[r]  = (1/n) sum_s mu[s, r]
 //   var[r]   = (1/n) sum_s v[s, r] + (1/n) sum_s (mu[s, r] - mean[r])^2      (law of total variance, population form)
 //
-// The product is the tile of k_loglik's lppd form (d3p_loglik.hip): 128 draws x 128 rows per workgroup, 4 wavefronts (2 x 2: wm =
-// draw half, wn = row half) of 64 x 64, K in slices of 32 staged through LDS, v_mfma_f32_32x32x2_f32 (exact float32 products), the
-// grid over row tiles only, the workgroup walking the draw tiles; the accumulators go through LDS so that lane l owns row l and
-// walks 32 draws.  It is a THIRD COPY of that loop, on purpose: sharing it changed k_predict_logreg's generated code (DESIGN.md
-// sections 4c, 4d); unifying the three is a refactor of its own with its own measurements.
+// The product is the shared tile (d3p_glm_tile.h): 128 draws x 128 rows per workgroup, 4 wavefronts (2 x 2: wm = draw half, wn = row
+// half) of 64 x 64; as in k_loglik's lppd form (d3p_loglik.hip) the grid runs over row tiles only and the workgroup walks the draw
+// tiles; the accumulators go through LDS so that lane l owns row l and walks 32 draws.
 //
 // Epilogue in float32, no clamps (exp(t) = inf stays inf); accumulation per lane and row, in draw order, in float64:
 //   logistic          sum p and sum q, p = sigmoid(t) and q = sigmoid(-t) both formed from ONE e = exp(-|t|) (the smaller is
@@ -24,15 +22,10 @@
 // Non-finite values: a NaN t makes the row's mean and variance NaN.  An infinite mu is not added to the sums (inf - inf) but
 // remembered: a row with a +inf mu gives (+inf, +inf) (linear, t = -inf: (-inf, +inf); both signs: NaN, as the mean is).
 #include "d3p_device.h"
+#include "d3p_glm_tile.h"
 #include "d3p_host.h"
 
 namespace d3p {
-
-#define D3P_MO_TM 128
-#define D3P_MO_TN 128
-#define D3P_MO_TK 32
-#define D3P_MO_LD (D3P_MO_TN + 4)
-typedef float moments_f16v __attribute__((ext_vector_type(16)));
 
 struct MomentsArgs {
     const float* X;
@@ -60,67 +53,22 @@ template <int FAMILY>
 __global__ void __launch_bounds__(256, 1) k_moments(MomentsArgs g)
 {
     // [k][draw] | [k][row] during the product; afterwards the same bytes hold each wave's t, half a tile at a time (4 x 32 x 65 floats)
-    __shared__ __attribute__((aligned(16))) float smem[2 * D3P_MO_TK * D3P_MO_LD];
-    float (*As)[D3P_MO_LD] = reinterpret_cast<float (*)[D3P_MO_LD]>(smem);
-    float (*Bs)[D3P_MO_LD] = reinterpret_cast<float (*)[D3P_MO_LD]>(smem + D3P_MO_TK * D3P_MO_LD);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ __attribute__((aligned(16))) float smem[D3P_TILE_SMEM];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_MO_TN;
-    const int d = g.d;
+    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_TILE_N;
     const uint64_t r = r0 + wn * 64 + lane;   // lane l owns row r in the epilogue
     const bool live = r < g.rows;
     double a0 = 0.0, a1 = 0.0;   // LOGREG: sum p, sum q; else: sum (mu - c), sum (mu - c)^2
     float c = 0.f;               // the shift: this wave's first finite mu of the row
     uint32_t cnt = 0, inf_seen = 0;   // values in the sums; bit 0: a +inf mu came by, bit 1: a -inf one
-    for (uint32_t s0 = 0; s0 < g.n; s0 += D3P_MO_TM) {
-        moments_f16v acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-        // staging: element e = tid + 256 q of a slice -> (tile row e / 32, k e % 32): 32 consecutive threads read 128 contiguous bytes
-        float ra[16], rb[16];
-        auto fetch = [&](int kc) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int e = tid + 256 * q, row = e >> 5, k = kc + (e & 31);
-                const uint32_t s = s0 + row;
-                const uint64_t rr = r0 + row;
-                ra[q] = (s < g.n && k < d) ? g.lat[(size_t)s * g.ld + g.w_off + k] : 0.f;
-                rb[q] = (rr < g.rows && k < d) ? g.X[rr * (uint64_t)d + k] : 0.f;
-            }
-        };
-        fetch(0);
-        for (int kc = 0; kc < d; kc += D3P_MO_TK) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int e = tid + 256 * q;
-                As[e & 31][e >> 5] = ra[q];
-                Bs[e & 31][e >> 5] = rb[q];
-            }
-            __syncthreads();
-            if (kc + D3P_MO_TK < d) fetch(kc + D3P_MO_TK);   // next slice in flight while this one multiplies
-#pragma unroll
-            for (int kk = 0; kk < D3P_MO_TK; kk += 2) {
-                const int k = kk + (lane >> 5), cc = lane & 31;
-                const float x0 = As[k][wm * 64 + cc], x1 = As[k][wm * 64 + 32 + cc];
-                const float y0 = Bs[k][wn * 64 + cc], y1 = Bs[k][wn * 64 + 32 + cc];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, y0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, y1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, y0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, y1, acc[1][1], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-        float* L = smem + wave * (32 * 65);   // [draw 0..31][row 0..63], rows padded to 65 floats
+    for (uint32_t s0 = 0; s0 < g.n; s0 += D3P_TILE_M) {
+        tile_f16v acc[2][2];
+        tile_product(smem, g, r0, s0, acc);
+        float* L = tile_block(smem);
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) L[(8 * (v >> 2) + 4 * (lane >> 5) + (v & 3)) * 65 + nb * 32 + (lane & 31)] = acc[mb][nb][v];
+            tile_scatter(L, acc[mb][0], acc[mb][1]);
             __syncthreads();
             if (live) {
 #pragma clang fp contract(off)
@@ -154,14 +102,14 @@ __global__ void __launch_bounds__(256, 1) k_moments(MomentsArgs g)
     }
     // the two waves of a row block: wm = 1 hands its sums over, wm = 0 merges (its own first) and finishes in float64
     double* S = reinterpret_cast<double*>(smem);   // [2][128] sums, then [128] shifts, counts and flags behind them
-    float* Cs = smem + 4 * D3P_MO_TN;
-    uint32_t* Ks = reinterpret_cast<uint32_t*>(smem + 5 * D3P_MO_TN);
-    uint32_t* Fs = reinterpret_cast<uint32_t*>(smem + 6 * D3P_MO_TN);
+    float* Cs = smem + 4 * D3P_TILE_N;
+    uint32_t* Ks = reinterpret_cast<uint32_t*>(smem + 5 * D3P_TILE_N);
+    uint32_t* Fs = reinterpret_cast<uint32_t*>(smem + 6 * D3P_TILE_N);
     const int slot = wn * 64 + lane;
-    if (wm == 1) { S[slot] = a0; S[D3P_MO_TN + slot] = a1; Cs[slot] = c; Ks[slot] = cnt; Fs[slot] = inf_seen; }
+    if (wm == 1) { S[slot] = a0; S[D3P_TILE_N + slot] = a1; Cs[slot] = c; Ks[slot] = cnt; Fs[slot] = inf_seen; }
     __syncthreads();
     if (wm == 0 && live) {
-        const double b0 = S[slot], b1 = S[D3P_MO_TN + slot];
+        const double b0 = S[slot], b1 = S[D3P_TILE_N + slot];
         const double nd = (double)g.n;
         double mean, var;
         if (FAMILY == D3P_FAMILY_LOGREG) {
@@ -205,24 +153,15 @@ int d3p_predict_moments(void* stream, const d3p_logreg_model* model, const float
     const d3p_logreg_model* m = model;
     // (there are no labels: validate_model's label check gets a pointer that is not null)
     if (int rc = validate_model(m, m, what)) return rc;   // D3P_GUIDE_EXP_SITES: D3P_E_UNSUPPORTED (the guide transform is not read otherwise)
-    if (m->family == D3P_FAMILY_GAUSS_MEAN)
-        return fail(D3P_E_UNSUPPORTED, "%s: the Gaussian-mean family has no per-row linear predictor (logistic, linear and Poisson regression only)", what);
-    if (!X_dev || !latent_dev || !mean_rows_dev || !var_rows_dev) return fail(D3P_E_INVALID_ARG, "%s: null X / latent / mean / var pointer", what);
-    if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
-    const int d = m->d;
-    if (!(w_off >= 0 && (int64_t)w_off + d <= latent_ld && b_col < latent_ld && b_col >= -1 && !(b_col >= w_off && b_col < w_off + d)))
-        return fail(D3P_E_INVALID_ARG, "%s: the weights [w_off, w_off + d) and the intercept column must lie in a latent row, apart", what);
-    if ((m->intercept != 0) != (b_col >= 0)) return fail(D3P_E_INVALID_ARG, "%s: b_col must be given exactly when the model has an intercept", what);
-    if (rows > 0xFFFFFFFFull || cdiv(rows, D3P_MO_TN) > 0x7fffffffu || cdiv(n, D3P_MO_TM) > 65535u)
-        return fail(D3P_E_INVALID_ARG, "%s: rows <= 2^32 - 1 and n <= 128 x 65535", what);
-    if (rows == 0) return D3P_OK;
-    if (!is_device_ptr(X_dev) || !is_device_ptr(latent_dev) || !is_device_ptr(mean_rows_dev) || !is_device_ptr(var_rows_dev))
-        return fail(D3P_E_INVALID_ARG, "%s: X, latent, mean and var must be device memory", what);
+    bool launch;
+    if (int rc = glm_tile_check(what, m, rows, latent_ld, w_off, b_col, n, {X_dev, latent_dev, mean_rows_dev, var_rows_dev}, "X / latent / mean / var",
+                                "X, latent, mean and var", &launch); rc || !launch)
+        return rc;
     MomentsArgs g;
-    g.X = X_dev; g.rows = rows; g.d = d; g.w_off = w_off; g.b_col = b_col; g.lat = latent_dev; g.ld = latent_ld; g.n = n;
+    g.X = X_dev; g.rows = rows; g.d = m->d; g.w_off = w_off; g.b_col = b_col; g.lat = latent_dev; g.ld = latent_ld; g.n = n;
     g.sigma = m->family == D3P_FAMILY_LINREG ? m->lik_sigma : 0.f;
     g.mean = mean_rows_dev; g.var = var_rows_dev;
-    const dim3 grid(cdiv(rows, D3P_MO_TN));
+    const dim3 grid(cdiv(rows, D3P_TILE_N));
     hipStream_t s = (hipStream_t)stream;
     if (m->family == D3P_FAMILY_LINREG) hipLaunchKernelGGL((k_moments<D3P_FAMILY_LINREG>), grid, dim3(256), 0, s, g);
     else if (m->family == D3P_FAMILY_POISSON) hipLaunchKernelGGL((k_moments<D3P_FAMILY_POISSON>), grid, dim3(256), 0, s, g);

@@ -7,12 +7,13 @@
 //   draw_key            modelling._sample_a_lot: keys = jax.random.split(rng_key, n), draw i = single-draw function of keys[i]
 //   draw_chains         modelling.sample_posterior_predictive: model_key, guide_key = jax.random.split(key)
 //   seed_site_key       numpyro.handlers.seed: `rng, site_key = split(rng)` at every sample statement that takes a key
-//   normal_site_value   numpyro.distributions.Normal.sample: loc + random.normal(key, shape) * scale
+//   normal_site_value   numpyro.distributions.Normal.sample: loc + random.normal(key, shape) * scale   (d3p_glm_tile.h: shared with d3p_predict_glm.hip)
 //   bernoulli_draw      numpyro.distributions.Bernoulli(Logits / Probs).sample: random.uniform(key, shape) < probs
 //   sigmoid_probs       BernoulliLogits.probs = jax.scipy.special.expit(logits)
 // Which sites take a key (substituted / observed sites and a plate whose size equals its subsample size take none) is decided on
 // the host (d3p_amd/modelling.py: site_plan) and arrives here as key indices.
 #include "d3p_device.h"
+#include "d3p_glm_tile.h"
 #include "d3p_host.h"
 
 namespace d3p {
@@ -53,16 +54,6 @@ __device__ __forceinline__ void seed_site_key(const uint32_t (&chain)[2], int in
         split2(c0, c1, n0, n1, s0, s1);
         c0 = n0; c1 = n1;
     }
-}
-
-// numpyro Normal.sample: loc + random.normal(key, shape) * scale -- a product, then a sum (two roundings, no fused multiply-add).
-// The pragma is what keeps them apart: hipcc contracts across inlined code by default, and HIP's __fadd_rn / __fmul_rn are plain
-// `+` / `*` there, so without it the product and the sum became one v_fma_f32 (tests/test_gpu_predictive_edges.py checks the two
-// roundings bit for bit)
-__device__ __forceinline__ float normal_site_value(float loc, float eps, float scale)
-{
-#pragma clang fp contract(off)
-    return loc + eps * scale;
 }
 
 // BernoulliLogits.probs = expit(logits) = 1 / (1 + exp(-logits))
@@ -128,19 +119,9 @@ __global__ void __launch_bounds__(256) k_predict_draws(DrawsArgs a)
 }
 
 // ---- logistic regression: obs[s, r] = bernoulli(uniform(obs_key_s, rows)[r] < sigmoid(X[r] . w_s + b_s)) ----------------------
-// Workgroup tile: 128 draws x 128 rows, 4 wavefronts (2 x 2) of 64 x 64, K in slices of 32 staged through LDS (X and the draws'
-// weights, both transposed to [k][.] so that a fragment read is 32 consecutive floats).  Product on the matrix cores:
-// v_mfma_f32_32x32x2_f32, exact float32 products, lane l: A row / B column l % 32, k = l / 32; D[i][j] with j = l % 32,
-// i = 8 (v / 4) + 4 (l / 32) + v % 4.  A = the draws' weights (i = draw), B = X^T (j = row): the 32 lanes of a half-wave hold 32
-// consecutive rows, so the int32 outcomes leave in 128-byte segments.  X is read once per tile of 128 draws; the weights of a
-// tile (128 x d) are re-read per row tile from L2 in K slices (at d = 512 they would be 256 KB of LDS).  The uniforms come from
-// tf_iota_word (one threefry call per outcome, its second word discarded) in the epilogue.
-#define D3P_PL_TM 128
-#define D3P_PL_TN 128
-#define D3P_PL_TK 32
-#define D3P_PL_LD (D3P_PL_TN + 4)
-typedef float predict_f16v __attribute__((ext_vector_type(16)));
-
+// The product is the shared tile (d3p_glm_tile.h): 128 draws x 128 rows per workgroup, 4 wavefronts (2 x 2) of 64 x 64; lane l of a
+// half-wave holds row l, so the int32 outcomes leave in 128-byte segments.  The uniforms come from tf_iota_word (one threefry call
+// per outcome, its second word discarded) in the epilogue.
 struct LogregPredictArgs {
     const float* X;
     uint64_t rows;
@@ -155,66 +136,21 @@ struct LogregPredictArgs {
 __global__ void __launch_bounds__(256) k_predict_logreg(LogregPredictArgs g)
 {
     // [k][draw] | [k][row] during the product; afterwards the same bytes hold each wave's logits, half a tile at a time
-    __shared__ float smem[2 * D3P_PL_TK * D3P_PL_LD];
-    float (*As)[D3P_PL_LD] = reinterpret_cast<float (*)[D3P_PL_LD]>(smem);
-    float (*Bs)[D3P_PL_LD] = reinterpret_cast<float (*)[D3P_PL_LD]>(smem + D3P_PL_TK * D3P_PL_LD);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float smem[D3P_TILE_SMEM];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_PL_TN;
-    const uint32_t s0 = blockIdx.y * D3P_PL_TM;
-    const int d = g.d;
-    predict_f16v acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-    // staging: element e = tid + 256 q of a slice -> (tile row e / 32, k e % 32): 32 consecutive threads read 128 contiguous bytes
-    float ra[16], rb[16];
-    auto fetch = [&](int kc) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q, row = e >> 5, k = kc + (e & 31);
-            const uint32_t s = s0 + row;
-            const uint64_t r = r0 + row;
-            ra[q] = (s < g.n && k < d) ? g.lat[(size_t)s * g.ld + g.w_off + k] : 0.f;
-            rb[q] = (r < g.rows && k < d) ? g.X[r * (uint64_t)d + k] : 0.f;
-        }
-    };
-    fetch(0);
-    for (int kc = 0; kc < d; kc += D3P_PL_TK) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q;
-            As[e & 31][e >> 5] = ra[q];
-            Bs[e & 31][e >> 5] = rb[q];
-        }
-        __syncthreads();
-        if (kc + D3P_PL_TK < d) fetch(kc + D3P_PL_TK);   // next slice in flight while this one multiplies
-#pragma unroll
-        for (int kk = 0; kk < D3P_PL_TK; kk += 2) {
-            const int k = kk + (lane >> 5), c = lane & 31;
-            const float a0 = As[k][wm * 64 + c], a1 = As[k][wm * 64 + 32 + c];
-            const float b0 = Bs[k][wn * 64 + c], b1 = Bs[k][wn * 64 + 32 + c];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_TILE_N;
+    const uint32_t s0 = blockIdx.y * D3P_TILE_M;
+    tile_f16v acc[2][2];
+    tile_product(smem, g, r0, s0, acc);
     // Epilogue, per half of the wave's 64 draws: the accumulators go to LDS ([draw 0..31][row 0..63], rows padded to 65 floats), then
     // lane l owns row l and walks the 32 draws -- one threefry call per outcome, 64 consecutive int32 per store.  (Done straight from
     // the accumulator registers, 64 inlined threefry calls per lane make the compiler give up unrolling and index them in scratch.)
-    float* L = smem + wave * (32 * 65);
+    float* L = tile_block(smem);
     const uint64_t r = r0 + wn * 64 + lane;
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) L[(8 * (v >> 2) + 4 * (lane >> 5) + (v & 3)) * 65 + nb * 32 + (lane & 31)] = acc[mb][nb][v];
+        tile_scatter(L, acc[mb][0], acc[mb][1]);
         __syncthreads();
         if (r < g.rows) {
             for (int i = 0; i < 32; ++i) {
@@ -364,7 +300,7 @@ int d3p_predict_logreg(void* stream, const float* X_dev, uint64_t rows, int32_t 
     D3P_REQUIRE(d >= 1 && n >= 1, "d3p_predict_logreg: d >= 1 and n >= 1 required");
     D3P_REQUIRE(w_off >= 0 && (int64_t)w_off + d <= latent_ld && b_col < latent_ld && b_col >= -1 && !(b_col >= w_off && b_col < w_off + d),
                 "d3p_predict_logreg: the weights [w_off, w_off + d) and the intercept column must lie in a latent row, apart");
-    D3P_REQUIRE(cdiv(rows, D3P_PL_TN) <= 0x7fffffffu && cdiv(n, D3P_PL_TM) <= 65535u, "d3p_predict_logreg: grid too large");
+    D3P_REQUIRE(cdiv(rows, D3P_TILE_N) <= 0x7fffffffu && cdiv(n, D3P_TILE_M) <= 65535u, "d3p_predict_logreg: grid too large");
     D3P_REQUIRE_DEV(X_dev, "d3p_predict_logreg: X_dev must be device memory");
     D3P_REQUIRE_DEV(latent_dev, "d3p_predict_logreg: latent_dev must be device memory");
     D3P_REQUIRE_DEV(obs_keys_dev, "d3p_predict_logreg: obs_keys_dev must be device memory");
@@ -372,7 +308,7 @@ int d3p_predict_logreg(void* stream, const float* X_dev, uint64_t rows, int32_t 
     LogregPredictArgs g;
     g.X = X_dev; g.rows = rows; g.d = d; g.w_off = w_off; g.b_col = b_col; g.lat = latent_dev; g.ld = latent_ld; g.n = n;
     g.obs_keys = obs_keys_dev; g.obs = obs_dev;
-    hipLaunchKernelGGL(k_predict_logreg, dim3(cdiv(rows, D3P_PL_TN), cdiv(n, D3P_PL_TM)), dim3(256), 0, (hipStream_t)stream, g);
+    hipLaunchKernelGGL(k_predict_logreg, dim3(cdiv(rows, D3P_TILE_N), cdiv(n, D3P_TILE_M)), dim3(256), 0, (hipStream_t)stream, g);
     return check_launch("d3p_predict_logreg");
 }
 

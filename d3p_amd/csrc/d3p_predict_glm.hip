@@ -4,11 +4,9 @@
 //   linear    obs[s, r] = fl(t + fl(eps sigma)), eps = normal(obs_key_s, (rows,))[r]    float32   (numpyro Normal.sample)
 //   Poisson   obs[s, r] = poisson_draw(exp(t), the uniforms of obs_key_s)               int32     (the project's own rule, below)
 //
-// The product is k_predict_logreg's tile (d3p_predict.hip): 128 draws x 128 rows per workgroup, 4 wavefronts (2 x 2) of 64 x 64, K in
-// slices of 32 staged through LDS, v_mfma_f32_32x32x2_f32 (exact float32 products), the grid over (row tiles, draw tiles); the
-// accumulators go through LDS so that lane l owns row l and walks 32 draws: a store is 64 consecutive words.  It is a FOURTH COPY of
-// that loop, on purpose, as the third was (d3p_moments.hip): sharing it changed k_predict_logreg's generated code (DESIGN.md sections
-// 4c, 4d, 4e); unifying the four is a refactor of its own with its own measurements.
+// The product is the shared tile (d3p_glm_tile.h): 128 draws x 128 rows per workgroup, 4 wavefronts (2 x 2) of 64 x 64, the grid over
+// (row tiles, draw tiles); the accumulators go through LDS so that lane l owns row l and walks 32 draws: a store is 64 consecutive
+// words.
 //
 // The Poisson rule (UNPINNED and the project's own -- jax.random.poisson draws with whole-array while_loops
 // whose text is not available to this build, so no bit parity with it is claimed; the position d3po_gamma_sample takes for
@@ -25,15 +23,10 @@
 // Every loop has a fixed cap.  fold_in(obs_key_s, j) is the same for every row of a draw: iteration 0's key, the only one every
 // outcome needs, is derived once per draw and workgroup into LDS; a later iteration (0.13 to 0.33 per outcome) derives its own.
 #include "d3p_device.h"
+#include "d3p_glm_tile.h"
 #include "d3p_host.h"
 
 namespace d3p {
-
-#define D3P_PG_TM 128
-#define D3P_PG_TN 128
-#define D3P_PG_TK 32
-#define D3P_PG_LD (D3P_PG_TN + 4)
-typedef float predict_glm_f16v __attribute__((ext_vector_type(16)));
 
 struct GlmPredictArgs {
     const float* X;
@@ -46,14 +39,6 @@ struct GlmPredictArgs {
     const uint32_t* obs_keys;
     void* obs;     // LINREG: float32, POISSON: int32; n x rows
 };
-
-// numpyro Normal.sample: loc + random.normal(key, shape) * scale -- a product, then a sum (two roundings); normal_site_value's rule
-// (d3p_predict.hip), restated here because that file's text is pinned.  The pragma keeps hipcc from contracting them into one fma.
-__device__ __forceinline__ float glm_normal_value(float loc, float eps, float scale)
-{
-#pragma clang fp contract(off)
-    return loc + eps * scale;
-}
 
 // (U, V) = elements [r] and [rows + r] of jax.random.uniform(key, (2 rows,)): one threefry call, counter pair (r, rows + r)
 __device__ __forceinline__ void glm_uniform_pair(uint32_t k0, uint32_t k1, uint32_t rows, uint32_t r, double& U, double& V)
@@ -112,16 +97,13 @@ template <int FAMILY>
 __global__ void __launch_bounds__(256) k_predict_glm(GlmPredictArgs g)
 {
     // [k][draw] | [k][row] during the product; afterwards the same bytes hold each wave's t, half a tile at a time
-    __shared__ float smem[2 * D3P_PG_TK * D3P_PG_LD];
-    __shared__ uint32_t keys[D3P_PG_TM][4];   // per draw of the tile: the obs key and fold_in(obs key, 0)
-    float (*As)[D3P_PG_LD] = reinterpret_cast<float (*)[D3P_PG_LD]>(smem);
-    float (*Bs)[D3P_PG_LD] = reinterpret_cast<float (*)[D3P_PG_LD]>(smem + D3P_PG_TK * D3P_PG_LD);
+    __shared__ float smem[D3P_TILE_SMEM];
+    __shared__ uint32_t keys[D3P_TILE_M][4];   // per draw of the tile: the obs key and fold_in(obs key, 0)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_PG_TN;
-    const uint32_t s0 = blockIdx.y * D3P_PG_TM;
-    const int d = g.d;
-    if (tid < D3P_PG_TM) {   // (read after the barriers of the product loop, which runs at least once: d >= 1)
+    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_TILE_N;
+    const uint32_t s0 = blockIdx.y * D3P_TILE_M;
+    if (tid < D3P_TILE_M) {   // (read after the barriers of the product loop, which runs at least once: d >= 1)
         const uint32_t s = s0 + tid;
         uint32_t o0 = 0u, o1 = 0u, f0 = 0u, f1 = 0u;
         if (s < g.n) {
@@ -131,60 +113,15 @@ __global__ void __launch_bounds__(256) k_predict_glm(GlmPredictArgs g)
         }
         keys[tid][0] = o0; keys[tid][1] = o1; keys[tid][2] = f0; keys[tid][3] = f1;
     }
-    predict_glm_f16v acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-    // staging: element e = tid + 256 q of a slice -> (tile row e / 32, k e % 32): 32 consecutive threads read 128 contiguous bytes
-    float ra[16], rb[16];
-    auto fetch = [&](int kc) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q, row = e >> 5, k = kc + (e & 31);
-            const uint32_t s = s0 + row;
-            const uint64_t r = r0 + row;
-            ra[q] = (s < g.n && k < d) ? g.lat[(size_t)s * g.ld + g.w_off + k] : 0.f;
-            rb[q] = (r < g.rows && k < d) ? g.X[r * (uint64_t)d + k] : 0.f;
-        }
-    };
-    fetch(0);
-    for (int kc = 0; kc < d; kc += D3P_PG_TK) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q;
-            As[e & 31][e >> 5] = ra[q];
-            Bs[e & 31][e >> 5] = rb[q];
-        }
-        __syncthreads();
-        if (kc + D3P_PG_TK < d) fetch(kc + D3P_PG_TK);   // next slice in flight while this one multiplies
-#pragma unroll
-        for (int kk = 0; kk < D3P_PG_TK; kk += 2) {
-            const int k = kk + (lane >> 5), c = lane & 31;
-            const float a0 = As[k][wm * 64 + c], a1 = As[k][wm * 64 + 32 + c];
-            const float b0 = Bs[k][wn * 64 + c], b1 = Bs[k][wn * 64 + 32 + c];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    tile_f16v acc[2][2];
+    tile_product(smem, g, r0, s0, acc);
     // Epilogue, per half of the wave's 64 draws: the accumulators go to LDS ([draw 0..31][row 0..63], rows padded to 65 floats), then
     // lane l owns row l and walks the 32 draws; the accumulators are dead from there on, so the outcome rule has the registers
-    float* L = smem + wave * (32 * 65);
+    float* L = tile_block(smem);
     const uint64_t r = r0 + wn * 64 + lane;
 #pragma unroll 1
     for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const float av = mb == 0 ? acc[0][nb][v] : acc[1][nb][v];
-                L[(8 * (v >> 2) + 4 * (lane >> 5) + (v & 3)) * 65 + nb * 32 + (lane & 31)] = av;
-            }
+        tile_scatter(L, mb == 0 ? acc[0][0] : acc[1][0], mb == 0 ? acc[0][1] : acc[1][1]);   // (selected by hand: the loop is not unrolled)
         __syncthreads();
         if (r < g.rows) {
 #pragma unroll 1
@@ -197,7 +134,7 @@ __global__ void __launch_bounds__(256) k_predict_glm(GlmPredictArgs g)
                 const size_t at = (size_t)s * g.rows + r;
                 if (FAMILY == D3P_FAMILY_LINREG) {
                     const float eps = bits_to_normal(tf_iota_word(keys[sl][0], keys[sl][1], g.rows, r));
-                    static_cast<float*>(g.obs)[at] = glm_normal_value(t, eps, g.sigma);
+                    static_cast<float*>(g.obs)[at] = normal_site_value(t, eps, g.sigma);
                 } else {
                     static_cast<int32_t*>(g.obs)[at] = poisson_draw(t, keys[sl][0], keys[sl][1], keys[sl][2], keys[sl][3], (uint32_t)g.rows, (uint32_t)r);
                 }
@@ -224,23 +161,17 @@ int d3p_predict_glm(void* stream, const d3p_logreg_model* model, const float* X_
         return fail(D3P_E_UNSUPPORTED, "%s: linear and Poisson regression only (logistic regression: d3p_predict_logreg; the Gaussian mean: "
                     "d3p_predict_gauss)", what);
     if (d != m->d) return fail(D3P_E_INVALID_ARG, "%s: d = %d differs from the model's %d", what, d, m->d);
-    if (!X_dev || !latent_dev || !obs_keys_dev || !obs_dev) return fail(D3P_E_INVALID_ARG, "%s: null X / latent / obs_keys / obs pointer", what);
-    if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
-    if (!(w_off >= 0 && (int64_t)w_off + d <= latent_ld && b_col < latent_ld && b_col >= -1 && !(b_col >= w_off && b_col < w_off + d)))
-        return fail(D3P_E_INVALID_ARG, "%s: the weights [w_off, w_off + d) and the intercept column must lie in a latent row, apart", what);
-    if ((m->intercept != 0) != (b_col >= 0)) return fail(D3P_E_INVALID_ARG, "%s: b_col must be given exactly when the model has an intercept", what);
-    if (rows > 0xFFFFFFFFull || cdiv(rows, D3P_PG_TN) > 0x7fffffffu || cdiv(n, D3P_PG_TM) > 65535u)
-        return fail(D3P_E_INVALID_ARG, "%s: rows <= 2^32 - 1 and n <= 128 x 65535", what);
     if (m->family == D3P_FAMILY_POISSON && 2 * rows > 0xFFFFFFFFull)
         return fail(D3P_E_INVALID_ARG, "%s: Poisson outcomes need 2 rows < 2^32 (one threefry stream of 2 rows uniforms per iteration)", what);
-    if (rows == 0) return D3P_OK;
-    if (!is_device_ptr(X_dev) || !is_device_ptr(latent_dev) || !is_device_ptr(obs_keys_dev) || !is_device_ptr(obs_dev))
-        return fail(D3P_E_INVALID_ARG, "%s: X, latent, obs_keys and obs must be device memory", what);
+    bool launch;
+    if (int rc = glm_tile_check(what, m, rows, latent_ld, w_off, b_col, n, {X_dev, latent_dev, obs_keys_dev, obs_dev}, "X / latent / obs_keys / obs",
+                                "X, latent, obs_keys and obs", &launch); rc || !launch)
+        return rc;
     GlmPredictArgs g;
     g.X = X_dev; g.rows = rows; g.d = d; g.w_off = w_off; g.b_col = b_col; g.lat = latent_dev; g.ld = latent_ld; g.n = n;
     g.sigma = m->family == D3P_FAMILY_LINREG ? m->lik_sigma : 0.f;
     g.obs_keys = obs_keys_dev; g.obs = obs_dev;
-    const dim3 grid(cdiv(rows, D3P_PG_TN), cdiv(n, D3P_PG_TM));
+    const dim3 grid(cdiv(rows, D3P_TILE_N), cdiv(n, D3P_TILE_M));
     hipStream_t s = (hipStream_t)stream;
     if (m->family == D3P_FAMILY_LINREG) hipLaunchKernelGGL((k_predict_glm<D3P_FAMILY_LINREG>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((k_predict_glm<D3P_FAMILY_POISSON>), grid, dim3(256), 0, s, g);

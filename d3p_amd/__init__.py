@@ -7,15 +7,15 @@ PyTorch is used for device memory, streams and torch.distributed only.
 """
 from .version import __version__  # noqa: F401
 
-__all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density"]
+__all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria"]
 
 
 def __getattr__(name):
     # d3p_amd.infer_util (log_likelihood, log predictive densities), d3p_amd.prediction (posterior predictive mean and variance) and
     # d3p_amd.predictive (predictive sampling for the regression family) and d3p_amd.mixture (predictive sampling and cluster
     # assignment for the mixture model) and d3p_amd.mixture_density (log predictive density and responsibilities of the mixture model)
-    # without making `import d3p_amd` import torch
-    if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density"):
+    # and d3p_amd.criteria (waic, posterior_waic, compare) without making `import d3p_amd` import torch
+    if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

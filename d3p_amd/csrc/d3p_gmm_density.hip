@@ -6,6 +6,8 @@
 //   rows form     ll[s, r]   = logsumexp_j a[s, r, j]                                 (n x rows)
 //   reduced form  lppd[r]    = logsumexp_s ll[s, r] - log n                           (rows)
 //                 resp[r, j] = (1 / n) sum_s exp(a[s, r, j] - ll[s, r])               (rows x k)
+//   WAIC form     lppd[r]    = the reduced form's value, bit for bit                  (rows)
+//                 pwaic[r]   = Var_s ll[s, r] = M2 / (n - ddof)                       (rows)
 // The reduced form writes neither a nor ll to memory.
 //
 // Geometry.  A workgroup owns D3P_GD_ROW_TILE = 64 rows, staged once in LDS with an odd stride (d | 1: the 32 lanes of a bank group
@@ -29,12 +31,21 @@
 // Special values: pis_j = 0 gives a_j = -inf, which adds nothing; a draw whose every a_j is -inf has ll = -inf (never NaN) and
 // contributes NaN (0 / 0) to the row's resp; every draw -inf gives lppd = -inf.  A NaN in a row of obs or in a draw's latents makes
 // every a_j of that (draw, row) NaN in effect: ll is NaN and so is every responsibility, as d3p_gmm_assign makes the whole row NaN.
+//
+// The WAIC form (REDUCE = 2; d3p_amd/criteria.py) keeps no responsibility sums: per row the running (max, sum)
+// as the reduced form, and beside it k_moments' shifted sums of ll (d3p_shifted_sums.h): c = the wave's first finite ll of the row,
+// float64 sums of (ll - c) and (ll - c)^2, a count and flags.  Wave 0 merges the waves' parts in Chan's pairwise form in the same
+// fixed order 1, 2, 3 (a wave that owned no draw has count 0 and is skipped, never divided by) and finishes pwaic = M2 / (n - ddof)
+// in float64, rounded to float32 once; every draw of a row equal gives exactly 0.  Special values as k_loglik's WAIC form: ll = -inf
+// is not added but remembered, and such a row gets pwaic = +inf (also when every draw is -inf, where lppd = -inf); a NaN ll makes
+// both outputs NaN; ll = +inf (not reached from finite inputs) is not added either and makes pwaic NaN.
 #include <mutex>
 #include <utility>
 #include <vector>
 
 #include "d3p_device.h"
 #include "d3p_host.h"
+#include "d3p_shifted_sums.h"
 
 namespace d3p {
 
@@ -51,6 +62,8 @@ struct GmmDensityArgs {
     float* ll;     // rows form
     float* lppd;   // reduced form, nullable
     float* resp;   // reduced form, nullable
+    float* pwaic;    // WAIC form (with lppd; both required)
+    uint32_t ddof;   // WAIC form: 0 or 1
 };
 
 // floats of LDS in front of the waves' latent copies (the row tile, rounded up to a float2 boundary) and per wave
@@ -83,6 +96,9 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
     double racc[KMAX];
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) racc[j] = 0.0;
+    double v1 = 0.0, v2 = 0.0;        // WAIC form: sum (ll - vc), sum (ll - vc)^2
+    float vc = 0.f;                   //            the shift: this wave's first finite ll of the row
+    uint32_t vcnt = 0, vflags = 0;    //            values in the sums; D3P_SHIFTED_* flags
     // every wave runs the same number of passes (the barriers are workgroup-wide); a wave without a draw in the last pass idles
     const uint32_t passes = (g.n + (uint32_t)W - 1) / (uint32_t)W;
     for (uint32_t it = 0; it < passes; ++it) {
@@ -164,26 +180,36 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
             } else if (ll != -INFINITY) {   // (a NaN ll makes the sum NaN)
                 run_s += (double)expf(ll - run_m);
             }
-            if (g.resp) {
+            if (REDUCE == 1 && g.resp) {
 #pragma unroll
                 for (int j = 0; j < KMAX; ++j)
                     if (j < k) racc[j] += (double)(q[j] * rinv);
             }
+            if (REDUCE == 2) shifted_add(ll, vc, v1, v2, vcnt, vflags);
         }
     }
     if (REDUCE) {
         // waves 1 .. W - 1 hand their accumulators to wave 0, one after the other; the row tile and the latents are no longer needed
         double* Rs = reinterpret_cast<double*>(lds);   // [j][lane]
-        double* Ss = Rs + (size_t)k * 64;              // [lane]
+        double* Ss = Rs + (REDUCE == 2 ? 0 : (size_t)k * 64);   // [lane] (the WAIC form has no Rs)
         float* Ms = reinterpret_cast<float*>(Ss + 64);  // [lane]
+        // WAIC form, behind them: [2][lane] shifted sums, then [lane] shifts, counts and flags
+        double* Vs = reinterpret_cast<double*>(Ms + 64);
+        float* Cs = reinterpret_cast<float*>(Vs + 128);
+        uint32_t* Ks = reinterpret_cast<uint32_t*>(Cs + 64);
+        uint32_t* Fs = Ks + 64;
+        uint32_t ka = vcnt;
+        double ma = 0.0, qa = 0.0;
+        if (REDUCE == 2 && ka) moments_part(ka, vc, v1, v2, ma, qa);   // wave 0's own part first
         __syncthreads();
         for (int w = 1; w < W; ++w) {
             if (wave == w) {
                 Ss[lane] = run_s;
                 Ms[lane] = run_m;
+                if (REDUCE == 2) { Vs[lane] = v1; Vs[64 + lane] = v2; Cs[lane] = vc; Ks[lane] = vcnt; Fs[lane] = vflags; }
 #pragma unroll
                 for (int j = 0; j < KMAX; ++j)
-                    if (j < k) Rs[j * 64 + lane] = racc[j];
+                    if (REDUCE == 1 && j < k) Rs[j * 64 + lane] = racc[j];
             }
             __syncthreads();
             if (wave == 0) {
@@ -197,7 +223,14 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
                 run_m = mm;
 #pragma unroll
                 for (int j = 0; j < KMAX; ++j)
-                    if (j < k) racc[j] += Rs[j * 64 + lane];
+                    if (REDUCE == 1 && j < k) racc[j] += Rs[j * 64 + lane];
+                if (REDUCE == 2) {
+                    const uint32_t kb = Ks[lane];
+                    double mb = 0.0, qb = 0.0;
+                    if (kb) moments_part(kb, Cs[lane], Vs[lane], Vs[64 + lane], mb, qb);
+                    chan_merge(ka, ma, qa, kb, mb, qb);
+                    vflags |= Fs[lane];
+                }
             }
             __syncthreads();
         }
@@ -205,11 +238,12 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
             const uint64_t r = r0 + lane;
             if (g.lppd)
                 g.lppd[r] = (run_m == -INFINITY && run_s == 0.0) ? -INFINITY : (float)(((double)run_m + log(run_s)) - log((double)g.n));
-            if (g.resp) {
+            if (REDUCE == 1 && g.resp) {
 #pragma unroll
                 for (int j = 0; j < KMAX; ++j)
                     if (j < k) g.resp[r * (uint64_t)k + j] = (float)(racc[j] / (double)g.n);
             }
+            if (REDUCE == 2) g.pwaic[r] = pwaic_value(qa, g.n, g.ddof, vflags);   // (no finite ll at all: M2 = 0, and the flags say so)
         }
     }
 }
@@ -246,28 +280,33 @@ static int gd_launch(const char* what, hipStream_t s, const GmmDensityArgs& g, i
 
 template <int REDUCE>
 static int gd_entry(const char* what, void* stream, const float* obs, uint64_t rows, int32_t d, const float* latent, int64_t ld, int32_t k,
-                    uint32_t n, float* ll, float* lppd, float* resp)
+                    uint32_t n, float* ll, float* lppd, float* resp, float* pwaic = nullptr, uint32_t ddof = 0)
 {
     if (!obs || !latent) return fail(D3P_E_INVALID_ARG, "%s: null obs / latent pointer", what);
+    if (REDUCE == 2 && (!lppd || !pwaic)) return fail(D3P_E_INVALID_ARG, "%s: null lppd / pwaic pointer", what);
     if (REDUCE ? (!lppd && !resp) : !ll)
         return fail(D3P_E_INVALID_ARG, REDUCE ? "%s: at least one of the two outputs is required" : "%s: null output pointer", what);
-    if (!gd_aligned(obs) || !gd_aligned(latent) || !gd_aligned(ll) || !gd_aligned(lppd) || !gd_aligned(resp))
+    if (!gd_aligned(obs) || !gd_aligned(latent) || !gd_aligned(ll) || !gd_aligned(lppd) || !gd_aligned(resp) || !gd_aligned(pwaic))
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (k < 1 || d < 1) return fail(D3P_E_INVALID_ARG, "%s: k and d must be >= 1 (k = %d, d = %d)", what, k, d);
     if (k > 32 || d > 256 || (k > 16 && d > 128))
         return fail(D3P_E_UNSUPPORTED, "%s: supported shapes are k <= 16 with d <= 256 and k <= 32 with d <= 128 (k = %d, d = %d)", what, k, d);
     if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
     if (n > 0x7fffffffu) return fail(D3P_E_UNSUPPORTED, "%s: n <= 2^31 - 1", what);
+    if (REDUCE == 2 && ddof > 1) return fail(D3P_E_INVALID_ARG, "%s: ddof must be 0 or 1 (got %u)", what, ddof);
+    if (REDUCE == 2 && n <= ddof) return fail(D3P_E_INVALID_ARG, "%s: n > ddof is required (n = %u, ddof = %u)", what, n, ddof);
     if (ld < (int64_t)k + 2 * (int64_t)k * d) return fail(D3P_E_INVALID_ARG, "%s: a latent row holds k + 2 k d values", what);
     if (rows > 0xFFFFFFFFull || rows * (uint64_t)d > 0xFFFFFFFFull) return fail(D3P_E_UNSUPPORTED, "%s: rows d < 2^32", what);
     if (rows == 0) return D3P_OK;
     if (!is_device_ptr(obs) || !is_device_ptr(latent) || (ll && !is_device_ptr(ll)) || (lppd && !is_device_ptr(lppd)) ||
-        (resp && !is_device_ptr(resp)))
+        (resp && !is_device_ptr(resp)) || (pwaic && !is_device_ptr(pwaic)))
         return fail(D3P_E_INVALID_ARG, "%s: every pointer must be device memory", what);
     GmmDensityArgs g;
     g.obs = obs; g.lat = latent; g.ld = ld; g.rows = (uint32_t)rows; g.n = n; g.k = k; g.d = d; g.ll = ll; g.lppd = lppd; g.resp = resp;
+    g.pwaic = pwaic; g.ddof = ddof;
     // four waves split the draws where their four latent copies fit beside the row tile, otherwise two: a function of (k, d) alone
-    const size_t combine = REDUCE ? (size_t)64 * 8 * (k + 1) + 64 * 4 : 0;
+    // (the WAIC form hands over the sum, the maximum, two shifted sums, the shift, the count and the flags per lane)
+    const size_t combine = REDUCE == 2 ? (size_t)64 * (8 + 4 + 2 * 8 + 3 * 4) : REDUCE ? (size_t)64 * 8 * (k + 1) + 64 * 4 : 0;
     int W = D3P_GD_DRAW_TILE;
     size_t lds = sizeof(float) * ((size_t)gd_tile_floats(d) + (size_t)W * gd_wave_floats(k, d));
     if (lds > D3P_GD_LDS_MAX) {
@@ -298,6 +337,13 @@ int d3p_gmm_loglik_reduce(void* stream, const float* obs_dev, uint64_t rows, int
                           uint32_t n, float* lppd_out_dev, float* resp_out_dev)
 {
     return gd_entry<1>("d3p_gmm_loglik_reduce", stream, obs_dev, rows, d, latent_dev, latent_ld, k, n, nullptr, lppd_out_dev, resp_out_dev);
+}
+
+int d3p_gmm_loglik_waic(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld, int32_t k,
+                        uint32_t n, uint32_t ddof, float* lppd_rows_dev, float* pwaic_rows_dev)
+{
+    return gd_entry<2>("d3p_gmm_loglik_waic", stream, obs_dev, rows, d, latent_dev, latent_ld, k, n, nullptr, lppd_rows_dev, nullptr, pwaic_rows_dev,
+                       ddof);
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 #include "d3p_device.h"
 #include "d3p_glm_tile.h"
 #include "d3p_host.h"
+#include "d3p_shifted_sums.h"
 
 namespace d3p {
 
@@ -38,15 +39,6 @@ struct MomentsArgs {
     float* mean;
     float* var;
 };
-
-// (count, mean, sum of squared deviations from it) of the k values whose sums shifted by c are s1, s2; k >= 1
-__device__ __forceinline__ void moments_part(uint32_t k, float c, double s1, double s2, double& mean, double& m2)
-{
-    const double kd = (double)k;
-    mean = (double)c + s1 / kd;
-    const double r = s2 - (s1 * s1) / kd;
-    m2 = r < 0.0 ? 0.0 : r;   // (a NaN stays)
-}
 
 template <int FAMILY>
 // Registers: as k_loglik's lppd form, one wave per SIMD (the staging addresses live across the draw-tile loop); no scratch.

@@ -135,11 +135,18 @@ def _model_struct(model, fam, d):
                             _lib.D3P_GUIDE_SOFTPLUS, float(getattr(model, "obs_scale", 0.0)) if fam == _lib.D3P_FAMILY_LINREG else 0.0)
 
 
-def _launch(lppd, model, fam, model_args, rows, d, n, latent):
-    """latent = (tensor at the first latent row, ld, w_off, b_col); returns (n, rows) or (rows,) float32 on the current GPU."""
+def _launch(lppd, model, fam, model_args, rows, d, n, latent, waic_ddof=None):
+    """latent = (tensor at the first latent row, ld, w_off, b_col); returns (n, rows) or (rows,) float32 on the current GPU.
+    waic_ddof = 0 or 1 (d3p_amd.criteria): the WAIC form, which returns (lppd, p_waic), both (rows,)."""
     first, ld, w_off, b_col = latent
     X = M._f32(model_args[0], "X")
     y = M._f32(model_args[1], "y").reshape(rows)
+    if waic_ddof is not None:
+        out, pw = torch.empty((rows,), dtype=torch.float32, device=X.device), torch.empty((rows,), dtype=torch.float32, device=X.device)
+        ms = _model_struct(model, fam, d)
+        check(_lib.load().d3p_loglik_waic(stream_ptr(), C.byref(ms), ptr(X), ptr(y), rows, ptr(first), ld, w_off, b_col, n, int(waic_ddof),
+                                          ptr(out), ptr(pw)))
+        return out, pw
     out = torch.empty((rows,) if lppd else (n, rows), dtype=torch.float32, device=X.device)
     ms = _model_struct(model, fam, d)
     fn = _lib.load().d3p_loglik_lppd if lppd else _lib.load().d3p_loglik_rows
@@ -147,14 +154,25 @@ def _launch(lppd, model, fam, model_args, rows, d, n, latent):
     return out
 
 
-def _over_samples(lppd, model, posterior_samples, model_args):
+def _over_samples(lppd, model, posterior_samples, model_args, waic_ddof=None):
     fam = _family(model)
     rows, d = _data(model, model_args)
     n, single = _sample_shape(model, posterior_samples, d)
+    _check_ddof(n, waic_ddof)
     _lib.require_device()   # (every check above runs without a device)
     with torch.cuda.device(M._device()):
-        out = _launch(lppd, model, fam, model_args, rows, d, n, _pack(model, posterior_samples, n, d))
+        out = _launch(lppd, model, fam, model_args, rows, d, n, _pack(model, posterior_samples, n, d), waic_ddof)
     return out, single, rows, d
+
+
+def _check_ddof(n, ddof):
+    """The WAIC forms' divisor n - ddof (None: not a WAIC form): ddof is 0 or 1 and n > ddof."""
+    if ddof is None:
+        return
+    if isinstance(ddof, bool) or ddof not in (0, 1):
+        raise ValueError(f"ddof must be 0 or 1, got {ddof!r}")
+    if n <= ddof:
+        raise ValueError(f"{n} posterior draw(s): the variance over the draws with ddof = {ddof} needs n > ddof")
 
 
 def log_likelihood(model, posterior_samples, *model_args, **kwargs):
@@ -211,12 +229,17 @@ def posterior_log_predictive_density(rng_key, n, model, model_args, guide, param
     threefry (jax) key as for ``d3p_amd.modelling``.  The draws follow ``sample_multi_posterior_predictive``'s key rule (draw i on
     ``split(rng_key, n)[i]``, the guide's chain, site key 0 onwards): with the same key and ``n`` the latents are the ones that
     function returns.  Guides: ``AutoDiagonalNormal``, ``DiagonalNormalGuide``; ``MeanFieldGuide`` for logistic regression."""
+    return _posterior(rng_key, n, model, model_args, guide, params)
+
+
+def _posterior(rng_key, n, model, model_args, guide, params, waic_ddof=None):
     fam = _family(model)
     _check_guide(model, guide)
     n = int(n)
     if n < 1:
         raise ValueError("n must be >= 1")
     rows, d = _data(model, model_args)
+    _check_ddof(n, waic_ddof)
     if not isinstance(params, dict):
         raise ValueError("params: the dict DPSVI.get_params returns is required")
     gparams = [(name, M._param(params, name, size)) for name, size in M._guide_param_names(guide, model, d)]
@@ -225,4 +248,4 @@ def posterior_log_predictive_density(rng_key, n, model, model_args, guide, param
     dev = key.device
     with torch.cuda.device(dev):
         latent = _guide_latents(key, n, model, guide, gparams, d, rows, dev)
-        return _launch(True, model, fam, model_args, rows, d, n, latent)
+        return _launch(True, model, fam, model_args, rows, d, n, latent, waic_ddof)

@@ -17,6 +17,9 @@ map (:113-161) -- instead of the closest mode.
 --held-out-density (off by default; d3p_amd.mixture_density) adds two lines after training: the mean log predictive density of the
 test split under --posterior-draws draws from the fitted guide, and the accuracy of the argmax of the responsibilities averaged over
 the same draws, beside the assignment accuracy above.
+
+--waic (off by default; d3p_amd.criteria) adds one line: elpd_waic +- its standard error and p_waic of the fitted mixture on the
+training split, under --posterior-draws draws from the fitted guide.
 """
 import argparse
 import itertools
@@ -94,6 +97,14 @@ def held_out_density(X_test, z_test, params, k, num_draws, seed=4321):
     return float(out["log_predictive_density"].mean()), best
 
 
+def waic_report(X, params, k, num_draws, seed=4322):
+    """The WAICResult of the fitted mixture on X under num_draws draws from the guide at params."""
+    from d3p_amd import criteria
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    return criteria.posterior_waic(threefry.PRNGKey(seed), num_draws, model, (k, X), GaussianMixtureGuide(model), params)
+
+
 def main(args):
     L.require_device()
     N, k, d = args.num_samples, args.num_components, args.dimensions
@@ -159,6 +170,10 @@ def main(args):
         print("held-out log predictive density (mean over {} points, {} posterior draws): {:.4f}".format(
             X_test.shape[0], args.posterior_draws, lppd))
         print("assignment accuracy (argmax of posterior responsibilities): {:.4f}".format(soft_acc))
+    if getattr(args, "waic", False):
+        res = waic_report(X_train, params, k, args.posterior_draws)
+        print("WAIC ({} points, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
+            res.n_rows, res.n_draws, float(res.elpd_waic), float(res.se), float(res.p_waic)))
     return acc, pis, modes
 
 
@@ -178,7 +193,8 @@ def parse_args(argv=None):
                         help="'posterior': score with the per-component log-posterior, as the reference does")
     parser.add_argument('--held-out-density', action='store_true',
                         help='report the held-out log predictive density and the soft-assignment accuracy under the fitted posterior')
-    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --held-out-density')
+    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --held-out-density and --waic')
+    parser.add_argument('--waic', action='store_true', help='report elpd_waic, its standard error and p_waic of the fitted mixture')
     return parser.parse_args(argv)
 
 

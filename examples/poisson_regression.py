@@ -4,6 +4,10 @@ with AutoDiagonalNormal, training with the device-resident loop (`run_steps`), t
 from the weights that generated the data.
 
     w ~ Normal(0, 1)^d, intercept ~ Normal(0, 1);  ys ~ Poisson(rate = exp(xs @ w + intercept))
+
+--waic (off by default; d3p_amd.criteria) adds three lines: elpd_waic +- its standard error and p_waic of the trained model under
+--posterior-draws draws from the fitted guide, the same for a LinearRegression trained on the same counts with the same settings, and
+the paired comparison of the two.
 """
 import argparse
 import os
@@ -16,7 +20,7 @@ import torch  # noqa: E402
 import d3p_amd._lib as L  # noqa: E402
 import d3p_amd.random as rng_suite  # noqa: E402
 from d3p_amd.minibatch import subsample_batchify_data  # noqa: E402
-from d3p_amd.models import Adam, AutoDiagonalNormal, PoissonRegression, Trace_ELBO  # noqa: E402
+from d3p_amd.models import Adam, AutoDiagonalNormal, LinearRegression, PoissonRegression, Trace_ELBO  # noqa: E402
 from d3p_amd.svi import DPSVI  # noqa: E402
 
 
@@ -27,6 +31,30 @@ def create_toy_data(N, d, seed=123):
     X = torch.randn(N, d, generator=g, device="cuda")
     y = torch.poisson(torch.exp(X @ w_true), generator=g)
     return X.contiguous(), y.to(torch.float32).contiguous(), w_true
+
+
+def fit(model, X, y, args):
+    """DPSVI with AutoDiagonalNormal on (X, y) with the example's settings and keys: (svi, trained state)."""
+    svi = DPSVI(model, AutoDiagonalNormal(model), Adam(args.learning_rate), Trace_ELBO(), dp_scale=args.sigma,
+                clipping_threshold=args.clip_threshold, num_obs_total=X.shape[0], rng_suite=rng_suite)
+    key, init_key, batch_key = rng_suite.split(rng_suite.PRNGKey(0), 3)
+    init, get_batch = subsample_batchify_data((X, y), args.batch_size, rng_suite=rng_suite)
+    _, batchifier_state = init(rng_key=batch_key)
+    state = svi.init(init_key, *get_batch(0, batchifier_state))
+    state, _ = svi.run_steps(state, get_batch, batchifier_state, 0, args.num_steps)
+    return svi, state
+
+
+def waic_report(model, svi, state, X, y, num_draws, seed=2):
+    """The WAICResult (pointwise arrays kept, for compare) of a trained model on (X, y) under num_draws draws from its guide."""
+    from d3p_amd import criteria
+    import d3p_amd.random.debug as jax_random
+    return criteria.posterior_waic(jax_random.PRNGKey(seed), num_draws, model, (X, y), svi.guide, svi.get_params(state), pointwise=True)
+
+
+def _waic_line(name, res):
+    return "{} WAIC ({} rows, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
+        name, res.n_rows, res.n_draws, float(res.elpd_waic), float(res.se), float(res.p_waic))
 
 
 def main(args):
@@ -53,6 +81,16 @@ def main(args):
     pred = posterior_predictive_samples(jax_random.PRNGKey(1), 100, model, (X,), svi.guide, svi.get_params(state))["obs"].double()
     print("posterior predictive check (100 draws): observed mean {:.4f}, variance {:.4f};  predictive mean {:.4f}, variance {:.4f}".format(
         float(y.mean()), float(y.var()), float(pred.mean()), float(pred.var(dim=1).mean())))
+    if getattr(args, "waic", False):
+        from d3p_amd import criteria
+        draws = getattr(args, "posterior_draws", 100)
+        poisson = waic_report(model, svi, state, X, y, draws)
+        print(_waic_line("Poisson", poisson))
+        linear_model = LinearRegression(d, prior_scale=1.0, intercept=True)
+        linear = waic_report(linear_model, *fit(linear_model, X, y, args), X, y, draws)
+        print(_waic_line("linear", linear))
+        diff = criteria.compare(poisson, linear)
+        print("Poisson against linear on the same counts: elpd_diff {:.2f} +- {:.2f}".format(float(diff.elpd_diff), float(diff.se_diff)))
     return first, last, err0, err
 
 
@@ -65,4 +103,7 @@ if __name__ == "__main__":
     parser.add_argument('-batch-size', default=200, type=int, help='batch size')
     parser.add_argument('-d', '--dimensions', default=4, type=int, help='data dimension')
     parser.add_argument('-N', '--num-samples', default=10000, type=int, help='data samples count')
+    parser.add_argument('--waic', action='store_true',
+                        help='report WAIC of the trained model, of a linear regression on the same counts, and their comparison')
+    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --waic')
     main(parser.parse_args())

@@ -862,6 +862,22 @@ int d3p_gmm_loglik_rows(void* stream, const float* obs_dev, uint64_t rows, int32
 int d3p_gmm_loglik_reduce(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
                           int32_t k, uint32_t n, float* lppd_out_dev, float* resp_out_dev);
 
+/* WAIC (Watanabe-Akaike information criterion; Vehtari, Gelman & Gabry 2017, eqs. 11-13) per row over n posterior draws
+ * (d3p_amd/criteria.py); added symbols, ABI 9 unchanged.  With ll[s, r] of d3p_loglik_rows resp. d3p_gmm_loglik_rows:
+ *   lppd_rows_dev[r]  = logsumexp_s ll[s, r] - log n              bit-identical to d3p_loglik_lppd's / d3p_gmm_loglik_reduce's value
+ *   pwaic_rows_dev[r] = sum_s (ll[s, r] - mean_s ll[s, r])^2 / (n - ddof)       the between-draw variance of ll
+ * in one pass, no n x rows intermediate: shifted float64 sums per wave in draw order (the shift is the wave's first finite ll of the
+ * row), the waves merged in Chan's pairwise form in a fixed order, one rounding to float32; deterministic.  Every draw of a row equal:
+ * pwaic is exactly 0.  A draw with ll = -inf is left out of the sums and makes the row's pwaic +inf (lppd stays finite unless every
+ * draw is -inf); a NaN ll makes both outputs of the row NaN; ll = +inf (not reached from finite inputs) makes pwaic NaN.
+ * d3p_loglik_waic: arguments, limits and errors are d3p_loglik_lppd's, both outputs required.  d3p_gmm_loglik_waic: those of
+ * d3p_gmm_loglik_reduce, both outputs required.  In addition ddof must be 0 or 1 and n > ddof, else D3P_E_INVALID_ARG; rows == 0:
+ * D3P_OK, no launch. */
+int d3p_loglik_waic(void* stream, const d3p_logreg_model* model, const float* X_dev, const float* y_dev, uint64_t rows, const float* latent_dev,
+                    int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, uint32_t ddof, float* lppd_rows_dev, float* pwaic_rows_dev);
+int d3p_gmm_loglik_waic(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
+                        int32_t k, uint32_t n, uint32_t ddof, float* lppd_rows_dev, float* pwaic_rows_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

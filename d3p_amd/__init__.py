@@ -7,7 +7,7 @@ PyTorch is used for device memory, streams and torch.distributed only.
 """
 from .version import __version__  # noqa: F401
 
-__all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria"]
+__all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "loo", "posterior_loo", "LOOResult"]
 
 
 def __getattr__(name):
@@ -18,4 +18,7 @@ def __getattr__(name):
     if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria"):
         import importlib
         return importlib.import_module("." + name, __name__)
+    if name in ("loo", "posterior_loo", "LOOResult"):   # PSIS-LOO (d3p_amd.criteria), under the same lazy rule
+        import importlib
+        return getattr(importlib.import_module(".criteria", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,7 +1,9 @@
-"""WAIC and pairwise model comparison for the regression models and the Gaussian mixture model.
+"""WAIC, PSIS-LOO and pairwise model comparison for the regression models and the Gaussian mixture model (DESIGN.md sections 4h, 4i).
 
     waic(model, posterior_samples, *model_args, ddof=1, pointwise=False)                                  -> WAICResult
     posterior_waic(rng_key, n, model, model_args, guide, params, ddof=1, pointwise=False, **kwargs)       -> WAICResult
+    loo(model, posterior_samples, *model_args, pointwise=False, slab_bytes=64 << 20)                      -> LOOResult
+    posterior_loo(rng_key, n, model, model_args, guide, params, pointwise=False, slab_bytes=64 << 20, **kwargs) -> LOOResult
     compare(a, b)                                                                                         -> ComparisonResult
 
 The Watanabe-Akaike information criterion (Vehtari, Gelman & Gabry 2017, eqs. 11-13 and 23) over ``n`` posterior draws, with
@@ -28,8 +30,21 @@ draw is ``-inf``.  A NaN makes the row NaN in all three pointwise arrays.  Non-f
 NaN ``se``.
 
 ``compare`` needs both results with ``pointwise=True`` over the same rows: ``elpd_diff = sum_r (a_r - b_r)`` and ``se_diff = sqrt(rows
-Var_r (a_r - b_r))`` (sample variance), the paired form of eq. 24.  It is pure torch and runs where the pointwise tensors are.
+Var_r (a_r - b_r))`` (sample variance), the paired form of eq. 24.  It is pure torch and runs where the pointwise tensors are.  Two
+``WAICResult`` pair their ``elpd_waic``, two ``LOOResult`` their ``elpd_loo``; one of each is refused.
+
+PSIS-LOO (the paper's section 2.1; Pareto-smoothed importance sampling of the leave-one-out predictive densities) over the same
+``ll``: ``d3p_psis_loo`` (include/d3p_hip.h states the steps) gives per row ``elpd_loo[r]``, ``lppd[r]`` and the Pareto shape
+``pareto_k[r]`` of the row's importance ratios, the diagnostic WAIC lacks: where ``k > k_threshold = min(1 - 1 / log10(n), 0.7)`` the
+row's estimate is not to be trusted (``n_high_k`` counts those rows; ``+inf`` -- no fit: fewer than 5 tail draws, a ``-inf`` draw --
+and NaN count as high).  ``p_loo[r] = lppd[r] - elpd_loo[r]``, ``looic = -2 elpd_loo``, totals and ``se`` as for WAIC.  Unlike WAIC
+this reduction needs the column's order statistics, so the ``n x rows`` matrix IS written -- in row slabs: the rows are taken in
+chunks of ``max(128, (slab_bytes // (4 n)) // 128 * 128)``, each chunk written by the rows entry (``d3p_loglik_rows`` /
+``d3p_gmm_loglik_rows`` on offset views of the data) into one reused buffer and consumed by ``d3p_psis_loo`` on the same stream; the
+latents are packed once.  The result does not depend on ``slab_bytes``.  ``n <= 65535``.  Special values: a ``-inf`` draw makes the
+row's ``elpd_loo = -inf`` and ``pareto_k = +inf``; a NaN makes the row NaN.
 """
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -39,6 +54,7 @@ from . import mixture_density as MD
 from .models import GaussianMixtureModel
 
 __all__ = ["waic", "posterior_waic", "compare", "WAICResult", "ComparisonResult"]
+# (loo, posterior_loo and LOOResult are public as well: the package exports them as d3p_amd.loo, d3p_amd.posterior_loo, d3p_amd.LOOResult)
 
 
 class WAICResult(NamedTuple):
@@ -51,8 +67,20 @@ class WAICResult(NamedTuple):
     pointwise: Optional[dict]    # None, or {"lppd", "p_waic", "elpd_waic"}: (rows,) float32
 
 
+class LOOResult(NamedTuple):
+    elpd_loo: torch.Tensor       # 0-d float64
+    p_loo: torch.Tensor          # 0-d float64: sum_r (lppd[r] - elpd_loo[r])
+    looic: torch.Tensor          # -2 elpd_loo
+    se: torch.Tensor             # standard error of elpd_loo
+    n_draws: int
+    n_rows: int
+    k_threshold: float           # min(1 - 1 / log10(n_draws), 0.7)
+    n_high_k: torch.Tensor       # 0-d int64: rows with pareto_k > k_threshold (NaN and +inf count)
+    pointwise: Optional[dict]    # None, or {"elpd_loo", "p_loo", "lppd", "pareto_k"}: (rows,) float32
+
+
 class ComparisonResult(NamedTuple):
-    elpd_diff: torch.Tensor      # 0-d float64: elpd_waic of a minus elpd_waic of b
+    elpd_diff: torch.Tensor      # 0-d float64: elpd (elpd_waic resp. elpd_loo) of a minus that of b
     se_diff: torch.Tensor        # its standard error from the paired pointwise differences
 
 
@@ -79,7 +107,7 @@ def _is_mixture(model, what):
         U._family(model)
     except TypeError:
         raise TypeError(f"{what}: unsupported model {type(model).__name__} (LogisticRegression, LinearRegression, PoissonRegression "
-                        "and GaussianMixtureModel have a WAIC here)") from None
+                        "and GaussianMixtureModel have a WAIC and a PSIS-LOO here)") from None
     return False
 
 
@@ -117,13 +145,61 @@ def posterior_waic(rng_key, n, model, model_args, guide, params, ddof=1, pointwi
     return _result(lppd, pw, int(n), pointwise)
 
 
+def _k_threshold(n):
+    """min(1 - 1 / log10(n), 0.7): the Pareto shape above which n draws do not give a reliable estimate (n = 1: -inf)."""
+    return min(1.0 - 1.0 / math.log10(n), 0.7) if n > 1 else -math.inf
+
+
+def _loo_result(elpd, lppd, khat, n, pointwise):
+    p = lppd - elpd
+    total, se = _total_and_se(elpd)
+    thr = _k_threshold(int(n))
+    high = torch.logical_not(khat <= thr).sum()
+    keep = {"elpd_loo": elpd, "p_loo": p, "lppd": lppd, "pareto_k": khat} if pointwise else None
+    return LOOResult(total, _total_and_se(p)[0], -2.0 * total, se, int(n), int(elpd.shape[0]), thr, high, keep)
+
+
+def _slab_bytes(slab_bytes):
+    U._check_slab_bytes(slab_bytes)   # (n <= 65535 is checked where n is known)
+    return slab_bytes
+
+
+def loo(model, posterior_samples, *model_args, pointwise=False, slab_bytes=64 << 20):
+    """PSIS-LOO of ``model`` on ``model_args``' data over the given posterior draws (module docstring)."""
+    mixture = _is_mixture(model, "loo")
+    slab_bytes = _slab_bytes(slab_bytes)
+    if mixture:
+        obs = model_args[0] if model_args else None
+        elpd, lppd, khat = MD._from_samples(model, posterior_samples, obs, False, True, False, loo_slab_bytes=slab_bytes)
+        n = MD.MX._shape_of(posterior_samples["pis"])[0]
+    else:
+        (elpd, lppd, khat), single, _, _ = U._over_samples(True, model, posterior_samples, model_args, loo_slab_bytes=slab_bytes)
+        n = 1 if single else MD.MX._shape_of(posterior_samples["w"])[0]
+    return _loo_result(elpd, lppd, khat, n, pointwise)
+
+
+def posterior_loo(rng_key, n, model, model_args, guide, params, pointwise=False, slab_bytes=64 << 20, **kwargs):
+    """``loo`` over ``n`` draws from the guide at ``params``, drawn on the device on ``posterior_waic``'s key rule: with the same key
+    and ``n`` the draws are the ones ``sample_multi_posterior_predictive`` resp. ``mixture.posterior_predictive_samples`` returns."""
+    mixture = _is_mixture(model, "posterior_loo")
+    slab_bytes = _slab_bytes(slab_bytes)
+    if mixture:
+        elpd, lppd, khat = MD._posterior(rng_key, n, model, model_args, guide, params, kwargs, True, False, loo_slab_bytes=slab_bytes)
+    else:
+        elpd, lppd, khat = U._posterior(rng_key, n, model, model_args, guide, params, loo_slab_bytes=slab_bytes)
+    return _loo_result(elpd, lppd, khat, int(n), pointwise)
+
+
 def compare(a, b):
-    """Paired comparison of two ``WAICResult`` over the same rows, both with ``pointwise=True``: ``ComparisonResult(elpd_diff,
-    se_diff)``, positive ``elpd_diff`` favouring ``a``."""
+    """Paired comparison of two ``WAICResult`` or of two ``LOOResult`` over the same rows, both with ``pointwise=True``:
+    ``ComparisonResult(elpd_diff, se_diff)``, positive ``elpd_diff`` favouring ``a``."""
     for name, r in (("a", a), ("b", b)):
-        if not isinstance(r, WAICResult) or r.pointwise is None:
-            raise ValueError(f"compare: {name} must be a WAICResult with its pointwise arrays (pointwise=True)")
+        if not isinstance(r, (WAICResult, LOOResult)) or r.pointwise is None:
+            raise ValueError(f"compare: {name} must be a WAICResult or a LOOResult with its pointwise arrays (pointwise=True)")
+    if type(a) is not type(b):
+        raise ValueError(f"compare: a {type(a).__name__} and a {type(b).__name__} estimate different quantities; compare two of a kind")
     if a.n_rows != b.n_rows:
         raise ValueError(f"compare: the results cover {a.n_rows} and {b.n_rows} rows; a paired comparison needs the same rows")
-    diff = a.pointwise["elpd_waic"].to(torch.float64) - b.pointwise["elpd_waic"].to(torch.float64)
+    site = "elpd_waic" if isinstance(a, WAICResult) else "elpd_loo"
+    diff = a.pointwise[site].to(torch.float64) - b.pointwise[site].to(torch.float64)
     return ComparisonResult(*_total_and_se(diff))

@@ -135,12 +135,50 @@ def _model_struct(model, fam, d):
                             _lib.D3P_GUIDE_SOFTPLUS, float(getattr(model, "obs_scale", 0.0)) if fam == _lib.D3P_FAMILY_LINREG else 0.0)
 
 
-def _launch(lppd, model, fam, model_args, rows, d, n, latent, waic_ddof=None):
+def _check_slab_bytes(slab_bytes):
+    if isinstance(slab_bytes, bool) or not isinstance(slab_bytes, int) or slab_bytes < 1:
+        raise ValueError(f"slab_bytes must be an int >= 1, got {slab_bytes!r}")
+
+
+def _loo_chunk(n, slab_bytes):
+    """Rows per slab of the PSIS-LOO forms (slab_bytes None: not one): max(128, a multiple of 128 whose n x chunk float32 matrix fits
+    slab_bytes).  Host checks only: slab_bytes an int >= 1 and n <= 65535 (d3p_psis_loo's limit)."""
+    if slab_bytes is None:
+        return None
+    _check_slab_bytes(slab_bytes)
+    if n > 65535:
+        raise ValueError(f"{n} posterior draws: PSIS-LOO runs at most 65535 draws (n <= 65535)")
+    return max(128, (slab_bytes // (4 * n)) // 128 * 128)
+
+
+def _psis_slabs(rows, n, chunk, dev, fill):
+    """PSIS-LOO over the rows in slabs of `chunk`: fill(lo, count, buf) launches the rows entry that writes ll[:, lo:lo + count] as an
+    (n, count) matrix at the head of the one reused buffer, and d3p_psis_loo follows on the same stream.  Returns (elpd_loo, lppd,
+    pareto_k), each (rows,) float32."""
+    lib = _lib.load()
+    elpd, lppd, khat = (torch.empty((rows,), dtype=torch.float32, device=dev) for _ in range(3))
+    buf = torch.empty((n * min(chunk, rows),), dtype=torch.float32, device=dev)
+    for lo in range(0, rows, chunk):
+        count = min(chunk, rows - lo)
+        fill(lo, count, buf)
+        check(lib.d3p_psis_loo(stream_ptr(), ptr(buf), count, n, count, ptr(elpd[lo:]), ptr(lppd[lo:]), ptr(khat[lo:])))
+    return elpd, lppd, khat
+
+
+def _launch(lppd, model, fam, model_args, rows, d, n, latent, waic_ddof=None, loo_chunk=None):
     """latent = (tensor at the first latent row, ld, w_off, b_col); returns (n, rows) or (rows,) float32 on the current GPU.
-    waic_ddof = 0 or 1 (d3p_amd.criteria): the WAIC form, which returns (lppd, p_waic), both (rows,)."""
+    waic_ddof = 0 or 1 (d3p_amd.criteria): the WAIC form, which returns (lppd, p_waic), both (rows,).  loo_chunk (d3p_amd.criteria):
+    the PSIS-LOO form in row slabs of that many rows, which returns (elpd_loo, lppd, pareto_k), each (rows,)."""
     first, ld, w_off, b_col = latent
     X = M._f32(model_args[0], "X")
     y = M._f32(model_args[1], "y").reshape(rows)
+    if loo_chunk is not None:
+        ms = _model_struct(model, fam, d)
+
+        def fill(lo, count, buf):
+            check(_lib.load().d3p_loglik_rows(stream_ptr(), C.byref(ms), ptr(X[lo:lo + count]), ptr(y[lo:lo + count]), count, ptr(first), ld,
+                                              w_off, b_col, n, ptr(buf)))
+        return _psis_slabs(rows, n, loo_chunk, X.device, fill)
     if waic_ddof is not None:
         out, pw = torch.empty((rows,), dtype=torch.float32, device=X.device), torch.empty((rows,), dtype=torch.float32, device=X.device)
         ms = _model_struct(model, fam, d)
@@ -154,14 +192,15 @@ def _launch(lppd, model, fam, model_args, rows, d, n, latent, waic_ddof=None):
     return out
 
 
-def _over_samples(lppd, model, posterior_samples, model_args, waic_ddof=None):
+def _over_samples(lppd, model, posterior_samples, model_args, waic_ddof=None, loo_slab_bytes=None):
     fam = _family(model)
     rows, d = _data(model, model_args)
     n, single = _sample_shape(model, posterior_samples, d)
     _check_ddof(n, waic_ddof)
+    chunk = _loo_chunk(n, loo_slab_bytes)
     _lib.require_device()   # (every check above runs without a device)
     with torch.cuda.device(M._device()):
-        out = _launch(lppd, model, fam, model_args, rows, d, n, _pack(model, posterior_samples, n, d), waic_ddof)
+        out = _launch(lppd, model, fam, model_args, rows, d, n, _pack(model, posterior_samples, n, d), waic_ddof, chunk)
     return out, single, rows, d
 
 
@@ -232,7 +271,7 @@ def posterior_log_predictive_density(rng_key, n, model, model_args, guide, param
     return _posterior(rng_key, n, model, model_args, guide, params)
 
 
-def _posterior(rng_key, n, model, model_args, guide, params, waic_ddof=None):
+def _posterior(rng_key, n, model, model_args, guide, params, waic_ddof=None, loo_slab_bytes=None):
     fam = _family(model)
     _check_guide(model, guide)
     n = int(n)
@@ -240,6 +279,7 @@ def _posterior(rng_key, n, model, model_args, guide, params, waic_ddof=None):
         raise ValueError("n must be >= 1")
     rows, d = _data(model, model_args)
     _check_ddof(n, waic_ddof)
+    chunk = _loo_chunk(n, loo_slab_bytes)
     if not isinstance(params, dict):
         raise ValueError("params: the dict DPSVI.get_params returns is required")
     gparams = [(name, M._param(params, name, size)) for name, size in M._guide_param_names(guide, model, d)]
@@ -248,4 +288,4 @@ def _posterior(rng_key, n, model, model_args, guide, params, waic_ddof=None):
     dev = key.device
     with torch.cuda.device(dev):
         latent = _guide_latents(key, n, model, guide, gparams, d, rows, dev)
-        return _launch(True, model, fam, model_args, rows, d, n, latent, waic_ddof)
+        return _launch(True, model, fam, model_args, rows, d, n, latent, waic_ddof, chunk)

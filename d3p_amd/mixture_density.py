@@ -38,7 +38,7 @@ from . import _lib
 from . import mixture as MX
 from . import modelling as M
 from ._lib import check, ptr, stream_ptr
-from .infer_util import _check_ddof
+from .infer_util import _check_ddof, _loo_chunk, _psis_slabs
 from .models import GaussianMixtureGuide, GaussianMixtureModel
 
 __all__ = ["log_likelihood", "log_predictive_density", "responsibilities", "posterior_log_predictive_density",
@@ -119,11 +119,16 @@ def _pack(samples, n, k, d):
     return buf, k + 2 * kd
 
 
-def _run(x, rows, d, latent, ld, k, n, want_ll, want_lppd, want_resp, waic_ddof=None):
+def _run(x, rows, d, latent, ld, k, n, want_ll, want_lppd, want_resp, waic_ddof=None, loo_chunk=None):
     """The launches on the current device; x is (rows, d) float32 contiguous there.  waic_ddof = 0 or 1 (d3p_amd.criteria): the
-    WAIC form, which returns (lppd, p_waic), both (rows,)."""
+    WAIC form, which returns (lppd, p_waic), both (rows,).  loo_chunk (d3p_amd.criteria): the PSIS-LOO form in row slabs of that many
+    rows, which returns (elpd_loo, lppd, pareto_k), each (rows,)."""
     dev = x.device
     lib = _lib.load()
+    if loo_chunk is not None:
+        def fill(lo, count, buf):
+            check(lib.d3p_gmm_loglik_rows(stream_ptr(), ptr(x[lo:lo + count]), count, d, ptr(latent), ld, k, n, ptr(buf)))
+        return _psis_slabs(rows, n, loo_chunk, dev, fill)
     if waic_ddof is not None:
         lppd, pw = torch.empty((rows,), dtype=torch.float32, device=dev), torch.empty((rows,), dtype=torch.float32, device=dev)
         if rows > 0:
@@ -141,10 +146,11 @@ def _run(x, rows, d, latent, ld, k, n, want_ll, want_lppd, want_resp, waic_ddof=
     return lppd, resp
 
 
-def _from_samples(model, samples, obs, want_ll, want_lppd, want_resp, waic_ddof=None):
+def _from_samples(model, samples, obs, want_ll, want_lppd, want_resp, waic_ddof=None, loo_slab_bytes=None):
     _check_model(model)
     n, k, d = _sample_shapes(samples)
     _check_ddof(n, waic_ddof)
+    chunk = _loo_chunk(n, loo_slab_bytes)
     if obs is None:
         raise ValueError("obs is required")
     rows, d_obs = M._rows_of(obs, "obs")
@@ -157,7 +163,7 @@ def _from_samples(model, samples, obs, want_ll, want_lppd, want_resp, waic_ddof=
     with torch.cuda.device(dev):
         x = M._f32(obs, "obs")
         latent, ld = _pack(samples, n, k, d)
-        return _run(x, rows, d, latent, ld, k, n, want_ll, want_lppd, want_resp, waic_ddof)
+        return _run(x, rows, d, latent, ld, k, n, want_ll, want_lppd, want_resp, waic_ddof, chunk)
 
 
 def log_likelihood(model, posterior_samples, obs):
@@ -177,7 +183,7 @@ def responsibilities(model, posterior_samples, obs):
     return _from_samples(model, posterior_samples, obs, False, False, True)[1]
 
 
-def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, want_resp, waic_ddof=None):
+def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, want_resp, waic_ddof=None, loo_slab_bytes=None):
     _check_model(model)
     if not isinstance(guide, GaussianMixtureGuide):
         raise TypeError(f"mixture density: guide must be a GaussianMixtureGuide, got {type(guide).__name__}")
@@ -187,6 +193,7 @@ def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, 
     if nn > 2 ** 31 - 1:
         raise ValueError("n <= 2^31 - 1")
     _check_ddof(nn, waic_ddof)
+    chunk = _loo_chunk(nn, loo_slab_bytes)
     k, rows, d = MX._shape(model, model_args, kwargs)
     a = list(model_args) + [None] * (4 - len(model_args))
     obs = a[1] if a[1] is not None else kwargs.get("obs")
@@ -210,7 +217,7 @@ def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, 
         obs_keys = torch.empty((nn, 2), dtype=torch.uint32, device=dev)   # (written by the launch, not used here)
         check(lib.d3p_predict_gmm_draws(stream_ptr(), ptr(key), nn, 1, 1, k, d, ptr(alpha_log), ptr(mus_loc),
                                         float(model.prior_mu_scale), None, None, None, ptr(latent), ptr(obs_keys)))
-        return _run(x, rows, d, latent, ld, k, nn, False, want_lppd, want_resp, waic_ddof)
+        return _run(x, rows, d, latent, ld, k, nn, False, want_lppd, want_resp, waic_ddof, chunk)
 
 
 def posterior_log_predictive_density(rng_key, n, model, model_args, guide, params, **kwargs):

@@ -20,6 +20,9 @@ the same draws, beside the assignment accuracy above.
 
 --waic (off by default; d3p_amd.criteria) adds one line: elpd_waic +- its standard error and p_waic of the fitted mixture on the
 training split, under --posterior-draws draws from the fitted guide.
+
+--loo (off by default; d3p_amd.criteria) adds one line: the PSIS-LOO elpd_loo +- its standard error, p_loo and the number of points
+whose Pareto shape lies above the threshold, on the same split and draws.
 """
 import argparse
 import itertools
@@ -105,6 +108,14 @@ def waic_report(X, params, k, num_draws, seed=4322):
     return criteria.posterior_waic(threefry.PRNGKey(seed), num_draws, model, (k, X), GaussianMixtureGuide(model), params)
 
 
+def loo_report(X, params, k, num_draws, seed=4322):
+    """The LOOResult of the fitted mixture on X on waic_report's draws."""
+    from d3p_amd import criteria
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    return criteria.posterior_loo(threefry.PRNGKey(seed), num_draws, model, (k, X), GaussianMixtureGuide(model), params)
+
+
 def main(args):
     L.require_device()
     N, k, d = args.num_samples, args.num_components, args.dimensions
@@ -174,6 +185,10 @@ def main(args):
         res = waic_report(X_train, params, k, args.posterior_draws)
         print("WAIC ({} points, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
             res.n_rows, res.n_draws, float(res.elpd_waic), float(res.se), float(res.p_waic)))
+    if getattr(args, "loo", False):
+        res = loo_report(X_train, params, k, args.posterior_draws)
+        print("PSIS-LOO ({} points, {} posterior draws): elpd_loo {:.2f} +- {:.2f}, p_loo {:.2f}, pareto k above {:.2f} in {} points".format(
+            res.n_rows, res.n_draws, float(res.elpd_loo), float(res.se), float(res.p_loo), res.k_threshold, int(res.n_high_k)))
     return acc, pis, modes
 
 
@@ -193,7 +208,9 @@ def parse_args(argv=None):
                         help="'posterior': score with the per-component log-posterior, as the reference does")
     parser.add_argument('--held-out-density', action='store_true',
                         help='report the held-out log predictive density and the soft-assignment accuracy under the fitted posterior')
-    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --held-out-density and --waic')
+    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --held-out-density, --waic and --loo')
+    parser.add_argument('--loo', action='store_true',
+                        help='report the PSIS-LOO elpd_loo, its standard error, p_loo and the count of high Pareto shapes')
     parser.add_argument('--waic', action='store_true', help='report elpd_waic, its standard error and p_waic of the fitted mixture')
     return parser.parse_args(argv)
 

@@ -8,6 +8,9 @@ from the weights that generated the data.
 --waic (off by default; d3p_amd.criteria) adds three lines: elpd_waic +- its standard error and p_waic of the trained model under
 --posterior-draws draws from the fitted guide, the same for a LinearRegression trained on the same counts with the same settings, and
 the paired comparison of the two.
+
+--loo (off by default; d3p_amd.criteria) adds the same three lines for PSIS-LOO: elpd_loo +- its standard error, p_loo and the number
+of rows whose Pareto shape lies above the threshold (where the estimate is not to be trusted), for both models, and their comparison.
 """
 import argparse
 import os
@@ -57,6 +60,18 @@ def _waic_line(name, res):
         name, res.n_rows, res.n_draws, float(res.elpd_waic), float(res.se), float(res.p_waic))
 
 
+def loo_report(model, svi, state, X, y, num_draws, seed=2):
+    """The LOOResult (pointwise arrays kept, for compare) on waic_report's draws."""
+    from d3p_amd import criteria
+    import d3p_amd.random.debug as jax_random
+    return criteria.posterior_loo(jax_random.PRNGKey(seed), num_draws, model, (X, y), svi.guide, svi.get_params(state), pointwise=True)
+
+
+def _loo_line(name, res):
+    return "{} PSIS-LOO ({} rows, {} posterior draws): elpd_loo {:.2f} +- {:.2f}, p_loo {:.2f}, pareto k above {:.2f} in {} rows".format(
+        name, res.n_rows, res.n_draws, float(res.elpd_loo), float(res.se), float(res.p_loo), res.k_threshold, int(res.n_high_k))
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
@@ -81,16 +96,29 @@ def main(args):
     pred = posterior_predictive_samples(jax_random.PRNGKey(1), 100, model, (X,), svi.guide, svi.get_params(state))["obs"].double()
     print("posterior predictive check (100 draws): observed mean {:.4f}, variance {:.4f};  predictive mean {:.4f}, variance {:.4f}".format(
         float(y.mean()), float(y.var()), float(pred.mean()), float(pred.var(dim=1).mean())))
+    linear_fit = None
     if getattr(args, "waic", False):
         from d3p_amd import criteria
         draws = getattr(args, "posterior_draws", 100)
         poisson = waic_report(model, svi, state, X, y, draws)
         print(_waic_line("Poisson", poisson))
         linear_model = LinearRegression(d, prior_scale=1.0, intercept=True)
-        linear = waic_report(linear_model, *fit(linear_model, X, y, args), X, y, draws)
+        linear_fit = fit(linear_model, X, y, args)
+        linear = waic_report(linear_model, *linear_fit, X, y, draws)
         print(_waic_line("linear", linear))
         diff = criteria.compare(poisson, linear)
         print("Poisson against linear on the same counts: elpd_diff {:.2f} +- {:.2f}".format(float(diff.elpd_diff), float(diff.se_diff)))
+    if getattr(args, "loo", False):
+        from d3p_amd import criteria
+        draws = getattr(args, "posterior_draws", 100)
+        poisson = loo_report(model, svi, state, X, y, draws)
+        print(_loo_line("Poisson", poisson))
+        linear_model = LinearRegression(d, prior_scale=1.0, intercept=True)
+        linear = loo_report(linear_model, *(linear_fit or fit(linear_model, X, y, args)), X, y, draws)
+        print(_loo_line("linear", linear))
+        diff = criteria.compare(poisson, linear)
+        print("Poisson against linear on the same counts (PSIS-LOO): elpd_diff {:.2f} +- {:.2f}".format(float(diff.elpd_diff),
+                                                                                                        float(diff.se_diff)))
     return first, last, err0, err
 
 
@@ -105,5 +133,7 @@ if __name__ == "__main__":
     parser.add_argument('-N', '--num-samples', default=10000, type=int, help='data samples count')
     parser.add_argument('--waic', action='store_true',
                         help='report WAIC of the trained model, of a linear regression on the same counts, and their comparison')
-    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --waic')
+    parser.add_argument('--loo', action='store_true',
+                        help='report PSIS-LOO of the trained model, of a linear regression on the same counts, and their comparison')
+    parser.add_argument('--posterior-draws', default=100, type=int, help='posterior draws for --waic and --loo')
     main(parser.parse_args())

@@ -878,6 +878,26 @@ int d3p_loglik_waic(void* stream, const d3p_logreg_model* model, const float* X_
 int d3p_gmm_loglik_waic(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
                         int32_t k, uint32_t n, uint32_t ddof, float* lppd_rows_dev, float* pwaic_rows_dev);
 
+/* PSIS-LOO (Pareto-smoothed importance-sampling leave-one-out; Vehtari, Gelman & Gabry 2017, section 2.1 and appendix) per row of a
+ * draws x rows log-likelihood matrix (d3p_amd/criteria.py, d3p_psis.hip); added symbol, ABI 9 unchanged.
+ * ll_dev[s * ll_ld + r] is the float32 matrix d3p_loglik_rows / d3p_gmm_loglik_rows write; the entry knows nothing of the model.  Per
+ * row, in float64 after the loads, one rounding to float32 per output:
+ *   x[s] = min_s ll - ll[s]                                    the log importance ratios, the largest shifted to 0
+ *   lppd_rows_dev[r] = logsumexp_s ll[s, r] - log n
+ *   M = ceil(min(n / 5, 3 sqrt n));  cut = max((M+1)-th largest x, log DBL_MIN);  the tail is the T <= M draws with x > cut (strictly)
+ *   the tail, ascending, with e_j = exp(x_j) - exp(cut), is fitted by a generalised Pareto distribution (Zhang & Stephens 2009: m = 30 +
+ *   floor(sqrt T) candidates, their profile-likelihood weights, those below 10 DBL_EPSILON dropped); k is regularised to (T k + 5) /
+ *   (T + 10) and tail element j is replaced by min(0, log(exp(cut) + sigma expm1(-k log1p(-(j - 0.5) / T)) / k))
+ *   elpd_rows_dev[r] = logsumexp_s (x[s] + ll[s]) - logsumexp_s x[s];   k_rows_dev[r] = the regularised k
+ * T <= 4 (n = 1 and all draws equal among them), a non-finite k or sigma, or sigma <= 0: the raw ratios stand and k = +inf.  The
+ * selection is exact on the float32 values (ties at the cut shorten the tail).  A draw with ll = -inf: elpd = -inf and k = +inf, lppd
+ * finite unless every draw is -inf.  A NaN in the column: all three outputs NaN.  ll = +inf: elpd and k NaN, lppd +inf.
+ * Deterministic: no floating-point atomics, fixed summation orders, and a row's result does not depend on the other rows of the launch.
+ * 1 <= n <= 65535 (M <= 768), ll_ld >= rows, every pointer non-null, aligned to 4 bytes and device memory, else D3P_E_INVALID_ARG
+ * before any launch; rows > 32 (2^31 - 1): D3P_E_UNSUPPORTED; rows == 0: D3P_OK, no launch. */
+int d3p_psis_loo(void* stream, const float* ll_dev, int64_t ll_ld, uint32_t n, uint64_t rows, float* elpd_rows_dev, float* lppd_rows_dev,
+                 float* k_rows_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

@@ -7,18 +7,23 @@ PyTorch is used for device memory, streams and torch.distributed only.
 """
 from .version import __version__  # noqa: F401
 
-__all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "loo", "posterior_loo", "LOOResult"]
+__all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "loo", "posterior_loo", "LOOResult",
+           "diagnostics", "log_likelihood_total", "log_joint", "guide_diagnostic", "GuideDiagnostic"]
 
 
 def __getattr__(name):
     # d3p_amd.infer_util (log_likelihood, log predictive densities), d3p_amd.prediction (posterior predictive mean and variance) and
     # d3p_amd.predictive (predictive sampling for the regression family) and d3p_amd.mixture (predictive sampling and cluster
     # assignment for the mixture model) and d3p_amd.mixture_density (log predictive density and responsibilities of the mixture model)
-    # and d3p_amd.criteria (waic, posterior_waic, compare) without making `import d3p_amd` import torch
-    if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria"):
+    # and d3p_amd.criteria (waic, posterior_waic, compare) and d3p_amd.diagnostics (whole-table log joint, ELBO and the Pareto k of a
+    # guide) without making `import d3p_amd` import torch
+    if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "diagnostics"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("loo", "posterior_loo", "LOOResult"):   # PSIS-LOO (d3p_amd.criteria), under the same lazy rule
         import importlib
         return getattr(importlib.import_module(".criteria", __name__), name)
+    if name in ("log_likelihood_total", "log_joint", "guide_diagnostic", "GuideDiagnostic"):   # d3p_amd.diagnostics, likewise
+        import importlib
+        return getattr(importlib.import_module(".diagnostics", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

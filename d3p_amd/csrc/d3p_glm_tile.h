@@ -1,5 +1,6 @@
 // The draws x rows product tile of the regression kernels: t[s, r] = X[r] . w_s on a workgroup tile of 128 draws x 128 rows, used by
 //   k_predict_logreg (d3p_predict.hip)   k_loglik (d3p_loglik.hip)   k_moments (d3p_moments.hip)   k_predict_glm (d3p_predict_glm.hip)
+//   k_draw_sums (d3p_draw_sums.hip)
 // which differ only in what they do with t.  One copy of the staging, the matrix-core loop and the accumulator scatter, and one
 // copy of the argument checks their C entries share (measurements: docs/experiments_glm_tile.md).
 //
@@ -100,6 +101,30 @@ __device__ __forceinline__ void tile_scatter(float* L, const tile_f16v& h0, cons
         p[0] = h0[v];
         p[32] = h1[v];
     }
+}
+
+// ---- the pointwise log-likelihood of the forms that reduce it: k_loglik (d3p_loglik.hip) and k_draw_sums (d3p_draw_sums.hip) ---------
+// log p(y | t): the `ll` of glm_link (d3p_logreg_kernel.h) without its gradient half, same expressions and rounding order for the
+// linear and the Poisson family; c = glm_label_const's value (LINREG: ll_const, POISSON: lgammaf(y + 1)), once per row.  No clamps:
+// exp(t) = inf gives -inf, what float32 jax computes.
+// LOGREG differs from glm_link's y t - softplus(t) ON PURPOSE: that form cancels where the label is predicted well (y = 1, t = 4:
+// 4 - 4.018, half an ulp of 4 against a result of 0.018), which a loss summed over a batch never sees and a per-element bound does.
+// Here ll = -(max(t, 0) - y t + log1p(exp(-|t|))) with max(t, 0) - y t taken as (1 - y) t (t >= 0) or -y t (t < 0): exact for
+// y in {0, 1} (-softplus(-t) resp. -softplus(t)), and numpyro's BernoulliLogits.log_prob for any y in [0, 1].
+template <int FAMILY>
+__device__ __forceinline__ float loglik_value(float t, float y, float nh, float c)
+{
+#pragma clang fp contract(off)
+    if (FAMILY == D3P_FAMILY_LINREG) {
+        const float r = t - y;
+        return (nh * r) * r - c;
+    }
+    if (FAMILY == D3P_FAMILY_POISSON) {
+        const float mu = expf(t);
+        return (y * t - mu) - c;
+    }
+    const float lin = t >= 0.0f ? (1.0f - y) * t : -(y * t);
+    return -(lin + log1pf(expf(-fabsf(t))));
 }
 
 // ---- host: the argument checks of the C entries that take a model and a latent buffer (d3p_loglik_rows / _lppd, d3p_predict_moments,

@@ -46,28 +46,7 @@ struct LoglikArgs {
     uint32_t ddof;   // WAIC form: 0 or 1
 };
 
-// log p(y | t): the `ll` of glm_link (d3p_logreg_kernel.h) without its gradient half, same expressions and rounding order for the
-// linear and the Poisson family; c = glm_label_const's value (LINREG: ll_const, POISSON: lgammaf(y + 1)), once per row.  No clamps:
-// exp(t) = inf gives -inf, what float32 jax computes.
-// LOGREG differs from glm_link's y t - softplus(t) ON PURPOSE: that form cancels where the label is predicted well (y = 1, t = 4:
-// 4 - 4.018, half an ulp of 4 against a result of 0.018), which a loss summed over a batch never sees and a per-element bound does.
-// Here ll = -(max(t, 0) - y t + log1p(exp(-|t|))) with max(t, 0) - y t taken as (1 - y) t (t >= 0) or -y t (t < 0): exact for
-// y in {0, 1} (-softplus(-t) resp. -softplus(t)), and numpyro's BernoulliLogits.log_prob for any y in [0, 1].
-template <int FAMILY>
-__device__ __forceinline__ float loglik_value(float t, float y, float nh, float c)
-{
-#pragma clang fp contract(off)
-    if (FAMILY == D3P_FAMILY_LINREG) {
-        const float r = t - y;
-        return (nh * r) * r - c;
-    }
-    if (FAMILY == D3P_FAMILY_POISSON) {
-        const float mu = expf(t);
-        return (y * t - mu) - c;
-    }
-    const float lin = t >= 0.0f ? (1.0f - y) * t : -(y * t);
-    return -(lin + log1pf(expf(-fabsf(t))));
-}
+// (loglik_value<FAMILY>, log p(y | t), is in d3p_glm_tile.h: the draw-sums form of d3p_draw_sums.hip evaluates the same text)
 
 #define D3P_LOGLIK_ROWS 0
 #define D3P_LOGLIK_LPPD 1

@@ -4,6 +4,10 @@ with AutoDiagonalNormal, training with the device-resident loop (`run_steps`), t
 from the weights that generated the data.
 
     w ~ Normal(0, 1)^d, intercept ~ Normal(0, 1);  ys ~ Normal(xs @ w + intercept, obs_scale)
+
+--guide-diagnostic [N_DRAWS] (off by default; d3p_amd.diagnostics) adds one line after training: the full-data ELBO +- its standard
+error, the importance-sampling estimate of the log evidence, the Pareto k of the guide's importance ratios against its threshold and
+their effective sample size (Yao et al. 2018: is the trained guide a usable approximation of the posterior?).
 """
 import argparse
 import os
@@ -27,6 +31,17 @@ def create_toy_data(N, d, seed=123, obs_scale=0.5):
     X = torch.randn(N, d, generator=g, device="cuda")
     y = X @ w_true + obs_scale * torch.randn(N, generator=g, device="cuda")
     return X.contiguous(), y.to(torch.float32).contiguous(), w_true
+
+
+def guide_diagnostic_report(model, svi, state, X, y, num_draws, seed=3):
+    """The guide diagnostic line (d3p_amd.diagnostics): ELBO, importance-sampling evidence, Pareto k and effective sample size of
+    num_draws draws from the trained guide on the whole table."""
+    from d3p_amd import diagnostics
+    import d3p_amd.random.debug as jax_random
+    res = diagnostics.guide_diagnostic(jax_random.PRNGKey(seed), num_draws, model, (X, y), svi.guide, svi.get_params(state))
+    return ("guide diagnostic ({} rows, {} draws): elbo {:.2f} +- {:.2f}, log_evidence_is {:.2f}, pareto k {:.2f} (threshold {:.2f}), "
+            "ess {:.1f}").format(res.n_rows, res.n_draws, float(res.elbo), float(res.elbo_se), float(res.log_evidence_is),
+                                 float(res.pareto_k), res.k_threshold, float(res.ess))
 
 
 def main(args):
@@ -53,6 +68,8 @@ def main(args):
     pred = posterior_predictive_samples(jax_random.PRNGKey(1), 100, model, (X,), svi.guide, svi.get_params(state))["obs"].double()
     print("posterior predictive check (100 draws): observed mean {:.4f}, variance {:.4f};  predictive mean {:.4f}, variance {:.4f}".format(
         float(y.mean()), float(y.var()), float(pred.mean()), float(pred.var(dim=1).mean())))
+    if getattr(args, "guide_diagnostic", None) is not None:
+        print(guide_diagnostic_report(model, svi, state, X, y, args.guide_diagnostic))
     return first, last, err0, err
 
 
@@ -66,4 +83,7 @@ if __name__ == "__main__":
     parser.add_argument('-d', '--dimensions', default=4, type=int, help='data dimension')
     parser.add_argument('-N', '--num-samples', default=10000, type=int, help='data samples count')
     parser.add_argument('--obs-scale', default=0.5, type=float, help='standard deviation of the observation noise')
+    parser.add_argument('--guide-diagnostic', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, report the ELBO, the importance-sampling evidence, the Pareto k and the effective sample '
+                             'size of N_DRAWS (default 100) draws from the guide on the whole table')
     main(parser.parse_args())

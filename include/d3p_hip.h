@@ -898,6 +898,30 @@ int d3p_gmm_loglik_waic(void* stream, const float* obs_dev, uint64_t rows, int32
 int d3p_psis_loo(void* stream, const float* ll_dev, int64_t ll_ld, uint32_t n, uint64_t rows, float* elpd_rows_dev, float* lppd_rows_dev,
                  float* k_rows_dev);
 
+/* Per-draw sums of the pointwise log-likelihood over a whole table (d3p_amd/diagnostics.py: full-data log joint, ELBO and the Pareto k
+ * of a guide's importance ratios; d3p_draw_sums.hip); added symbols, ABI 9 and d3p_logreg_model unchanged.  With ll[s, r]
+ * of d3p_loglik_rows, bit for bit (D3P_FAMILY_LOGREG, LINREG and POISSON):
+ *   out_draws_dev[s] = sum_{r < rows} ll[s, r]                       n float64; IEEE float64 additions of the float32 values
+ * without the n x rows matrix.  Nothing is clamped: a draw with a -inf element (a Poisson rate that overflows float32) gives -inf for
+ * that draw only, a NaN gives NaN.  Rows beyond `rows` and draws beyond n contribute nothing.
+ * Summation order, fixed (no floating-point atomics; the output bits are identical between calls and a function of the arguments
+ * only, not of the device): the table is cut into tiles of 128 rows and those into strips of `per` consecutive tiles,
+ *   tiles = ceil(rows / 128);  per = ceil(tiles / 512);  strips = ceil(tiles / per) <= 512          (a function of rows alone)
+ * A tile's rows fall into four quarters q = 0..3 of 32 consecutive rows.  For draw s: quarter sum (strip, q) = the elements of quarter
+ * q of every tile of the strip, tiles ascending, rows ascending within a tile, added one by one from 0.0; strip partial = ((q0 + q1) +
+ * q2) + q3, kept in the workspace as float64 [strip][n]; out[s] = the strips' partials added in ascending strip order from strip 0's,
+ * by a second small launch on the same stream.
+ * d3p_loglik_draw_sums_workspace(rows, n) = 8 strips n bytes (0 for rows == 0).  Arguments, limits and errors are d3p_loglik_rows' (the
+ * same checks in the same order: D3P_E_UNSUPPORTED before any launch for D3P_FAMILY_GAUSS_MEAN and D3P_GUIDE_EXP_SITES;
+ * D3P_E_INVALID_ARG for a null X / y / latent / out, n < 1, a latent layout that does not fit, b_col >= 0 without model->intercept or
+ * the reverse), then, also before any launch, D3P_E_INVALID_ARG for an out that is not aligned to 8 bytes and for a workspace that is
+ * null, not aligned to 8 bytes, not device memory or smaller than the size above.  rows == 0: out is filled with 0.0 (a memset, no
+ * launch; the workspace is not read and may be null) and D3P_OK. */
+size_t d3p_loglik_draw_sums_workspace(uint64_t rows, uint32_t n);
+int d3p_loglik_draw_sums(void* stream, const d3p_logreg_model* model, const float* X_dev, const float* y_dev, uint64_t rows,
+                         const float* latent_dev, int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, double* out_draws_dev,
+                         void* workspace_dev, size_t workspace_bytes);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

@@ -276,6 +276,10 @@ SIGNATURES = {
     # symbols, ABI 9 unchanged
     "d3p_gmm_loglik_rows": (C.c_int, [_V, _V, _U64, _I32, _V, C.c_int64, _I32, _U32, _V]),
     "d3p_gmm_loglik_reduce": (C.c_int, [_V, _V, _U64, _I32, _V, C.c_int64, _I32, _U32, _V, _V]),
+    # per-draw float64 sums of the mixture's pointwise log-likelihood over a whole table (d3p_amd/mixture_diagnostics.py): added symbols,
+    # ABI 9 unchanged
+    "d3p_gmm_loglik_draw_sums_workspace": (_SZ, [_U64, _I32, _I32, _U32]),
+    "d3p_gmm_loglik_draw_sums": (C.c_int, [_V, _V, _U64, _I32, _V, C.c_int64, _I32, _U32, _V, _V, _SZ]),
     # multi-particle ELBO (Trace_ELBO(num_particles=K)): added symbols, ABI 9 unchanged
     "d3p_logreg_px_grads_particles_workspace": (_SZ, [_PM, _U32, _U32]),
     "d3p_logreg_particles_max_latent": (C.c_int, [C.c_int]),

@@ -39,6 +39,22 @@
 // in float64, rounded to float32 once; every draw of a row equal gives exactly 0.  Special values as k_loglik's WAIC form: ll = -inf
 // is not added but remembered, and such a row gets pwaic = +inf (also when every draw is -inf, where lppd = -inf); a NaN ll makes
 // both outputs NaN; ll = +inf (not reached from finite inputs) is not added either and makes pwaic NaN.
+//
+// The draw-sums form (REDUCE = 3; d3p_amd/mixture_diagnostics.py): out[s] = sum_{r < rows} ll[s, r] as float64,
+// every other reduction here runs over the draws, once per row; this one runs over the rows, once per draw.  ll[s, r] is bit for bit
+// the float32 value the rows form writes: the same instantiated text up to the line that stores it.  Grid: the table's row tiles are
+// cut into strips of `per` consecutive tiles,
+//   tiles = ceil(rows / 64);  per = ceil(tiles / 2048);  strips = ceil(tiles / per)  (<= 2048)
+// a function of rows alone, as d3p_draw_sums.hip's.  A workgroup walks the tiles of its strip in ascending order and, per tile, all n
+// draws exactly as the other forms do (the same W, the same staging).  Summation order of out[s], fixed:
+//   tile sum   = the 64 lanes' (double)ll in the xor butterfly v = v + v[lane ^ off], off = 1, 2, 4, 8, 16, 32, i.e. the balanced binary
+//                tree over the rows of the tile in index order; a row past the end is exactly 0.0 (its value, of a staged zero row, is
+//                computed and dropped);
+//   strip sum  = the tile sums of the strip added one by one in ascending tile order, from 0.0, kept at ws[strip][s] by the lane
+//                that owns (strip, s) -- lane 0 of wave s % W of workgroup `strip`, always the same -- with a plain load, add and store;
+//   out[s]     = the strip sums added in ascending strip order, starting from strip 0's (k_gmm_draw_sums_merge, a second launch).
+// No floating-point atomics, no arrival order; a draw's sum does not depend on the other draws of the launch.  Nothing is clamped:
+// a draw with ll = -inf in some row sums to -inf, a NaN row of obs makes every draw NaN, a NaN in a draw's latents that draw only.
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -52,6 +68,7 @@ namespace d3p {
 #define D3P_GD_ROW_TILE 64
 #define D3P_GD_DRAW_TILE 4
 #define D3P_GD_LDS_MAX 163840   // 160 KiB: a compute unit's LDS
+#define D3P_GD_MAX_STRIPS 2048  // draw-sums form: workgroups of one launch (several per compute unit: the kernel is latency-bound)
 
 struct GmmDensityArgs {
     const float* obs;
@@ -64,6 +81,9 @@ struct GmmDensityArgs {
     float* resp;   // reduced form, nullable
     float* pwaic;    // WAIC form (with lppd; both required)
     uint32_t ddof;   // WAIC form: 0 or 1
+    double* part;    // draw-sums form: [strip][n], a strip's running sums (the workspace)
+    uint32_t tiles;  //                 row tiles of the table
+    uint32_t per;    //                 row tiles per strip
 };
 
 // floats of LDS in front of the waves' latent copies (the row tile, rounded up to a float2 boundary) and per wave
@@ -82,15 +102,12 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
     float2* st = reinterpret_cast<float2*>(mine);   // [j d + c] = (mus, 1 / sigs)
     float* lg = mine;                               // [c k + j] = logf(sigs): the same floats, before the pairs are written
     float* cj = mine + 2 * kd;                      // [j] = C_j
-    const uint64_t r0 = (uint64_t)blockIdx.x * D3P_GD_ROW_TILE;
-    const uint32_t left = g.rows - (uint32_t)r0;
-    const uint32_t total = (left < D3P_GD_ROW_TILE ? left : D3P_GD_ROW_TILE) * (uint32_t)d;
-    for (uint32_t e = tid; e < (uint32_t)(D3P_GD_ROW_TILE * d); e += blockDim.x) {
-        const uint32_t row = e / (uint32_t)d, c = e - row * (uint32_t)d;
-        xs[row * ldx + c] = e < total ? g.obs[r0 * (uint64_t)d + e] : 0.f;   // (rows past the end: zeros, never written out)
-    }
-    const bool live = r0 + lane < g.rows;
-    const float* xrow = xs + lane * ldx;
+    // REDUCE == 3 walks the row tiles of its strip in ascending order; every other form owns the one tile of its workgroup (the loop's
+    // condition is false at compile time and its body, left at its indentation, is the text those forms always had)
+    const uint32_t tile_lo = REDUCE == 3 ? blockIdx.x * g.per : blockIdx.x;
+    const uint32_t tile_hi = REDUCE == 3 ? (tile_lo + g.per < g.tiles ? tile_lo + g.per : g.tiles) : tile_lo + 1;
+    uint32_t tile = tile_lo;
+    bool live;
     float run_m = -INFINITY;
     double run_s = 0.0;
     double racc[KMAX];
@@ -99,6 +116,16 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
     double v1 = 0.0, v2 = 0.0;        // WAIC form: sum (ll - vc), sum (ll - vc)^2
     float vc = 0.f;                   //            the shift: this wave's first finite ll of the row
     uint32_t vcnt = 0, vflags = 0;    //            values in the sums; D3P_SHIFTED_* flags
+    do {
+    const uint64_t r0 = (uint64_t)tile * D3P_GD_ROW_TILE;
+    const uint32_t left = g.rows - (uint32_t)r0;
+    const uint32_t total = (left < D3P_GD_ROW_TILE ? left : D3P_GD_ROW_TILE) * (uint32_t)d;
+    for (uint32_t e = tid; e < (uint32_t)(D3P_GD_ROW_TILE * d); e += blockDim.x) {
+        const uint32_t row = e / (uint32_t)d, c = e - row * (uint32_t)d;
+        xs[row * ldx + c] = e < total ? g.obs[r0 * (uint64_t)d + e] : 0.f;   // (rows past the end: zeros, never written out)
+    }
+    live = r0 + lane < g.rows;
+    const float* xrow = xs + lane * ldx;
     // every wave runs the same number of passes (the barriers are workgroup-wide); a wave without a draw in the last pass idles
     const uint32_t passes = (g.n + (uint32_t)W - 1) / (uint32_t)W;
     for (uint32_t it = 0; it < passes; ++it) {
@@ -123,7 +150,11 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
                 for (int c = lane; c < d; c += 64) st[j * d + c] = make_float2(row[k + j * d + c], 1.0f / row[k + kd + j * d + c]);
         }
         __syncthreads();
-        if (!(active && live)) continue;   // (no barrier below this line inside the loop)
+        // (no barrier below this line inside the loop; the draw-sums form keeps the lanes past the end for its butterfly: their rows
+        // are staged zeros, their values are computed and dropped)
+        if (REDUCE == 3 ? !active : !(active && live)) continue;
+        double prev = 0.0;   // draw-sums form: the strip's running sum of this draw, asked for before the evaluation that hides the load
+        if (REDUCE == 3 && lane == 0 && tile != tile_lo) prev = g.part[(size_t)blockIdx.x * g.n + s];
         float q[KMAX];
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) q[j] = 0.f;
@@ -172,6 +203,14 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
         }
         if (!REDUCE) {
             g.ll[(size_t)s * g.rows + (r0 + lane)] = ll;
+        } else if (REDUCE == 3) {
+            // the tile's 64 values of this draw in a fixed tree: a lane past the end gives exactly 0.0; after the six steps every lane
+            // holds the same float64 sum (IEEE addition commutes).  Lane 0 of the wave that owns the draw -- always this one -- adds
+            // it to the strip's running sum by a plain load, add and store in program order.
+            double v = live ? (double)ll : 0.0;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off);
+            if (lane == 0) g.part[(size_t)blockIdx.x * g.n + s] = prev + v;
         } else {
             // k_loglik's running (max, sum): one expf per draw, the sum in float64
             if (ll > run_m) {
@@ -188,7 +227,9 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
             if (REDUCE == 2) shifted_add(ll, vc, v1, v2, vcnt, vflags);
         }
     }
-    if (REDUCE) {
+    if (REDUCE == 3) __syncthreads();   // the tile's rows are read before the next tile overwrites them
+    } while (REDUCE == 3 && ++tile < tile_hi);
+    if (REDUCE == 1 || REDUCE == 2) {
         // waves 1 .. W - 1 hand their accumulators to wave 0, one after the other; the row tile and the latents are no longer needed
         double* Rs = reinterpret_cast<double*>(lds);   // [j][lane]
         double* Ss = Rs + (REDUCE == 2 ? 0 : (size_t)k * 64);   // [lane] (the WAIC form has no Rs)
@@ -235,7 +276,7 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
             __syncthreads();
         }
         if (wave == 0 && live) {
-            const uint64_t r = r0 + lane;
+            const uint64_t r = (uint64_t)tile_lo * D3P_GD_ROW_TILE + lane;
             if (g.lppd)
                 g.lppd[r] = (run_m == -INFINITY && run_s == 0.0) ? -INFINITY : (float)(((double)run_m + log(run_s)) - log((double)g.n));
             if (REDUCE == 1 && g.resp) {
@@ -269,12 +310,25 @@ static int gd_dynamic_lds(const void* fn, const char* what)
     return D3P_OK;
 }
 
+// four waves split the draws where their four latent copies fit beside the row tile, otherwise two: a function of (k, d) alone.
+// Returns the bytes of LDS of the staging.
+static size_t gd_waves(int k, int d, int* W)
+{
+    *W = D3P_GD_DRAW_TILE;
+    size_t lds = sizeof(float) * ((size_t)gd_tile_floats(d) + (size_t)*W * gd_wave_floats(k, d));
+    if (lds > D3P_GD_LDS_MAX) {
+        *W = 2;
+        lds = sizeof(float) * ((size_t)gd_tile_floats(d) + (size_t)*W * gd_wave_floats(k, d));
+    }
+    return lds;
+}
+
 template <int KMAX, int REDUCE>
-static int gd_launch(const char* what, hipStream_t s, const GmmDensityArgs& g, int W, size_t lds)
+static int gd_launch(const char* what, hipStream_t s, const GmmDensityArgs& g, int W, size_t lds, uint32_t grid)
 {
     const void* fn = reinterpret_cast<const void*>(&k_gmm_density<KMAX, REDUCE>);
     if (int rc = gd_dynamic_lds(fn, what)) return rc;
-    hipLaunchKernelGGL((k_gmm_density<KMAX, REDUCE>), dim3(cdiv(g.rows, D3P_GD_ROW_TILE)), dim3(64 * W), lds, s, g);
+    hipLaunchKernelGGL((k_gmm_density<KMAX, REDUCE>), dim3(grid), dim3(64 * W), lds, s, g);
     return check_launch(what);
 }
 
@@ -301,24 +355,38 @@ static int gd_entry(const char* what, void* stream, const float* obs, uint64_t r
     if (!is_device_ptr(obs) || !is_device_ptr(latent) || (ll && !is_device_ptr(ll)) || (lppd && !is_device_ptr(lppd)) ||
         (resp && !is_device_ptr(resp)) || (pwaic && !is_device_ptr(pwaic)))
         return fail(D3P_E_INVALID_ARG, "%s: every pointer must be device memory", what);
-    GmmDensityArgs g;
+    GmmDensityArgs g = {};
     g.obs = obs; g.lat = latent; g.ld = ld; g.rows = (uint32_t)rows; g.n = n; g.k = k; g.d = d; g.ll = ll; g.lppd = lppd; g.resp = resp;
     g.pwaic = pwaic; g.ddof = ddof;
-    // four waves split the draws where their four latent copies fit beside the row tile, otherwise two: a function of (k, d) alone
     // (the WAIC form hands over the sum, the maximum, two shifted sums, the shift, the count and the flags per lane)
     const size_t combine = REDUCE == 2 ? (size_t)64 * (8 + 4 + 2 * 8 + 3 * 4) : REDUCE ? (size_t)64 * 8 * (k + 1) + 64 * 4 : 0;
-    int W = D3P_GD_DRAW_TILE;
-    size_t lds = sizeof(float) * ((size_t)gd_tile_floats(d) + (size_t)W * gd_wave_floats(k, d));
-    if (lds > D3P_GD_LDS_MAX) {
-        W = 2;
-        lds = sizeof(float) * ((size_t)gd_tile_floats(d) + (size_t)W * gd_wave_floats(k, d));
-    }
+    int W;
+    size_t lds = gd_waves(k, d, &W);
     if (lds < combine) lds = combine;
     if (lds > D3P_GD_LDS_MAX) return fail(D3P_E_UNSUPPORTED, "%s: %zu bytes of LDS needed (k = %d, d = %d)", what, lds, k, d);
     hipStream_t s = (hipStream_t)stream;
-    if (k <= 4) return gd_launch<4, REDUCE>(what, s, g, W, lds);
-    if (k <= 16) return gd_launch<16, REDUCE>(what, s, g, W, lds);
-    return gd_launch<32, REDUCE>(what, s, g, W, lds);
+    const uint32_t grid = cdiv(g.rows, D3P_GD_ROW_TILE);
+    if (k <= 4) return gd_launch<4, REDUCE>(what, s, g, W, lds, grid);
+    if (k <= 16) return gd_launch<16, REDUCE>(what, s, g, W, lds, grid);
+    return gd_launch<32, REDUCE>(what, s, g, W, lds, grid);
+}
+
+// the strip function of the draw-sums form (file comment): rows alone decide
+static inline void gd_strips(uint64_t rows, uint32_t* tiles, uint32_t* per, uint32_t* strips)
+{
+    *tiles = cdiv(rows, D3P_GD_ROW_TILE);
+    *per = *tiles ? cdiv(*tiles, D3P_GD_MAX_STRIPS) : 0;
+    *strips = *tiles ? cdiv(*tiles, *per) : 0;
+}
+
+// out[s] = the strips' sums of draw s in ascending strip order
+__global__ void __launch_bounds__(256) k_gmm_draw_sums_merge(const double* part, uint32_t strips, uint32_t n, double* out)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= n) return;
+    double a = part[s];
+    for (uint32_t t = 1; t < strips; ++t) a += part[(size_t)t * n + s];
+    out[s] = a;
 }
 
 }  // namespace d3p
@@ -344,6 +412,58 @@ int d3p_gmm_loglik_waic(void* stream, const float* obs_dev, uint64_t rows, int32
 {
     return gd_entry<2>("d3p_gmm_loglik_waic", stream, obs_dev, rows, d, latent_dev, latent_ld, k, n, nullptr, lppd_rows_dev, nullptr, pwaic_rows_dev,
                        ddof);
+}
+
+size_t d3p_gmm_loglik_draw_sums_workspace(uint64_t rows, int32_t d, int32_t k, uint32_t n)
+{
+    (void)d; (void)k;   // (the strips are a function of rows alone)
+    uint32_t tiles, per, strips;
+    gd_strips(rows, &tiles, &per, &strips);
+    return (size_t)strips * n * sizeof(double);
+}
+
+int d3p_gmm_loglik_draw_sums(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
+                             int32_t k, uint32_t n, double* out_dev, void* workspace_dev, size_t workspace_bytes)
+{
+    const char* what = "d3p_gmm_loglik_draw_sums";
+    // gd_entry's checks in its order, then the output's and the workspace's; all of them before any launch
+    if (!obs_dev || !latent_dev) return fail(D3P_E_INVALID_ARG, "%s: null obs / latent pointer", what);
+    if (!out_dev) return fail(D3P_E_INVALID_ARG, "%s: null output pointer", what);
+    if (!gd_aligned(obs_dev) || !gd_aligned(latent_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
+    if (k < 1 || d < 1) return fail(D3P_E_INVALID_ARG, "%s: k and d must be >= 1 (k = %d, d = %d)", what, k, d);
+    if (k > 32 || d > 256 || (k > 16 && d > 128))
+        return fail(D3P_E_UNSUPPORTED, "%s: supported shapes are k <= 16 with d <= 256 and k <= 32 with d <= 128 (k = %d, d = %d)", what, k, d);
+    if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
+    if (n > 0x7fffffffu) return fail(D3P_E_UNSUPPORTED, "%s: n <= 2^31 - 1", what);
+    if (latent_ld < (int64_t)k + 2 * (int64_t)k * d) return fail(D3P_E_INVALID_ARG, "%s: a latent row holds k + 2 k d values", what);
+    if (rows > 0xFFFFFFFFull || rows * (uint64_t)d > 0xFFFFFFFFull) return fail(D3P_E_UNSUPPORTED, "%s: rows d < 2^32", what);
+    if ((uintptr_t)out_dev % sizeof(double)) return fail(D3P_E_INVALID_ARG, "%s: out must be aligned to 8 bytes", what);
+    hipStream_t s = (hipStream_t)stream;
+    if (rows == 0) {   // the empty sum, without a launch
+        if (!is_device_ptr(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: out must be device memory", what);
+        D3P_HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)n * sizeof(double), s));
+        return D3P_OK;
+    }
+    if (!is_device_ptr(obs_dev) || !is_device_ptr(latent_dev) || !is_device_ptr(out_dev))
+        return fail(D3P_E_INVALID_ARG, "%s: every pointer must be device memory", what);
+    GmmDensityArgs g = {};
+    uint32_t strips;
+    gd_strips(rows, &g.tiles, &g.per, &strips);
+    const size_t need = (size_t)strips * n * sizeof(double);
+    if (!workspace_dev || (uintptr_t)workspace_dev % sizeof(double) || !is_device_ptr(workspace_dev))
+        return fail(D3P_E_INVALID_ARG, "%s: the workspace must be device memory aligned to 8 bytes", what);
+    if (workspace_bytes < need)
+        return fail(D3P_E_INVALID_ARG, "%s: workspace of %zu bytes, %zu needed (d3p_gmm_loglik_draw_sums_workspace)", what, workspace_bytes, need);
+    g.obs = obs_dev; g.lat = latent_dev; g.ld = latent_ld; g.rows = (uint32_t)rows; g.n = n; g.k = k; g.d = d;
+    g.part = static_cast<double*>(workspace_dev);
+    int W;
+    const size_t lds = gd_waves(k, d, &W);   // the other forms' rule: the same W, so the same staging per draw
+    if (lds > D3P_GD_LDS_MAX) return fail(D3P_E_UNSUPPORTED, "%s: %zu bytes of LDS needed (k = %d, d = %d)", what, lds, k, d);
+    if (int rc = k <= 4 ? gd_launch<4, 3>(what, s, g, W, lds, strips) : k <= 16 ? gd_launch<16, 3>(what, s, g, W, lds, strips)
+                                                                                : gd_launch<32, 3>(what, s, g, W, lds, strips))
+        return rc;
+    hipLaunchKernelGGL(k_gmm_draw_sums_merge, dim3(cdiv(n, 256)), dim3(256), 0, s, g.part, strips, n, out_dev);
+    return check_launch(what);
 }
 
 }  // extern "C"

@@ -183,7 +183,10 @@ def responsibilities(model, posterior_samples, obs):
     return _from_samples(model, posterior_samples, obs, False, False, True)[1]
 
 
-def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, want_resp, waic_ddof=None, loo_slab_bytes=None):
+def _posterior_latents(rng_key, n, model, model_args, guide, params, kwargs, host_checks=None):
+    """Every host check of the ``posterior_*`` functions, then the one ``d3p_predict_gmm_draws`` launch on the multi form's key rule:
+    ``(x (rows, d) float32, rows, d, latent (n, ld) float32, ld, k, n)`` on the key's device.  ``host_checks(n)`` runs among the host
+    checks, before ``model_args`` is read."""
     _check_model(model)
     if not isinstance(guide, GaussianMixtureGuide):
         raise TypeError(f"mixture density: guide must be a GaussianMixtureGuide, got {type(guide).__name__}")
@@ -192,8 +195,8 @@ def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, 
     nn, _ = MX._count(n)
     if nn > 2 ** 31 - 1:
         raise ValueError("n <= 2^31 - 1")
-    _check_ddof(nn, waic_ddof)
-    chunk = _loo_chunk(nn, loo_slab_bytes)
+    if host_checks is not None:
+        host_checks(nn)
     k, rows, d = MX._shape(model, model_args, kwargs)
     a = list(model_args) + [None] * (4 - len(model_args))
     obs = a[1] if a[1] is not None else kwargs.get("obs")
@@ -217,7 +220,18 @@ def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, 
         obs_keys = torch.empty((nn, 2), dtype=torch.uint32, device=dev)   # (written by the launch, not used here)
         check(lib.d3p_predict_gmm_draws(stream_ptr(), ptr(key), nn, 1, 1, k, d, ptr(alpha_log), ptr(mus_loc),
                                         float(model.prior_mu_scale), None, None, None, ptr(latent), ptr(obs_keys)))
-        return _run(x, rows, d, latent, ld, k, nn, False, want_lppd, want_resp, waic_ddof, chunk)
+    return x, rows, d, latent, ld, k, nn
+
+
+def _posterior(rng_key, n, model, model_args, guide, params, kwargs, want_lppd, want_resp, waic_ddof=None, loo_slab_bytes=None):
+    chunk = []
+
+    def host_checks(nn):
+        _check_ddof(nn, waic_ddof)
+        chunk.append(_loo_chunk(nn, loo_slab_bytes))
+    x, rows, d, latent, ld, k, nn = _posterior_latents(rng_key, n, model, model_args, guide, params, kwargs, host_checks)
+    with torch.cuda.device(x.device):
+        return _run(x, rows, d, latent, ld, k, nn, False, want_lppd, want_resp, waic_ddof, chunk[0])
 
 
 def posterior_log_predictive_density(rng_key, n, model, model_args, guide, params, **kwargs):

@@ -23,6 +23,10 @@ training split, under --posterior-draws draws from the fitted guide.
 
 --loo (off by default; d3p_amd.criteria) adds one line: the PSIS-LOO elpd_loo +- its standard error, p_loo and the number of points
 whose Pareto shape lies above the threshold, on the same split and draws.
+
+--guide-diagnostic [N_DRAWS] (off by default; d3p_amd.mixture_diagnostics) adds one line: the full-data ELBO +- its standard error, the
+importance-sampling estimate of the log evidence, the Pareto k of the guide's importance ratios against its threshold and their
+effective sample size, on the training split (Yao et al. 2018: is the trained guide a usable approximation of the posterior?).
 """
 import argparse
 import itertools
@@ -116,6 +120,18 @@ def loo_report(X, params, k, num_draws, seed=4322):
     return criteria.posterior_loo(threefry.PRNGKey(seed), num_draws, model, (k, X), GaussianMixtureGuide(model), params)
 
 
+def guide_diagnostic_report(X, params, k, num_draws, seed=4323):
+    """The guide diagnostic line (d3p_amd.mixture_diagnostics): ELBO, importance-sampling evidence, Pareto k and effective sample
+    size of num_draws draws from the guide at params on the whole table X."""
+    from d3p_amd import mixture_diagnostics
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    res = mixture_diagnostics.guide_diagnostic(threefry.PRNGKey(seed), num_draws, model, (k, X), GaussianMixtureGuide(model), params)
+    return ("guide diagnostic ({} rows, {} draws): elbo {:.2f} +- {:.2f}, log_evidence_is {:.2f}, pareto k {:.2f} (threshold {:.2f}), "
+            "ess {:.1f}").format(res.n_rows, res.n_draws, float(res.elbo), float(res.elbo_se), float(res.log_evidence_is),
+                                 float(res.pareto_k), res.k_threshold, float(res.ess))
+
+
 def main(args):
     L.require_device()
     N, k, d = args.num_samples, args.num_components, args.dimensions
@@ -189,6 +205,8 @@ def main(args):
         res = loo_report(X_train, params, k, args.posterior_draws)
         print("PSIS-LOO ({} points, {} posterior draws): elpd_loo {:.2f} +- {:.2f}, p_loo {:.2f}, pareto k above {:.2f} in {} points".format(
             res.n_rows, res.n_draws, float(res.elpd_loo), float(res.se), float(res.p_loo), res.k_threshold, int(res.n_high_k)))
+    if getattr(args, "guide_diagnostic", None) is not None:
+        print(guide_diagnostic_report(X_train, params, k, args.guide_diagnostic))
     return acc, pis, modes
 
 
@@ -212,6 +230,9 @@ def parse_args(argv=None):
     parser.add_argument('--loo', action='store_true',
                         help='report the PSIS-LOO elpd_loo, its standard error, p_loo and the count of high Pareto shapes')
     parser.add_argument('--waic', action='store_true', help='report elpd_waic, its standard error and p_waic of the fitted mixture')
+    parser.add_argument('--guide-diagnostic', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, report the ELBO, the importance-sampling evidence, the Pareto k and the effective sample '
+                             'size of N_DRAWS (default 100) draws from the guide on the training table')
     return parser.parse_args(argv)
 
 

@@ -922,6 +922,28 @@ int d3p_loglik_draw_sums(void* stream, const d3p_logreg_model* model, const floa
                          const float* latent_dev, int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, double* out_draws_dev,
                          void* workspace_dev, size_t workspace_bytes);
 
+/* Per-draw sums of the mixture model's pointwise log-likelihood over a whole table (d3p_amd/mixture_diagnostics.py: full-data log
+ * joint, ELBO and the Pareto k of the mixture guide's importance ratios; d3p_gmm_density.hip); added symbols, ABI 9
+ * unchanged.  obs and the latents as for d3p_gmm_loglik_rows, and with its ll[s, r] BIT FOR BIT (one kernel text, instantiated for both):
+ *   out_dev[s] = sum_{r < rows} ll[s, r]                             n float64; IEEE float64 additions of the float32 values
+ * without the n x rows matrix.  Nothing is clamped: a draw with a -inf element (every pis_j of the draw 0) gives -inf for that draw
+ * only; a NaN in a row of obs makes every draw NaN, a NaN in a draw's latents that draw only.
+ * Summation order, fixed (no floating-point atomics, no arrival order; the output bits are identical between calls, a function of the
+ * arguments only and, for draw s, of that draw's latents only): the table is cut into tiles of 64 rows and those into strips of `per`
+ * consecutive tiles,
+ *   tiles = ceil(rows / 64);  per = ceil(tiles / 2048);  strips = ceil(tiles / per) <= 2048          (a function of rows alone)
+ * For draw s: tile sum = the balanced binary tree over the tile's 64 rows in index order, (double)ll of a row below `rows` and exactly
+ * 0.0 of a row past it -- level 1 adds rows (0, 1), (2, 3), ..., level 2 those pairs' sums (0..1, 2..3), ..., level 6 the two halves;
+ * strip sum = the strip's tile sums added one by one in ascending tile order from 0.0, kept in the workspace as float64 [strip][n];
+ * out[s] = the strip sums added in ascending strip order from strip 0's, by a second small launch on the same stream.
+ * d3p_gmm_loglik_draw_sums_workspace(rows, d, k, n) = 8 strips n bytes (0 for rows == 0; d and k do not enter).  Arguments, limits and
+ * errors are d3p_gmm_loglik_rows' (the same checks in the same order), then, also before any launch, D3P_E_INVALID_ARG for an out that
+ * is not aligned to 8 bytes and for a workspace that is null, not aligned to 8 bytes, not device memory or smaller than the size
+ * above.  rows == 0: out is filled with 0.0 (a memset, no launch; the workspace is not read and may be null) and D3P_OK. */
+size_t d3p_gmm_loglik_draw_sums_workspace(uint64_t rows, int32_t d, int32_t k, uint32_t n);
+int d3p_gmm_loglik_draw_sums(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
+                             int32_t k, uint32_t n, double* out_dev, void* workspace_dev, size_t workspace_bytes);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

@@ -39,6 +39,31 @@ class VaeModel(C.Structure):
                 ("H2", C.c_int32)]   # H2 > 0: a second hidden layer on each side (BASELINE config 5's [400, 200] variant)
 
 
+class GemmOpts(C.Structure):
+    """d3p_gemm_opts (include/d3p_hip.h, test aids): the options of the VAE's product dispatcher."""
+    _fields_ = [("a_last_one", C.c_int32), ("epi", C.c_int32), ("part", C.c_void_p), ("part_floats", C.c_uint64), ("C2", C.c_void_p),
+                ("ex_zu", C.c_void_p), ("ex_eps", C.c_void_p), ("ep_x", C.c_void_p), ("ep_ll", C.c_void_p), ("ep_xx", C.c_void_p),
+                ("ex_Z", C.c_int32), ("ex_sc", C.c_float), ("has_jumps", C.c_int32), ("n_seg", C.c_int32), ("k_seg", C.c_int32),
+                ("force_splits", C.c_int32), ("b_njump", C.c_int64), ("b_kjump", C.c_int64), ("bias_njump", C.c_int64),
+                ("c_njump", C.c_int64), ("b_row_scale", C.c_void_p), ("exact16_word", C.c_void_p), ("exact16_nonce", C.c_uint32),
+                ("leave_split", C.c_int32)]
+
+
+class GemmReport(C.Structure):
+    _fields_ = [("route", C.c_int32), ("splits", C.c_int32), ("splits_left", C.c_int32)]
+
+
+class GemmMember(C.Structure):
+    """d3p_gemm_member: one product of d3p_gemm_f32_group."""
+    _fields_ = [("A", C.c_void_p), ("a_sm", C.c_int64), ("a_sk", C.c_int64), ("B", C.c_void_p), ("b_sk", C.c_int64), ("b_sn", C.c_int64),
+                ("C", C.c_void_p), ("bias", C.c_void_p), ("ldc", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("alpha", C.c_float), ("accumulate", C.c_int32), ("opts", GemmOpts), ("report", GemmReport), ("joined", C.c_int32)]
+
+
+D3P_GROUP_MAX = 6
+GEMM_ROUTE_F32, GEMM_ROUTE_F32_VA, GEMM_ROUTE_F32_VB, GEMM_ROUTE_W8, GEMM_ROUTE_BF16X3, GEMM_ROUTE_GROUPED = 0, 1, 2, 4, 5, 6
+
+
 class PredictSite(C.Structure):
     """d3p_predict_site (include/d3p_hip.h): one latent sample site of the predictive draws."""
     _fields_ = [("size", C.c_int32), ("offset", C.c_int32), ("chain", C.c_int32), ("key_index", C.c_int32),
@@ -184,6 +209,10 @@ SIGNATURES = {
     "d3p_vae_num_params": (C.c_int64, [_V]),
     "d3p_dpvi_vae_workspace": (C.c_size_t, [_V, _U32]),
     "d3p_gemm_f32": (C.c_int, [_V, _V, C.c_int64, C.c_int64, _V, C.c_int64, C.c_int64, _V, _I32, _I32, _I32, _I32, _V, _F, _I32]),
+    # test aids: the dispatcher's options and the grouped launch on their own (tests/test_gpu_vae_gemm.py): added symbols, ABI 9 unchanged
+    "d3p_gemm_f32_ex": (C.c_int, [_V, _V, C.c_int64, C.c_int64, _V, C.c_int64, C.c_int64, _V, _I32, _I32, _I32, _I32, _V, _F, _I32,
+                                  C.POINTER(GemmOpts), C.POINTER(GemmReport)]),
+    "d3p_gemm_f32_group": (C.c_int, [_V, C.POINTER(GemmMember), _I32, _I32, _V, _V, _U32]),
     "d3p_vae_step_sums": (C.c_int, [_V, _V, _V, _V, _V, _U32, _V, _V, _F, _V, _V, _V, _V, C.c_size_t]),
     "d3p_vae_evaluate": (C.c_int, [_V, _V, _V, _V, _U32, _V, _V, _V, _V, C.c_size_t]),
     "d3p_dpvi_vae_update": (C.c_int, [_V, _V, _V, _V, _V, _V, _U32, _V, _V, _V, _V, C.c_size_t]),

@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(256) k_gemm_f32(GemmArgs g)
 //     wavefront's VALU, LDS or memory instruction, whatever its priority.  The efficiency of a GEMM is therefore
 //     MFMA cycles / (MFMA cycles + issue cycles of every other instruction on the SIMD + stalls nobody covers).
 // Hence: (a) few instructions per MFMA -- fragments are read with ds_read_b128 (4 MFMA steps per read), operands are fetched
-// with 16-byte loads whose addresses are a per-thread base + slice offset, edges are applied arithmetically at staging time;
+// with 16-byte loads whose addresses are a per-thread base + slice offset, edges are applied by selects at staging time;
 // (b) two wavefronts per SIMD even when the tile count gives one workgroup per CU (224 tiles for 4096 x 400), so that one's
 // waits (LDS round trip after the barrier, the barrier itself) are covered by the other's MFMAs; (c) one barrier per slice,
 // placed in the MIDDLE of the slice's MFMAs: 8 MFMAs | stage slice i + 1, fetch slice i + 3 | barrier | read the fragments
@@ -327,10 +327,11 @@ __global__ void __launch_bounds__(256) k_gemm_f32(GemmArgs g)
 // of the 32 k's gives the same sum), so lane (r, h) needs k = 16 h .. 16 h + 15 of its row: four ds_read_b128 per operand.
 // An operand that is k-fast in memory is stored as loaded (b128).  A row-fast one (float4 = 4 rows at one k) is transposed in
 // registers where the thread holds two k's (A: 4 x b64 stores) and by four b32 stores otherwise (B).
-// Loads are straight-line from CLAMPED addresses, the edges are applied arithmetically at staging time (guarded loads -- also
+// Loads are straight-line from CLAMPED addresses, the edges are applied to the LOADED values at staging time (guarded loads -- also
 // "valid ? load : fill", which LLVM turns back into a branch -- make the compiler wait with vmcnt(0): no prefetch):
-//   * k beyond the split's range: A is multiplied by 0 there (B may hold anything finite);
-//   * rows of A beyond m_real: multiplied by 0, plus 1 for the virtual row of ones; rows >= M / columns >= N only feed
+//   * k beyond the split's range: A is 0 there, and so is a k-fast B (selects: whatever the over-read padding holds, NaN and Inf
+//     included, stays out; an n-fast B is read from clamped rows of the matrix itself);
+//   * rows of A beyond m_real: 0, or 1 for the virtual row of ones (selects again); rows >= M / columns >= N only feed
 //     accumulator entries that are never stored.
 // The host guarantees N % 4 == 0 for an n-fast B (a float4 is inside or outside whole) and, for an m-fast A, a row stride of at
 // least roundup4(m_real) (the last float4 may hold up to three rows past m_real, masked one by one).
@@ -339,6 +340,10 @@ __global__ void __launch_bounds__(256) k_gemm_f32(GemmArgs g)
 #define D3P_GTM 128
 #define D3P_GKB 32
 #define D3P_GLD (D3P_GKB + 4)
+// an element of A at an edge: the loaded value where the row exists in memory and k lies inside the split's range, `fill` (1 for the
+// virtual row of ones, else 0) in a row that does not, 0 beyond the K range -- selected, never multiplied: the over-read padding
+// (header above) may hold NaN or Inf, and 0 * Inf would poison the row
+__device__ __forceinline__ float edge_sel(bool in_k, bool keep, float v, float fill) { return in_k ? (keep ? v : fill) : 0.f; }
 template <bool AK, bool BN>
 __global__ void __launch_bounds__(512) k_gemm_f32_w8(GemmArgs g)
 {
@@ -373,12 +378,15 @@ __global__ void __launch_bounds__(512) k_gemm_f32_w8(GemmArgs g)
     // K or lie beyond it -- the tail and the prefetches past the end -- clamp k per thread), and a tile that touches neither the
     // last rows of A nor the end of the split's K range is staged as loaded.
     // (K need not be a multiple of 4: the last float4 of a k-fast operand then runs past K inside its row -- the host checks the row
-    // stride -- and A is masked element by element there; what B holds beyond K multiplies zeros)
+    // stride -- and both operands are masked element by element there)
     const int K4 = (g.K + 3) & ~3;
     const int ka_last = AK ? K4 - 4 : g.K - 1, kb_last = BN ? g.K - 1 : K4 - 4;
     // (m-fast A: the last float4 that holds real rows starts at roundup4(m_real) - 4; it may run up to 3 rows past m_real inside the
     // row stride -- the host checks a_sk >= roundup4(m_real) -- and those rows are masked one by one)
     const int m_last = AK ? m_real - 1 : ((m_real + 3) & ~3) - 4, n_last = g.N - (BN ? 4 : 1);
+    // (a tile that holds nothing but the virtual row of ones -- m_real a multiple of the tile -- starts BEHIND the last row in memory:
+    // every row clamps to m_last, below m0, so the base moves there too and the 32-bit offsets stay >= 0; as n_base for B below)
+    const int m_base = m0 < m_last ? m0 : m_last;
     const long long a_kstride = AK ? 1 : g.a_sk, b_kstride = BN ? g.b_sk : 1;
     long long a_row[2];  // element offset of this thread's (clamped) row(s), k = 0
     unsigned a_off[2];   // ... + its k offset inside a slice, relative to the slice base
@@ -386,9 +394,9 @@ __global__ void __launch_bounds__(512) k_gemm_f32_w8(GemmArgs g)
     for (int r = 0; r < 2; ++r) {
         const int gm = m0 + a_m[r], cm = gm < m_last ? gm : m_last;
         a_row[r] = AK ? (long long)cm * g.a_sm : (long long)cm;
-        a_off[r] = (unsigned)(a_row[r] - (AK ? (long long)m0 * g.a_sm : (long long)m0) + (long long)a_k[r] * a_kstride);
+        a_off[r] = (unsigned)(a_row[r] - (AK ? (long long)m_base * g.a_sm : (long long)m_base) + (long long)a_k[r] * a_kstride);
     }
-    const float* a_tile = g.A + (AK ? (long long)m0 * g.a_sm : (long long)m0);  // uniform; rows clamp downwards only: offsets stay >= 0
+    const float* a_tile = g.A + (AK ? (long long)m_base * g.a_sm : (long long)m_base);  // uniform; offsets stay >= 0 (m_base above)
     const int gn_c = (n0 + b_n) < n_last ? (n0 + b_n) : n_last;
     const long long b_row = BN ? (long long)gn_c : (long long)gn_c * g.b_sn;
     // (a clamped column can lie left of the tile's first column only when the tile starts within 3 of N: then the base is moved)
@@ -434,23 +442,27 @@ __global__ void __launch_bounds__(512) k_gemm_f32_w8(GemmArgs g)
     };
     auto stage = [&](auto S, int buf, int k0) {  // register set S (slice starting at k0) -> LDS buffer, edges applied
         constexpr int s = decltype(S)::value;
-        const float4 bb = s ? rb1 : rb0;
+        float4 bb = s ? rb1 : rb0;
         float4 o[2] = {s ? ra10 : ra00, s ? ra11 : ra01};
         if (m_edge || k0 + D3P_GKB > kend) {
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const float in_k = (k0 + a_k[r] < kend) ? 1.f : 0.f;
+                const bool in_k = k0 + a_k[r] < kend;
                 const float4 v = o[r];
                 if (AK) {  // one row, four k's per float4: thread rows gm_a0 (r = 0), gm_a1 (r = 1)
-                    const float keep = r ? kp1 : kp0, one = r ? on1 : on0;
+                    const bool keep = (r ? kp1 : kp0) != 0.f;
+                    const float fill = r ? on1 : on0;
                     const int kq = k0 + a_k[r];
-                    const float i0 = kq + 0 < kend ? 1.f : 0.f, i1 = kq + 1 < kend ? 1.f : 0.f, i2 = kq + 2 < kend ? 1.f : 0.f, i3 = kq + 3 < kend ? 1.f : 0.f;
-                    o[r] = make_float4(__fmaf_rn(v.x, keep * i0, one * i0), __fmaf_rn(v.y, keep * i1, one * i1), __fmaf_rn(v.z, keep * i2, one * i2),
-                                       __fmaf_rn(v.w, keep * i3, one * i3));
+                    o[r] = make_float4(edge_sel(kq + 0 < kend, keep, v.x, fill), edge_sel(kq + 1 < kend, keep, v.y, fill),
+                                       edge_sel(kq + 2 < kend, keep, v.z, fill), edge_sel(kq + 3 < kend, keep, v.w, fill));
                 } else {   // four rows per float4
-                    o[r] = make_float4(__fmaf_rn(v.x, kp0 * in_k, on0 * in_k), __fmaf_rn(v.y, kp1 * in_k, on1 * in_k),
-                                       __fmaf_rn(v.z, kp2 * in_k, on2 * in_k), __fmaf_rn(v.w, kp3 * in_k, on3 * in_k));
+                    o[r] = make_float4(edge_sel(in_k, kp0 != 0.f, v.x, on0), edge_sel(in_k, kp1 != 0.f, v.y, on1),
+                                       edge_sel(in_k, kp2 != 0.f, v.z, on2), edge_sel(in_k, kp3 != 0.f, v.w, on3));
                 }
+            }
+            if (!BN) {   // a k-fast B: its last float4 may run past K inside the row, and what lies there need not be finite
+                const int kq = k0 + b_k;
+                bb = make_float4(kq + 0 < kend ? bb.x : 0.f, kq + 1 < kend ? bb.y : 0.f, kq + 2 < kend ? bb.z : 0.f, kq + 3 < kend ? bb.w : 0.f);
             }
         }
         if (AK) {
@@ -661,6 +673,9 @@ __device__ __forceinline__ void gemm_bf16x3_tile(const GemmArgs& g, const int tx
     const int K4 = (g.K + 3) & ~3;
     const int ka_last = AK ? K4 - 4 : g.K - 1, kb_last = BN ? g.K - 1 : K4 - 4;
     const int m_last = AK ? m_real - 1 : ((m_real + 3) & ~3) - 4, n_last = g.N - (BN ? 4 : 1);
+    // (a tile that holds nothing but the virtual row of ones -- m_real a multiple of the tile -- starts BEHIND the last row in memory:
+    // every row clamps to m_last, below m0, so the base moves there too and the 32-bit offsets stay >= 0; as n_base for B below)
+    const int m_base = m0 < m_last ? m0 : m_last;
     const long long a_kstride = AK ? 1 : g.a_sk, b_kstride = BN ? g.b_sk : 1;
     long long a_row[2];
     unsigned a_off[2];
@@ -668,9 +683,9 @@ __device__ __forceinline__ void gemm_bf16x3_tile(const GemmArgs& g, const int tx
     for (int r = 0; r < 2; ++r) {
         const int gm = m0 + a_m[r], cm = gm < m_last ? gm : m_last;
         a_row[r] = AK ? (long long)cm * g.a_sm : (long long)cm;
-        a_off[r] = (unsigned)(a_row[r] - (AK ? (long long)m0 * g.a_sm : (long long)m0) + (long long)a_k[r] * a_kstride);
+        a_off[r] = (unsigned)(a_row[r] - (AK ? (long long)m_base * g.a_sm : (long long)m_base) + (long long)a_k[r] * a_kstride);
     }
-    const float* a_tile = g.A + (AK ? (long long)m0 * g.a_sm : (long long)m0);
+    const float* a_tile = g.A + (AK ? (long long)m_base * g.a_sm : (long long)m_base);
     const int gn_c = (n0 + b_n) < n_last ? (n0 + b_n) : n_last;
     const long long b_row = BN ? (long long)gn_c : (long long)gn_c * g.b_sn;
     const int n_base = n0 < n_last ? n0 : n_last;
@@ -725,18 +740,22 @@ __device__ __forceinline__ void gemm_bf16x3_tile(const GemmArgs& g, const int tx
         if (decltype(EDGE)::value && (m_edge || k0 + D3P_GKB > kend)) {
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const float in_k = (k0 + a_k[r] < kend) ? 1.f : 0.f;
+                const bool in_k = k0 + a_k[r] < kend;
                 const float4 v = o[r];
                 if (AK) {
-                    const float keep = r ? kp1 : kp0, one = r ? on1 : on0;
+                    const bool keep = (r ? kp1 : kp0) != 0.f;
+                    const float fill = r ? on1 : on0;
                     const int kq = k0 + a_k[r];
-                    const float i0 = kq + 0 < kend ? 1.f : 0.f, i1 = kq + 1 < kend ? 1.f : 0.f, i2 = kq + 2 < kend ? 1.f : 0.f, i3 = kq + 3 < kend ? 1.f : 0.f;
-                    o[r] = make_float4(__fmaf_rn(v.x, keep * i0, one * i0), __fmaf_rn(v.y, keep * i1, one * i1), __fmaf_rn(v.z, keep * i2, one * i2),
-                                       __fmaf_rn(v.w, keep * i3, one * i3));
+                    o[r] = make_float4(edge_sel(kq + 0 < kend, keep, v.x, fill), edge_sel(kq + 1 < kend, keep, v.y, fill),
+                                       edge_sel(kq + 2 < kend, keep, v.z, fill), edge_sel(kq + 3 < kend, keep, v.w, fill));
                 } else {
-                    o[r] = make_float4(__fmaf_rn(v.x, kp0 * in_k, on0 * in_k), __fmaf_rn(v.y, kp1 * in_k, on1 * in_k),
-                                       __fmaf_rn(v.z, kp2 * in_k, on2 * in_k), __fmaf_rn(v.w, kp3 * in_k, on3 * in_k));
+                    o[r] = make_float4(edge_sel(in_k, kp0 != 0.f, v.x, on0), edge_sel(in_k, kp1 != 0.f, v.y, on1),
+                                       edge_sel(in_k, kp2 != 0.f, v.z, on2), edge_sel(in_k, kp3 != 0.f, v.w, on3));
                 }
+            }
+            if (!BN) {   // a k-fast B: its last float4 may run past K inside the row, and what lies there need not be finite
+                const int kq = k0 + b_k;
+                bb = make_float4(kq + 0 < kend ? bb.x : 0.f, kq + 1 < kend ? bb.y : 0.f, kq + 2 < kend ? bb.z : 0.f, kq + 3 < kend ? bb.w : 0.f);
             }
         }
         uint32_t w[3];
@@ -978,7 +997,7 @@ __global__ void __launch_bounds__(512) k_gemm_bf16x3(GemmArgs g)
 // launch floor): a linear grid over the workgroups of all members, dealt to the XCDs as xcd_tile deals one product's (every XCD
 // walks one contiguous run of the order member, K slab, m, n), the host choosing ONE K range per workgroup for all members so that
 // the run is a whole number of equal rounds (gemm_group_splits).
-#define D3P_GROUP_MAX 6
+// (D3P_GROUP_MAX members at most: include/d3p_hip.h)
 #define D3P_WPART_SPLITS 16  // most split-K partial tiles a product leaves
 struct GemmGroup {
     GemmArgs g[D3P_GROUP_MAX];
@@ -1055,6 +1074,18 @@ static int gemm_group_launch(hipStream_t s, GemmGroupPlan& G)
 // Split count of a k_gemm_bf16x3 product, or ONE count for all members of a group (they share K = the batch): the one whose rounds
 // of one workgroup per CU (92 KB of LDS each) cost least, a round costing its K range plus about two slices of prologue and
 // epilogue.  tiles = 128 x 64 tiles of the product, or of all members together.
+// can gemm_group_splits return sp for a K range?  The rounded K range reproduces the count and a range holds two slices or more.
+static bool gemm_split_count_ok(int sp, int K, int* k_per = nullptr, int* n_slabs = nullptr)
+{
+    if (sp < 1 || sp > D3P_WPART_SPLITS) return false;
+    int kp = (K + sp - 1) / sp;
+    kp = (kp + D3P_GKB - 1) / D3P_GKB * D3P_GKB;
+    const int ns = (K + kp - 1) / kp;
+    if (k_per) *k_per = kp;
+    if (n_slabs) *n_slabs = ns;
+    return ns == sp && kp >= 2 * D3P_GKB;
+}
+
 static int gemm_group_splits(unsigned tiles, int K)
 {
     static const int n_cu = [] {   // (one process drives one device: d3p_amd.dist; initialised once, thread-safely)
@@ -1066,10 +1097,8 @@ static int gemm_group_splits(unsigned tiles, int K)
     int best = 1;
     double best_cost = 1e30;
     for (int sp = 1; sp <= D3P_WPART_SPLITS; ++sp) {
-        int kp = (K + sp - 1) / sp;
-        kp = (kp + D3P_GKB - 1) / D3P_GKB * D3P_GKB;
-        const int ns = (K + kp - 1) / kp;
-        if (ns != sp || kp < 2 * D3P_GKB) continue;
+        int kp = 0, ns = 0;
+        if (!gemm_split_count_ok(sp, K, &kp, &ns)) continue;
         const double rounds = std::ceil((double)tiles * ns / n_cu);
         const double cost = rounds * (kp + 2 * D3P_GKB);
         if (cost < best_cost) { best_cost = cost; best = sp; }
@@ -1108,6 +1137,14 @@ static bool gemm_takes_bf16_nfast(const float* A, long long a_sm, long long a_sk
     return !fp32_mfma && va8 && vb8 && (M > 96 || (M > 32 && K >= 2048));
 }
 
+// what gemm() decided for a product (GemmOpts::report): written from the variables it branches on
+enum { GEMM_ROUTE_F32 = D3P_GEMM_ROUTE_F32, GEMM_ROUTE_F32_VA = D3P_GEMM_ROUTE_F32_VA, GEMM_ROUTE_F32_VB = D3P_GEMM_ROUTE_F32_VB, GEMM_ROUTE_W8 = D3P_GEMM_ROUTE_W8,
+       GEMM_ROUTE_BF16X3 = D3P_GEMM_ROUTE_BF16X3, GEMM_ROUTE_GROUPED = D3P_GEMM_ROUTE_GROUPED };
+struct GemmReport {
+    int route;    // k_gemm_f32<VA, VB>: GEMM_ROUTE_F32 | VA bit | VB bit; otherwise one of the other values
+    int splits;   // K slabs of the launch (gridDim.z)
+};
+
 // what a product may ask for beyond C = alpha op(A) op(B) + bias (+ C); every field optional
 struct GemmOpts {
     int a_last_one = 0;             // GemmArgs::a_last_one
@@ -1129,6 +1166,8 @@ struct GemmOpts {
     const float* b_row_scale = nullptr;    // GemmArgs::b_row_scale: bf16 kernel with an n-fast B only (gemm_takes_bf16_nfast)
     const float* ep_x = nullptr;    // epi 4 (with ex_sc): k-fast A, n-fast B on the bf16 kernel, unsplit (gemm_takes_bf16_nfast)
     float *ep_ll = nullptr, *ep_xx = nullptr;
+    GemmReport* report = nullptr;   // test aid (d3p_gemm_f32_ex): which kernel the product takes and its final split count
+    bool plan_only = false;         // test aid: decide (refusals, report) and return before anything is appended or launched
 };
 
 static int gemm(hipStream_t s, const float* A, long long a_sm, long long a_sk, const float* B, long long b_sk, long long b_sn,
@@ -1210,8 +1249,16 @@ static int gemm(hipStream_t s, const float* A, long long a_sm, long long a_sk, c
     g.k_per = k_per;
     g.part = splits > 1 ? part : nullptr;
     const dim3 grid(cdiv(N, D3P_GT), cdiv(M, tm), splits);
-    if (big && !fp32_mfma && group && splits_left && group->n < D3P_GROUP_MAX &&
-        (group->n == 0 || (group->ak == (a_sk == 1) && group->bn == (b_sn == 1)))) {
+    const bool joins = big && !fp32_mfma && group && splits_left && group->n < D3P_GROUP_MAX &&
+                       (group->n == 0 || (group->ak == (a_sk == 1) && group->bn == (b_sn == 1)));
+    if (o.report) {
+        o.report->route = joins ? GEMM_ROUTE_GROUPED
+                                : (big ? (fp32_mfma ? GEMM_ROUTE_W8 : GEMM_ROUTE_BF16X3)
+                                       : (GEMM_ROUTE_F32 | (va ? GEMM_ROUTE_F32_VA : 0) | (vb ? GEMM_ROUTE_F32_VB : 0)));
+        o.report->splits = splits;
+    }
+    if (o.plan_only) return D3P_OK;
+    if (joins) {
         const int p = group->n++;
         group->ak = a_sk == 1;
         group->bn = b_sn == 1;
@@ -2447,6 +2494,124 @@ int d3p_gemm_f32(void* stream, const float* A_dev, int64_t a_sm, int64_t a_sk, c
     D3P_REQUIRE(A_dev && B_dev && C_dev, "d3p_gemm_f32: null pointer");
     D3P_REQUIRE(M >= 1 && N >= 1 && K >= 1 && ldc >= N, "d3p_gemm_f32: bad shape");
     return gemm((hipStream_t)stream, A_dev, a_sm, a_sk, B_dev, b_sk, b_sn, C_dev, ldc, M, N, K, bias_dev, alpha, accumulate);
+}
+
+// ---- test aids: gemm() with its options, and the grouped launch, reachable on their own.  Production never calls them.
+// Everything gemm() cannot run, or a product of the VAE step never asks for, is refused before anything is enqueued.
+static int gemm_ex_check(const float* A, int64_t a_sm, int64_t a_sk, const float* B, const float* C, int32_t ldc, int32_t M, int32_t N,
+                         int32_t K, int32_t accumulate, const d3p_gemm_opts* o, int force_splits)
+{
+    D3P_REQUIRE(A && B && C && o, "d3p_gemm_f32_ex: null pointer");
+    D3P_REQUIRE(M >= 1 && N >= 1 && K >= 1 && ldc >= N, "d3p_gemm_f32_ex: bad shape");
+    D3P_REQUIRE(!o->a_last_one || M >= 2, "d3p_gemm_f32_ex: a_last_one needs a row of A in memory");
+    D3P_REQUIRE(o->epi >= 0 && o->epi <= 4, "d3p_gemm_f32_ex: unknown epilogue");
+    D3P_REQUIRE(!(o->epi == 1 || o->epi == 2) || o->C2, "d3p_gemm_f32_ex: epilogues 1 and 2 need C2");
+    D3P_REQUIRE(o->epi != 3 || (o->ex_zu && o->ex_eps && o->ex_Z == N && ldc >= 2 * N), "d3p_gemm_f32_ex: epilogue 3 needs ex_zu, ex_eps, ex_Z = N and ldc >= 2 N");
+    D3P_REQUIRE(o->epi != 4 || (o->ep_x && o->ep_ll && o->ep_xx && !accumulate && !o->has_jumps && !o->leave_split),
+                "d3p_gemm_f32_ex: epilogue 4 needs ep_x, ep_ll, ep_xx and a plain product");
+    D3P_REQUIRE(!o->leave_split || o->epi == 0, "d3p_gemm_f32_ex: tiles are left unreduced by products without an epilogue only");
+    D3P_REQUIRE(!o->part || o->part_floats >= (uint64_t)M * N, "d3p_gemm_f32_ex: part_floats is smaller than M N");
+    D3P_REQUIRE(o->part || o->part_floats == 0, "d3p_gemm_f32_ex: part_floats without part");
+    if (force_splits != 0) {
+        D3P_REQUIRE(o->part, "d3p_gemm_f32_ex: force_splits without part");
+        D3P_REQUIRE(gemm_split_count_ok(force_splits, K), "d3p_gemm_f32_ex: a force_splits that gemm_group_splits cannot return for this K");
+        D3P_REQUIRE(o->part_floats >= (uint64_t)force_splits * M * N, "d3p_gemm_f32_ex: part_floats is smaller than force_splits M N");
+    }
+    if (o->exact16_word) {
+        const int64_t m_real = o->a_last_one ? M - 1 : M;
+        const bool contiguous = (a_sk == 1 && a_sm == K) || (a_sm == 1 && a_sk == m_real);
+        D3P_REQUIRE(contiguous && (reinterpret_cast<uintptr_t>(A) & 15u) == 0 && (m_real * K) % 4 == 0,
+                    "d3p_gemm_f32_ex: the exactness pass needs a contiguous, 16-byte aligned A of a multiple of 4 elements");
+    }
+    return D3P_OK;
+}
+
+static void gemm_ex_opts(const d3p_gemm_opts* o, GemmOpts& g, GemmJumps& j, int* left, GemmReport* rep)
+{
+    g.a_last_one = o->a_last_one;
+    g.part = o->part; g.part_floats = (size_t)o->part_floats;
+    g.epi = o->epi; g.C2 = o->C2; g.ex_zu = o->ex_zu; g.ex_eps = o->ex_eps; g.ex_Z = o->ex_Z; g.ex_sc = o->ex_sc;
+    g.ep_x = o->ep_x; g.ep_ll = o->ep_ll; g.ep_xx = o->ep_xx;
+    if (o->has_jumps) {
+        j.n_seg = o->n_seg; j.k_seg = o->k_seg;
+        j.b_njump = o->b_njump; j.b_kjump = o->b_kjump; j.bias_njump = o->bias_njump; j.c_njump = o->c_njump;
+        g.jumps = &j;
+    }
+    g.b_row_scale = o->b_row_scale;
+    g.force_splits = o->force_splits;
+    g.splits_left = o->leave_split ? left : nullptr;
+    g.a_exact16 = o->exact16_word; g.a_exact_nonce = o->exact16_nonce;
+    g.report = rep;
+}
+
+// the exactness pass over A, as vae_enqueue_forward enqueues it in front of the products that read the flag
+static void gemm_ex_flag(hipStream_t s, const float* A, int32_t M, int32_t K, const d3p_gemm_opts* o)
+{
+    const size_t n4 = (size_t)(o->a_last_one ? M - 1 : M) * K / 4;
+    hipLaunchKernelGGL(k_exact16_flag, dim3(vae_exact_blocks(n4)), dim3(256), 0, s, A, n4, o->exact16_word, o->exact16_nonce);
+}
+
+int d3p_gemm_f32_ex(void* stream, const float* A_dev, int64_t a_sm, int64_t a_sk, const float* B_dev, int64_t b_sk, int64_t b_sn,
+                    float* C_dev, int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias_dev, float alpha, int32_t accumulate,
+                    const d3p_gemm_opts* opts, d3p_gemm_report* report)
+{
+    D3P_REQUIRE(report, "d3p_gemm_f32_ex: null report");
+    if (int rc = gemm_ex_check(A_dev, a_sm, a_sk, B_dev, C_dev, ldc, M, N, K, accumulate, opts, opts ? opts->force_splits : 0)) return rc;
+    GemmOpts g;
+    GemmJumps j;
+    GemmReport rep = {0, 0};
+    int left = 0;
+    gemm_ex_opts(opts, g, j, &left, &rep);
+    g.plan_only = true;   // gemm()'s own refusals, before the exactness pass is enqueued
+    if (int rc = gemm((hipStream_t)stream, A_dev, a_sm, a_sk, B_dev, b_sk, b_sn, C_dev, ldc, M, N, K, bias_dev, alpha, accumulate, g)) return rc;
+    g.plan_only = false;
+    if (opts->exact16_word) gemm_ex_flag((hipStream_t)stream, A_dev, M, K, opts);
+    const int rc = gemm((hipStream_t)stream, A_dev, a_sm, a_sk, B_dev, b_sk, b_sn, C_dev, ldc, M, N, K, bias_dev, alpha, accumulate, g);
+    report->route = rep.route;
+    report->splits = rep.splits;
+    report->splits_left = left;
+    return rc;
+}
+
+int d3p_gemm_f32_group(void* stream, d3p_gemm_member* members, int32_t n, int32_t force_splits, const float* sum_in_dev, float* sum_out_dev,
+                       uint32_t sum_n)
+{
+    D3P_REQUIRE(members && n >= 1 && n <= D3P_GROUP_MAX + 1, "d3p_gemm_f32_group: 1 .. D3P_GROUP_MAX + 1 members");
+    D3P_REQUIRE((sum_in_dev != nullptr) == (sum_out_dev != nullptr) && (sum_in_dev || sum_n == 0), "d3p_gemm_f32_group: sum_in and sum_out come together");
+    hipStream_t s = (hipStream_t)stream;
+    for (int p = 0; p < n; ++p) {   // every refusal before the first launch
+        d3p_gemm_member& m = members[p];
+        D3P_REQUIRE(m.opts.leave_split && m.opts.force_splits == 0 && m.opts.epi == 0, "d3p_gemm_f32_group: members leave their tiles and take the group's force_splits");
+        if (int rc = gemm_ex_check(m.A, m.a_sm, m.a_sk, m.B, m.C, m.ldc, m.M, m.N, m.K, m.accumulate, &m.opts, force_splits)) return rc;
+        GemmOpts g;
+        GemmJumps j;
+        GemmReport rep = {0, 0};
+        int left = 0;
+        gemm_ex_opts(&m.opts, g, j, &left, &rep);
+        g.force_splits = force_splits;
+        g.plan_only = true;
+        if (int rc = gemm(s, m.A, m.a_sm, m.a_sk, m.B, m.b_sk, m.b_sn, m.C, m.ldc, m.M, m.N, m.K, m.bias, m.alpha, m.accumulate, g)) return rc;
+    }
+    GemmGroupPlan plan;
+    GemmJumps jumps[D3P_GROUP_MAX + 1];
+    for (int p = 0; p < n; ++p) {
+        d3p_gemm_member& m = members[p];
+        GemmOpts g;
+        GemmReport rep = {0, 0};
+        int left = 0;
+        gemm_ex_opts(&m.opts, g, jumps[p], &left, &rep);
+        g.force_splits = force_splits;
+        g.group = &plan;
+        if (m.opts.exact16_word) gemm_ex_flag(s, m.A, m.M, m.K, &m.opts);
+        if (int rc = gemm(s, m.A, m.a_sm, m.a_sk, m.B, m.b_sk, m.b_sn, m.C, m.ldc, m.M, m.N, m.K, m.bias, m.alpha, m.accumulate, g)) return rc;
+        m.report.route = rep.route;
+        m.report.splits = rep.splits;
+        m.report.splits_left = left;
+        m.joined = rep.route == GEMM_ROUTE_GROUPED ? 1 : 0;
+    }
+    if (plan.n > 0) { plan.sum_in = sum_in_dev; plan.sum_out = sum_out_dev; plan.sum_n = sum_n; }
+    else D3P_REQUIRE(!sum_in_dev, "d3p_gemm_f32_group: no member joined the group, so nothing sums sum_in");
+    return gemm_group_launch(s, plan);
 }
 
 int64_t d3p_vae_num_params(const d3p_vae_model* model)

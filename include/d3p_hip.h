@@ -598,6 +598,83 @@ int d3p_gemm_f32(void* stream, const float* A_dev, int64_t a_sm, int64_t a_sk, c
                  int64_t b_sn, float* C_dev, int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias_dev,
                  float alpha, int32_t accumulate);
 
+/* ---- test aids (added symbols, ABI 9 unchanged): the options of the VAE's product dispatcher and its grouped launch, reachable
+ * on their own so that tests/test_gpu_vae_gemm.py can check every option against a float64 restatement.  Production never calls
+ * them.  Both refuse (D3P_E_INVALID_ARG, d3p_last_error) before anything is enqueued whatever the dispatcher cannot run or a
+ * product of the VAE step never asks for: null operands an option needs; epilogue 4 or b_row_scale on a product that does not take
+ * the bf16 kernel; part_floats < M N (or < force_splits M N); a force_splits the dispatcher's own split choice could not return for
+ * this K (the K range rounded up to slices of 32 must reproduce the count and hold two slices or more; at most 16).
+ *
+ * d3p_gemm_opts mirrors the dispatcher's options (zero = not asked for):
+ *   a_last_one    row M - 1 of op(A) is a virtual row of ones: A holds M - 1 rows in memory
+ *   part          split-K scratch of part_floats floats ([splits][M][N]); without it a product is never split
+ *   epi           0 store; 1 C = softplus(o), C2 = sigmoid(o); 2 C = o * C2; 3 C = [dz | du] with dz = o + ex_sc z,
+ *                 du = dz sd eps - ex_sc, [z | sd] = ex_zu (laid out like C, ldc >= 2 N), eps = ex_eps (M x ex_Z dense, ex_Z = N);
+ *                 4 (bf16 kernel, k-fast A, n-fast B, unsplit) C = ex_sc (sigmoid(o) - x), x = ep_x laid out like C, and per row and
+ *                 group of 32 columns the sums of x o - softplus(o) and of x^2 in ep_ll / ep_xx ([ceil(N / 32)][M])
+ *   has_jumps     the displaced segments: columns n >= n_seg of B, bias and C lie b_njump / bias_njump / c_njump elements further,
+ *                 rows k >= k_seg of B lie b_kjump further
+ *   b_row_scale   (bf16 kernel, n-fast B) row k of B is multiplied by b_row_scale[k] while it is staged
+ *   force_splits  K slabs of a product on the bf16 kernel, instead of a count of the dispatcher's own
+ *   leave_split   a split product is not reduced: its tiles stay in part and report.splits_left says how many (0: C was written)
+ *   exact16_word  caller-owned device word: the entry first enqueues the exactness pass over A with exact16_nonce into it (A
+ *                 contiguous, 16-byte aligned, a multiple of 4 elements), then the product reads it: A is taken as exactly
+ *                 bf16 iff the word differs from the nonce afterwards
+ * d3p_gemm_report: route = the kernel the dispatcher chose (from the variables it branches on), splits = K slabs launched. */
+#define D3P_GROUP_MAX 6          /* most products of one grouped launch */
+#define D3P_GEMM_ROUTE_F32 0     /* the 64 x 64 kernel; | D3P_GEMM_ROUTE_F32_VA / _VB: 16-byte fetches of A / of B */
+#define D3P_GEMM_ROUTE_F32_VA 1
+#define D3P_GEMM_ROUTE_F32_VB 2
+#define D3P_GEMM_ROUTE_W8 4      /* the eight-wave fp32 kernel (developer switch D3P_GEMM_FP32_MFMA) */
+#define D3P_GEMM_ROUTE_BF16X3 5  /* the eight-wave kernel on the bf16 pipe */
+#define D3P_GEMM_ROUTE_GROUPED 6 /* appended to a grouped launch */
+typedef struct {
+    int32_t a_last_one;
+    int32_t epi;
+    float* part;
+    uint64_t part_floats;
+    float* C2;
+    const float* ex_zu;
+    const float* ex_eps;
+    const float* ep_x;
+    float* ep_ll;
+    float* ep_xx;
+    int32_t ex_Z;
+    float ex_sc;
+    int32_t has_jumps, n_seg, k_seg, force_splits;
+    int64_t b_njump, b_kjump, bias_njump, c_njump;
+    const float* b_row_scale;
+    uint32_t* exact16_word;
+    uint32_t exact16_nonce;
+    int32_t leave_split;
+} d3p_gemm_opts;
+typedef struct {
+    int32_t route, splits, splits_left;
+} d3p_gemm_report;
+int d3p_gemm_f32_ex(void* stream, const float* A_dev, int64_t a_sm, int64_t a_sk, const float* B_dev, int64_t b_sk,
+                    int64_t b_sn, float* C_dev, int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias_dev,
+                    float alpha, int32_t accumulate, const d3p_gemm_opts* opts, d3p_gemm_report* report);
+/* Up to D3P_GROUP_MAX + 1 products appended to ONE grouped launch with a common force_splits (every member: leave_split set, no
+ * epilogue, its own force_splits 0), then launched.  Per member: report, and joined = 1 when it became part of the group, 0 when
+ * the dispatcher launched it alone (the seventh; one whose operand form differs from the group's; one that does not take the bf16
+ * kernel).  sum_in_dev / sum_out_dev / sum_n: optional, *sum_out = sum of sum_in[0 .. sum_n) by one more workgroup of the launch. */
+typedef struct {
+    const float* A;
+    int64_t a_sm, a_sk;
+    const float* B;
+    int64_t b_sk, b_sn;
+    float* C;
+    const float* bias;
+    int32_t ldc, M, N, K;
+    float alpha;
+    int32_t accumulate;
+    d3p_gemm_opts opts;
+    d3p_gemm_report report;
+    int32_t joined;
+} d3p_gemm_member;
+int d3p_gemm_f32_group(void* stream, d3p_gemm_member* members, int32_t n, int32_t force_splits, const float* sum_in_dev,
+                       float* sum_out_dev, uint32_t sum_n);
+
 /* Stages 1-3 of DPSVI.update fused (svi.py:238-348): sums_dev[P + 2] = [sum_i c_i g_i | sum_i loss_i | n] without ever
  * forming a per-example gradient: norms by ||a d^T||_F = ||a|| ||d||, clipped sums as A^T (diag(c) Delta) GEMMs.
  * eps_dev (B x Z, optional parity-mode noise) or jax_key_dev (per-example threefry keys, svi.py:289-290).

@@ -80,6 +80,16 @@ def main(args):
         errs.append(err)
         print("Epoch {}: loss on training set = {:.2f}, mean abs reconstruction error = {:.4f} ({:.2f} s.)".format(
             i, train_loss, err, t1 - t0))
+    n_draws = getattr(args, "held_out_density", None)
+    if n_draws:   # the reference reports a held-out loss per epoch (vae.py:250-265); here: unscaled, per image, after the last one
+        from d3p_amd.vae_density import held_out_density
+        _, density_rng = rng_suite.split(dpsvi_rng, 2)
+        res = held_out_density(rng_suite.convert_to_jax_rng_key(density_rng), n_draws, model, svi.guide, svi.get_params(svi_state),
+                               X_test, z_dim=args.z_dim, hidden_dim=args.hidden_dim)
+        B = res.n_images
+        print("held-out density ({} draws, {} images): ELBO per image = {:.3f}, IWAE bound per image = {:.3f} +- {:.3f}, "
+              "n_high_k = {} of {} (Pareto k above {:.2f})".format(res.n_draws, B, float(res.elbo_total) / B, float(res.log_px_is_total) / B,
+                                                                   float(res.log_px_is_total_se) / B, int(res.n_high_k), B, res.k_threshold))
     return errs
 
 
@@ -93,4 +103,7 @@ if __name__ == "__main__":
     parser.add_argument('-N', '--num-samples', default=8192, type=int, help='training images')
     parser.add_argument('--epsilon', default=1., type=float, help='targeted value for privacy parameter epsilon')
     parser.add_argument('--sigma', default=None, type=float, help='dp_scale of the Gaussian mechanism (overrides --epsilon)')
+    parser.add_argument('--held-out-density', nargs='?', const=64, default=None, type=int, metavar='N',
+                        help='after the last epoch: held-out ELBO, importance-weighted bound and Pareto k per test image from N guide '
+                             'draws each (default 64)')
     main(parser.parse_args())

@@ -1021,6 +1021,53 @@ size_t d3p_gmm_loglik_draw_sums_workspace(uint64_t rows, int32_t d, int32_t k, u
 int d3p_gmm_loglik_draw_sums(void* stream, const float* obs_dev, uint64_t rows, int32_t d, const float* latent_dev, int64_t latent_ld,
                              int32_t k, uint32_t n, double* out_dev, void* workspace_dev, size_t workspace_bytes);
 
+/* Log importance weights of the VAE's guide draws on a held-out batch and per-column float64 statistics (d3p_amd/vae_density.py: the
+ * per-image ELBO, the importance-weighted bound on log p(x) and the Pareto k of the amortised guide; d3p_vae_density.hip, DESIGN.md
+ * 4l); added symbols, ABI 9 and d3p_vae_model unchanged.  Nothing is scaled: model->scale and model->inv_obs are not read.
+ * For draw i < n and image b < B, with (zl_b, zs_b) the encoder's heads at X[b] (zs = the log of the guide's scale) and a_ib the
+ * decoder's output pre-activation at z_ib (the passes of d3p_predict_vae through the product kernels):
+ *   z_ib       = the z d3p_predict_vae's posterior path draws for (key, n, multi), bit for bit     -> z_out_dev [n][B][Z]
+ *   log_px     = sum_c x_bc a_ibc - softplus(a_ibc),   softplus(a) = max(a, 0) + log(1 + exp(-|a|))
+ *   log_pz     = sum_j -z^2 / 2 - log(2 pi) / 2
+ *   log_qz     = sum_j -u^2 / 2 - zs_bj - log(2 pi) / 2,   u = (z_ibj - zl_bj) exp(-zs_bj)
+ *   log_w[i,b] = (log_px + log_pz) - log_qz                                                         -> logw_out_dev [n][B]
+ * Every term is float32 arithmetic, each operation rounded on its own; the sums over D and Z are float64 in a fixed order (lane l of a
+ * wavefront owns the groups of four consecutive columns g with g mod 64 == l, ascending; Z at lane stride 64; the 64 lane sums merged
+ * by the xor butterfly 32, 16, .., 1); log_w is combined in float64 and every output is rounded to float32 once.  parts_out_dev
+ * (nullable) receives [3][n][B]: log_px, log_pz, log_qz.  No atomics, no scratch: the output bits are a function of the arguments'
+ * values alone -- not of the pointers' alignment (16-byte loads are used where D % 4 == 0 and the rows are aligned, scalar loads
+ * otherwise, over the same element-to-lane map) and not of draws_per_slab.
+ * The decoder runs over SLABS of whole draws (their z rows are contiguous), so that the workspace holds the activations and logits
+ * of one slab only.  The product dispatcher picks its kernel by a product's row count (more than 96 rows: bf16x3), so every slab is
+ * kept on the side of that threshold where the call's n B rows fall: n B <= 96 runs as one slab; otherwise a slab has
+ * max(draws_per_slab, ceil(97 / B)) draws and a remainder of fewer than ceil(97 / B) draws joins the slab before it.
+ * d3p_vae_log_weights_workspace(model, B, draws_per_slab) sizes for the longest such slab, max(draws_per_slab, ceil(97 / B)) +
+ * ceil(97 / B) - 1 draws (0 for a bad model, B == 0 or draws_per_slab == 0); n does not enter.
+ * Errors, all before any launch: bad model, B == 0, n == 0, n B >= 2^31, B D >= 2^32, B Z >= 2^31, n B Z > 2^40, draws_per_slab == 0, a
+ * pointer that is not device memory (parts_out_dev may be null): D3P_E_INVALID_ARG; a workspace below the size above:
+ * D3P_E_WORKSPACE.  A NaN in X[b] makes every output of image b NaN and touches no other image. */
+size_t d3p_vae_log_weights_workspace(const d3p_vae_model* model, uint32_t B, uint32_t draws_per_slab);
+int d3p_vae_log_weights(void* stream, const d3p_vae_model* model, const float* params_dev, const float* X_dev, uint32_t B,
+                        const uint32_t* key_dev, uint32_t n, int32_t multi, uint32_t draws_per_slab, float* z_out_dev, float* logw_out_dev,
+                        float* parts_out_dev, void* workspace_dev, size_t workspace_bytes);
+
+/* k_vae_logw on its own (tools/time_vae_density.py, tests): the reduction of d3p_vae_log_weights over `rows` rows of given logits
+ * [rows][D] and latents z [rows][Z], row r belonging to image r mod B of X [B][D], zl and zs [B][Z]; logw_out_dev [rows],
+ * parts_out_dev nullable [3][rows].  The same kernel and the same bits as inside d3p_vae_log_weights.  rows, B, D, Z >= 1, rows < 2^31
+ * and device pointers, else D3P_E_INVALID_ARG before the launch. */
+int d3p_vae_logw_rows(void* stream, const float* logits_dev, const float* X_dev, const float* z_dev, const float* zl_dev, const float* zs_dev,
+                      uint32_t rows, uint32_t B, int32_t D, int32_t Z, float* logw_out_dev, float* parts_out_dev);
+
+/* Per-column statistics of a float32 draws x cols matrix m_dev[s * ld + c] (model-free), in float64 after the loads:
+ *   out_dev[0 * cols + c] = mean_s m                          out_dev[1 * cols + c] = sum_s (m - mean)^2 / (n - 1)     (n == 1: NaN)
+ *   out_dev[2 * cols + c] = logsumexp_s m - log n             out_dev[3 * cols + c] = (sum_s r)^2 / sum_s r^2,  r = exp(m - max_s m)
+ * The draws are cut into four contiguous chunks of ceil(n / 4); each chunk is summed in ascending draw order from 0.0 and the four
+ * results are merged as ((c0 + c1) + c2) + c3; two sweeps (sum and max; then the centred squares, sum r and sum r^2); deterministic.
+ * A NaN in a column makes its four outputs NaN; every draw -inf: mean = lse = -inf, var = ess = NaN; a +inf draw: lse = +inf, ess = NaN;
+ * none of them touches another column.  n >= 1, ld >= cols, m aligned to 4 and out to 8 bytes, both device memory, else
+ * D3P_E_INVALID_ARG before any launch; cols >= 2^31: D3P_E_UNSUPPORTED; cols == 0: D3P_OK, no launch. */
+int d3p_col_stats(void* stream, const float* m_dev, int64_t ld, uint32_t n, uint64_t cols, double* out_dev);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

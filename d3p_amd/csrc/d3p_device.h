@@ -236,6 +236,20 @@ __device__ __forceinline__ uint32_t tf_iota_word(uint32_t k0, uint32_t k1, uint6
     return b;
 }
 
+// Sample key of the guide's latent draw for batch position p (see oracle d3po_px_sample_key):
+// px_key = split(jax_key, B)[p]; guide_seed = split(px_key)[1]; sample_key = split(guide_seed)[1].
+__device__ __forceinline__ void px_sample_key(uint32_t j0, uint32_t j1, uint32_t B, uint32_t p, uint32_t& o0,
+                                              uint32_t& o1)
+{
+    const uint32_t px0 = tf_iota_word(j0, j1, 2ull * B, 2ull * p);
+    const uint32_t px1 = tf_iota_word(j0, j1, 2ull * B, 2ull * p + 1);
+    uint32_t a, b, g0, g1;
+    threefry2x32(px0, px1, 0u, 2u, a, g0);  // split(key,2): counts [0,1 | 2,3]; key1 = (y1(0,2), y1(1,3))
+    threefry2x32(px0, px1, 1u, 3u, a, g1);
+    threefry2x32(g0, g1, 0u, 2u, a, o0);
+    threefry2x32(g0, g1, 1u, 3u, b, o1);
+}
+
 // jax.random.uniform's float32 construction: (bits >> 9) | 0x3f800000, minus 1, affine, clamp at lo.
 __device__ __forceinline__ float bits_to_uniform(uint32_t bits, float lo, float hi)
 {

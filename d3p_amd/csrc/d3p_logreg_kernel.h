@@ -102,20 +102,6 @@ static __global__ void k_pack(d3p_logreg_model m, const float* __restrict__ para
     if (e < D) pack_column(m, D, e, params[e], params[D + e], pack);
 }
 
-// Sample key of the guide's latent draw for batch position p (see oracle d3po_px_sample_key):
-// px_key = split(jax_key, B)[p]; guide_seed = split(px_key)[1]; sample_key = split(guide_seed)[1].
-__device__ __forceinline__ void px_sample_key(uint32_t j0, uint32_t j1, uint32_t B, uint32_t p, uint32_t& o0,
-                                              uint32_t& o1)
-{
-    const uint32_t px0 = tf_iota_word(j0, j1, 2ull * B, 2ull * p);
-    const uint32_t px1 = tf_iota_word(j0, j1, 2ull * B, 2ull * p + 1);
-    uint32_t a, b, g0, g1;
-    threefry2x32(px0, px1, 0u, 2u, a, g0);  // split(key,2): counts [0,1 | 2,3]; key1 = (y1(0,2), y1(1,3))
-    threefry2x32(px0, px1, 1u, 3u, a, g1);
-    threefry2x32(g0, g1, 0u, 2u, a, o0);
-    threefry2x32(g0, g1, 1u, 3u, b, o1);
-}
-
 // Sample key of particle q of K for batch position p (numpyro Trace_ELBO(num_particles=K)):
 // K == 1: px_sample_key itself; K > 1: particle_key = split(split(jax_key, B)[p], K)[q], then guide_seed = split(particle_key)[1]
 // and sample_key = split(guide_seed)[1] as above.  The one place of the particle rule (the MeanFieldGuide eps of

@@ -253,7 +253,7 @@ static int draws_enqueue(hipStream_t s, const uint32_t* key, uint32_t n, int32_t
     return check_launch("d3p_predict_draws");
 }
 
-// the VAE's dense layer stacks through the product kernels of d3p_vae.hip
+// the VAE's dense layer stacks through the product kernels of d3p_gemm.hip (vae_predict_encode / vae_predict_decode: d3p_vae.hip)
 int vae_predict_encode(hipStream_t s, const d3p_vae_model* m, const float* params, const float* X, uint32_t B, float* zl, float* zs, float* h0, float* h1,
                        float* sg);
 int vae_predict_decode(hipStream_t s, const d3p_vae_model* m, const float* params, const float* z, uint32_t rows, float* logits, float* h0, float* h1,

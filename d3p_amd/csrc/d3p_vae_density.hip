@@ -4,7 +4,7 @@
 // turn them into the per-image ELBO, the importance-weighted bound and the effective sample size.  All quantities are UNSCALED.
 //
 // d3p_vae_log_weights is unfused on purpose: the encoder runs once, d3p_predict_draws draws z under the posterior predictive's key
-// rule, and the decoder (the product kernels of d3p_vae.hip through vae_predict_decode) writes the logits of one SLAB of draws at a
+// rule, and the decoder (the product kernels of d3p_gemm.hip through vae_predict_decode) writes the logits of one SLAB of draws at a
 // time; k_vae_logw reads a slab's logits back and reduces each row.  (The logits round trip is 4 D bytes per row beside about
 // 2 (Z H + H D) flops of products: docs/experiments_vae_density.md has the measured share.)
 //
@@ -14,7 +14,7 @@
 // element-to-lane map is the same whether the four columns arrive as one 16-byte load (D % 4 == 0 and both row starts aligned) or as
 // scalar loads, so the output bits do not depend on the load path: they are a function of the arguments' values alone.  The Z terms
 // are walked at lane stride 64.  Per-term arithmetic is float32 with every operation rounded on its own (fp contract off):
-//   px term  x a - (max(a, 0) + log(1 + exp(-|a|)))          the softplus of the output product's epilogue 4 (d3p_vae.hip), __expf / __logf
+//   px term  x a - (max(a, 0) + log(1 + exp(-|a|)))          the softplus of the output product's epilogue 4 (d3p_gemm.hip), __expf / __logf
 //   pz term  (-0.5 (z z)) - HALF_LOG_2PI
 //   qz term  ((-0.5 (u u)) - zs) - HALF_LOG_2PI,  u = (z - zl) expf(-zs)
 // log_w = (px + pz) - qz in float64, rounded to float32 once; the parts are the float64 sums rounded to float32 once each.
@@ -195,7 +195,7 @@ __global__ void __launch_bounds__(256) k_col_stats(ColStatsArgs g)
 }
 
 // ---- the slabs of d3p_vae_log_weights -------------------------------------------------------------------------------------------
-// The product dispatcher of d3p_vae.hip picks its kernel by the row count of a product (more than 96 rows: the bf16x3 kernel), and the
+// The product dispatcher of d3p_gemm.hip picks its kernel by the row count of a product (more than 96 rows: the bf16x3 kernel), and the
 // two kernels round differently.  For outputs that do not depend on draws_per_slab every slab must therefore fall on the side of that
 // threshold on which the whole call's n B rows fall: n B <= D3P_LOGW_SMALL_ROWS runs as ONE slab; otherwise a slab holds at least
 // `floor_draws` = ceil((D3P_LOGW_SMALL_ROWS + 1) / B) draws, and a remainder shorter than that joins the slab before it.

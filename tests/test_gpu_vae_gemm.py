@@ -1,4 +1,4 @@
-"""The VAE's product kernels (d3p_amd/csrc/d3p_vae.hip: k_gemm_f32, k_gemm_f32_w8, k_gemm_bf16x3, k_gemm_bf16x3_group,
+"""The VAE's product kernels (d3p_amd/csrc/d3p_gemm.hip: k_gemm_f32, k_gemm_f32_w8, k_gemm_bf16x3, k_gemm_bf16x3_group,
 k_gemm_reduce) one option at a time, through the test aids d3p_gemm_f32_ex / d3p_gemm_f32_group, against the float64 restatement
 of tests/vae_gemm_ref.py.
 

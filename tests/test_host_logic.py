@@ -37,6 +37,22 @@ def test_struct_layouts_match_the_header():
     assert L.BatchSource.n_rows.offset == 40
 
 
+def test_build_lists_name_every_source_and_header():
+    """_SRC is what gets compiled and _DEPS decides whether a stale library is rebuilt; both are kept by hand."""
+    import d3p_amd._lib as L
+    csrc = os.path.join(os.path.dirname(L.__file__), "csrc")
+    names = sorted(os.listdir(csrc))
+    sources = [os.path.join(csrc, n) for n in names if n.endswith(".hip")]
+    assert sources and sorted(L._SRC) == sources
+    assert all(p in L._DEPS for p in L._SRC)
+    for n in names:
+        if n.endswith(".h"):
+            assert os.path.join(csrc, n) in L._DEPS, f"{n} is missing from _lib._DEPS"
+        if n.endswith((".h", ".hip")):
+            for inc in re.findall(r'^\s*#\s*include\s+"(d3p_\w+\.h)"', open(os.path.join(csrc, n)).read(), re.M):
+                assert any(os.path.basename(p) == inc for p in L._DEPS), f"{n} includes {inc}, which is missing from _lib._DEPS"
+
+
 def test_error_codes_without_touching_the_device():
     import d3p_amd._lib as L
     lib = L.load()

@@ -1,4 +1,4 @@
-"""Float64 restatement of the VAE's product dispatcher (d3p_amd/csrc/d3p_vae.hip: gemm(), GemmArgs) for tests/test_gpu_vae_gemm.py
+"""Float64 restatement of the VAE's product dispatcher (d3p_amd/csrc/d3p_gemm.hip: gemm(), GemmArgs) for tests/test_gpu_vae_gemm.py
 and tests/test_vae_gemm_host.py: strided products with bias, alpha and accumulate, the virtual row of ones, the displaced
 segments, the four epilogues from their definitions, a float32 restatement of the epilogues that calibrates their tolerance, and
 the case lists.  No device code; everything runs on the CPU in torch.

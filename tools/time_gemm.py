@@ -1,4 +1,4 @@
-"""Times d3p_gemm_f32 (fp32 MFMA) on the GEMM shapes of the VAE step (BASELINE config 5: 784 -> 400 -> 50, B = 4096):
+"""Times d3p_gemm_f32 (d3p_amd/csrc/d3p_gemm.hip) on the GEMM shapes of the VAE step (BASELINE config 5: 784 -> 400 -> 50, B = 4096):
 HIP events around 20 launches each; prints microseconds and TFLOP/s (fp32 MFMA peak of MI355X: 157)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

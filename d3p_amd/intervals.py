@@ -1,0 +1,300 @@
+"""Credible and predictive intervals for the regression models, and a summary of the latent draws: per-row quantiles over the
+posterior draws.
+
+    quantiles(matrix, probs)                                                                      -> (Q, cols) float32
+    credible_interval(model, posterior_samples, X[, y[, N]], prob=0.9, probs=None, slab_bytes=64 << 20)
+    posterior_credible_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20)
+    predictive_interval(rng_key, model, posterior_samples, X[, y[, N]], prob=0.9, probs=None, slab_bytes=64 << 20)
+    posterior_predictive_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20)
+    latent_summary(posterior_samples, prob=0.9)                             -> {site: {"mean", "std", "median", "lower", "upper"}}
+
+The interval functions return ``{"lower": (rows,), "median": (rows,), "upper": (rows,)}`` float32 on the GPU at the probabilities
+``((1 - prob) / 2, 0.5, (1 + prob) / 2)``, the equal-tailed interval; with ``probs`` (1 to 8 floats in [0, 1]) they return
+``{"quantiles": (Q, rows)}`` at those probabilities instead.
+
+``quantiles`` is the model-free reduction (``d3p_col_quantiles``, ``d3p_amd/csrc/d3p_quantiles.hip``): the quantiles of every column
+of a float32 or int32 ``(draws, cols)`` CUDA matrix with unit column stride and any row stride.  The quantile rule is numpy's
+``method='linear'``: with ``h = (n - 1) p`` in float64, ``lo = floor(h)`` and ``g = h - lo`` -- computed HERE, in Python floats, so
+that the device does no arithmetic on ``p`` -- the result lies between the (lo+1)-th smallest value ``a`` and the next ``b``:
+``a + (b - a) g`` where ``g < 0.5``, else ``b - (b - a) (1 - g)``, in float64 on the exactly selected values, rounded to float32 once
+(an int32 count above 2^24 therefore rounds).  -0 and +0 are one value; a NaN in a column makes the column's outputs NaN; between
+``-inf`` and ``+inf`` the result is NaN, between a finite value and an infinity that infinity.  ``n <= 65535``.
+
+``credible_interval`` is over ``mu[s, r] = E[y | x_r, draw s] = sigmoid(t) | t | exp(t)``, the uncertainty of the regression function
+(``LogisticRegression | LinearRegression | PoissonRegression``; ``t`` and the link exactly as ``d3p_amd.prediction`` forms them).
+``predictive_interval`` is over draws of ``obs``: ``LinearRegression`` (float32 outcomes) and ``PoissonRegression`` (int32 counts),
+the outcomes ``d3p_amd.predictive.predictive_samples`` returns for the same key; ``LogisticRegression`` raises ``TypeError`` there,
+since an outcome in {0, 1} has no useful quantiles -- ``credible_interval`` gives the interval of its probability.  Every other
+model raises ``TypeError``.
+
+Slabs.  The credible forms write the ``n x rows`` matrix in row slabs exactly as ``criteria.loo`` does: chunks of ``max(128,
+(slab_bytes // (4 n)) // 128 * 128)`` rows, each written by ``d3p_predict_mean_rows`` on the row range into one reused buffer and
+reduced by ``d3p_col_quantiles`` into the rows' part of the output on the same stream; the latents are packed once and the result
+does not depend on ``slab_bytes``.  The predictive forms are NOT cut into slabs: ``d3p_predict_glm`` indexes a draw's random stream
+by ``(rows, r)`` -- the whole table's row count and the row's index in it -- and has no row offset, so a row range would receive other
+outcomes than the whole-table call of ``predictive_samples``.  The entry is left as it is: the predictive matrix is written whole
+when its ``4 n rows`` bytes fit ``slab_bytes``, and a ``ValueError`` that names the required ``slab_bytes`` is raised when they do not.
+
+Keys are those of ``d3p_amd.predictive``.  ``posterior_credible_interval`` draws the latents through ``infer_util._guide_latents``, the
+draws ``posterior_predictive_moments`` and ``posterior_predictive_samples`` use for the same key and ``n``;
+``posterior_predictive_interval`` reduces the ``obs`` of ``posterior_predictive_samples`` itself.  Every host check runs before the
+device is touched; there is no CPU fallback.
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from . import infer_util as U
+from . import modelling as M
+from . import prediction as PM
+from . import predictive as PS
+from ._lib import check, ptr, stream_ptr
+
+__all__ = ["quantiles", "credible_interval", "posterior_credible_interval", "predictive_interval", "posterior_predictive_interval",
+           "latent_summary"]
+
+MAX_PROBS = 8
+MAX_DRAWS = 65535
+
+
+def _family(model, what):
+    fam = U._FAMILY.get(type(model))
+    if fam is None:
+        raise TypeError(f"{what}: unsupported model {type(model).__name__} (LogisticRegression, LinearRegression and PoissonRegression "
+                        "have intervals over a linear predictor)")
+    return fam
+
+
+def _probs(prob, probs):
+    """(the probabilities as a tuple of floats, the result's names or None) after the host checks."""
+    if probs is not None:
+        try:
+            ps = tuple(float(p) for p in probs)
+        except TypeError:
+            raise ValueError("probs: a sequence of 1 to 8 floats in [0, 1] is required") from None
+        if not 1 <= len(ps) <= MAX_PROBS:
+            raise ValueError(f"probs: 1 to {MAX_PROBS} probabilities per call, got {len(ps)}")
+        for p in ps:
+            if not 0.0 <= p <= 1.0:   # (a NaN fails both comparisons)
+                raise ValueError(f"probs: every probability must lie in [0, 1], got {p!r}")
+        return ps, None
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 < float(prob) < 1.0:
+        raise ValueError(f"prob must be a float in (0, 1), got {prob!r}")
+    prob = float(prob)
+    return ((1.0 - prob) / 2.0, 0.5, (1.0 + prob) / 2.0), ("lower", "median", "upper")
+
+
+def positions(probs, n):
+    """[(lo, g)] of the probabilities over n draws: h = (n - 1) p in float64, lo = floor(h), g = h - lo."""
+    out = []
+    for p in probs:
+        h = (n - 1) * float(p)
+        lo = int(math.floor(h))
+        out.append((lo, h - lo))
+    return out
+
+
+def _check_draws(n, what):
+    if n > MAX_DRAWS:
+        raise ValueError(f"{what}: {n} draws; the quantile kernel runs at most {MAX_DRAWS} draws (n <= {MAX_DRAWS})")
+
+
+def _reduce(first, dtype, ld, n, cols, pos, out, out_ld):
+    """d3p_col_quantiles on the (n, cols) matrix that starts at tensor `first`, into out (a tensor at the first output element)."""
+    Q = len(pos)
+    lo = (C.c_uint32 * Q)(*[p[0] for p in pos])
+    g = (C.c_double * Q)(*[p[1] for p in pos])
+    check(_lib.load().d3p_col_quantiles(stream_ptr(), ptr(first), 0 if dtype == torch.float32 else 1, ld, n, cols, Q, lo, g, ptr(out), out_ld))
+
+
+def _result(q, names):
+    return {"quantiles": q} if names is None else {name: q[i] for i, name in enumerate(names)}
+
+
+def quantiles(matrix, probs):
+    """The quantiles of every column of ``matrix`` -- a 2-D CUDA tensor ``(draws, cols)``, float32 or int32, any row stride, unit column
+    stride -- at ``probs`` (1 to 8 floats in [0, 1]): ``(Q, cols)`` float32 on the matrix's device, numpy's ``method='linear'`` on the
+    exactly selected order statistics (module docstring)."""
+    ps, _ = _probs(None, probs if probs is not None else ())
+    if not isinstance(matrix, torch.Tensor) or matrix.dim() != 2 or matrix.dtype not in (torch.float32, torch.int32) or not matrix.is_cuda:
+        raise ValueError("quantiles: a 2-D float32 or int32 CUDA tensor (draws, cols) is required")
+    n, cols = int(matrix.shape[0]), int(matrix.shape[1])
+    if cols > 1 and matrix.stride(1) != 1:
+        raise ValueError("quantiles: the matrix's columns must have unit stride (rows may be strided)")
+    if n < 1:
+        raise ValueError("quantiles: at least one draw")
+    _check_draws(n, "quantiles")
+    ld = int(matrix.stride(0)) if n > 1 else cols
+    if ld < cols:
+        raise ValueError("quantiles: the matrix's rows overlap (row stride below the column count)")
+    pos = positions(ps, n)
+    _lib.require_device()   # (every check above runs without a device)
+    with torch.cuda.device(matrix.device):
+        out = torch.empty((len(ps), cols), dtype=torch.float32, device=matrix.device)
+        if cols:
+            _reduce(matrix, matrix.dtype, ld, n, cols, pos, out, cols)
+    return out
+
+
+def _mean_slabs(model, fam, X, rows, d, n, latent, pos, chunk):
+    """(Q, rows) float32: the quantiles of mu[:, r] over the draws, the n x rows matrix written and reduced in row slabs of `chunk`."""
+    first, ld, w_off, b_col = latent
+    X = M._f32(X, "X")
+    lib = _lib.load()
+    ms = U._model_struct(model, fam, d)
+    out = torch.empty((len(pos), rows), dtype=torch.float32, device=X.device)
+    buf = torch.empty((n * min(chunk, rows),), dtype=torch.float32, device=X.device)
+    for lo in range(0, rows, chunk):
+        count = min(chunk, rows - lo)
+        check(lib.d3p_predict_mean_rows(stream_ptr(), C.byref(ms), ptr(X[lo:lo + count]), count, ptr(first), ld, w_off, b_col, n, ptr(buf), count))
+        _reduce(buf, torch.float32, count, n, count, pos, out[0, lo:], rows)
+    return out
+
+
+def credible_interval(model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+    """The equal-tailed ``prob`` interval and the median of ``mu[s, r] = E[y | x_r, draw s]`` over given posterior draws, per row:
+    ``{"lower", "median", "upper"}`` (or ``{"quantiles"}`` with ``probs``), float32 on the GPU (module docstring).
+
+    ``model_args = (X[, y[, N]])``; ``y`` and ``N`` are accepted and not read.  ``posterior_samples = {"w": (n, d)[, "intercept":
+    (n,) or (n, 1)]}`` as for ``predictive_moments``: packed views are read in place, everything else is packed once."""
+    fam = _family(model, "credible_interval")
+    ps, names = _probs(prob, probs)
+    rows, d = PM._data(model, model_args)
+    n, _ = U._sample_shape(model, posterior_samples, d)
+    _check_draws(n, "credible_interval")
+    chunk = U._loo_chunk(n, slab_bytes)
+    if chunk is None:
+        raise ValueError("slab_bytes must be an int >= 1, got None")
+    pos = positions(ps, n)
+    _lib.require_device()   # (every check above runs without a device)
+    with torch.cuda.device(M._device()):
+        q = _mean_slabs(model, fam, model_args[0], rows, d, n, U._pack(model, posterior_samples, n, d), pos, chunk)
+    return _result(q, names)
+
+
+def posterior_credible_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+    """``credible_interval`` over ``n`` draws from the guide at ``params`` (as ``DPSVI.get_params`` returns them), drawn on the device on
+    ``posterior_predictive_moments``' key rule and consumed there.  Guides: ``AutoDiagonalNormal``, ``DiagonalNormalGuide``;
+    ``MeanFieldGuide`` for logistic regression."""
+    fam = _family(model, "posterior_credible_interval")
+    U._check_guide(model, guide)
+    ps, names = _probs(prob, probs)
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    _check_draws(n, "posterior_credible_interval")
+    rows, d = PM._data(model, model_args)
+    chunk = U._loo_chunk(n, slab_bytes)
+    if chunk is None:
+        raise ValueError("slab_bytes must be an int >= 1, got None")
+    if not isinstance(params, dict):
+        raise ValueError("params: the dict DPSVI.get_params returns is required")
+    gparams = [(name, M._param(params, name, size)) for name, size in M._guide_param_names(guide, model, d)]
+    key = M._check_key(rng_key)
+    pos = positions(ps, n)
+    _lib.require_device()
+    dev = key.device
+    with torch.cuda.device(dev):
+        latent = U._guide_latents(key, n, model, guide, gparams, d, rows, dev)
+        q = _mean_slabs(model, fam, model_args[0], rows, d, n, latent, pos, chunk)
+    return _result(q, names)
+
+
+def _predictive_family(model, what):
+    fam = _family(model, what)
+    if fam == _lib.D3P_FAMILY_LOGREG:
+        raise TypeError(f"{what}: an outcome of LogisticRegression lies in {{0, 1}} and has no useful quantiles; credible_interval gives "
+                        "the interval of its probability")
+    return fam
+
+
+def _check_whole(n, rows, slab_bytes, what):
+    """The predictive matrix is written whole (module docstring): its 4 n rows bytes must fit slab_bytes."""
+    U._check_slab_bytes(slab_bytes)
+    need = 4 * n * rows
+    if need > slab_bytes:
+        raise ValueError(f"{what}: the {n} x {rows} predictive matrix is written whole (the outcome kernel has no row offset) and needs "
+                         f"slab_bytes >= {need}, got {slab_bytes}")
+
+
+def _reduce_obs(obs, n, rows, pos, names):
+    obs = obs.reshape(n, rows)
+    with torch.cuda.device(obs.device):
+        q = torch.empty((len(pos), rows), dtype=torch.float32, device=obs.device)
+        _reduce(obs, obs.dtype, rows, n, rows, pos, q, rows)
+    return _result(q, names)
+
+
+def predictive_interval(rng_key, model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+    """The equal-tailed ``prob`` interval and the median of the outcomes ``obs`` over given posterior draws, per row: the quantiles of
+    what ``predictive_samples(rng_key, model, posterior_samples, *model_args)`` returns, without that matrix leaving the device.
+    ``LinearRegression`` and ``PoissonRegression``; the matrix is written whole and must fit ``slab_bytes`` (module docstring)."""
+    _predictive_family(model, "predictive_interval")
+    ps, names = _probs(prob, probs)
+    rows, d = PS._data(model, model_args, kwargs)
+    n, _ = U._sample_shape(model, posterior_samples, d)
+    _check_draws(n, "predictive_interval")
+    _check_whole(n, rows, slab_bytes, "predictive_interval")
+    M._check_key(rng_key)
+    pos = positions(ps, n)
+    obs = PS.predictive_samples(rng_key, model, posterior_samples, *model_args, **kwargs)
+    return _reduce_obs(obs, n, rows, pos, names)
+
+
+def posterior_predictive_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+    """``predictive_interval`` over ``n`` draws from the posterior predictive at ``params``: the quantiles of the ``obs`` that
+    ``posterior_predictive_samples(rng_key, n, model, model_args, guide, params)`` returns for the same key."""
+    _predictive_family(model, "posterior_predictive_interval")
+    U._check_guide(model, guide)
+    ps, names = _probs(prob, probs)
+    n = PS._count(n)
+    _check_draws(n, "posterior_predictive_interval")
+    rows, d = PS._data(model, model_args, kwargs)
+    _check_whole(n, rows, slab_bytes, "posterior_predictive_interval")
+    pos = positions(ps, n)
+    obs = PS.posterior_predictive_samples(rng_key, n, model, model_args, guide, params, **kwargs)["obs"]
+    return _reduce_obs(obs, n, rows, pos, names)
+
+
+def latent_summary(posterior_samples, prob=0.9):
+    """Per site of ``posterior_samples`` (``w``, ``intercept``; each viewed as an ``n x D`` matrix of draws): ``{"mean", "std", "median",
+    "lower", "upper"}``, each of the site's shape without the draw axis -- the columns of numpyro's ``print_summary`` without ``n_eff``
+    and ``r_hat``, which are meaningless for independent draws from a guide.  ``mean`` and ``std`` are float64 from ``d3p_col_stats``
+    (the ``n - 1`` variance: ``n == 1`` gives a NaN ``std``); the three quantiles are float32 from ``d3p_col_quantiles`` at ``((1 -
+    prob) / 2, 0.5, (1 + prob) / 2)``."""
+    ps, names = _probs(prob, None)
+    if not isinstance(posterior_samples, dict) or not posterior_samples:
+        raise ValueError("posterior_samples: a dict of sites (n draws each) is required")
+    shapes = {}
+    for name, v in posterior_samples.items():
+        shp = tuple(v.shape) if hasattr(v, "shape") else ()
+        if len(shp) < 1 or shp[0] < 1 or M._numel(v) == 0:
+            raise ValueError(f"posterior_samples['{name}']: at least one draw along the first axis is required")
+        _check_draws(shp[0], "latent_summary")
+        shapes[name] = shp
+    _lib.require_device()   # (every check above runs without a device)
+    lib = _lib.load()
+    out = {}
+    for name, v in posterior_samples.items():
+        shp = shapes[name]
+        n = shp[0]
+        with torch.cuda.device(M._device()):
+            m = v.detach() if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 else M._f32(v, f"posterior_samples['{name}']")
+            m = m.reshape(n, -1)
+            cols = int(m.shape[1])
+            if cols > 1 and m.stride(1) != 1:
+                m = m.contiguous()
+            ld = int(m.stride(0)) if n > 1 else cols
+            if ld < cols:
+                m, ld = m.contiguous(), cols
+            with torch.cuda.device(m.device):
+                stats = torch.empty((4, cols), dtype=torch.float64, device=m.device)
+                check(lib.d3p_col_stats(stream_ptr(), ptr(m), ld, n, cols, ptr(stats)))
+                q = torch.empty((3, cols), dtype=torch.float32, device=m.device)
+                _reduce(m, torch.float32, ld, n, cols, positions(ps, n), q, cols)
+        site = {"mean": stats[0], "std": torch.sqrt(stats[1])}
+        site.update({nm: q[i] for i, nm in enumerate(names)})
+        out[name] = {k: t.reshape(shp[1:]) for k, t in site.items()}
+    return out

@@ -8,6 +8,10 @@ from the weights that generated the data.
 --guide-diagnostic [N_DRAWS] (off by default; d3p_amd.diagnostics) adds one line after training: the full-data ELBO +- its standard
 error, the importance-sampling estimate of the log evidence, the Pareto k of the guide's importance ratios against its threshold and
 their effective sample size (Yao et al. 2018: is the trained guide a usable approximation of the posterior?).
+
+--intervals [N_DRAWS] (off by default; d3p_amd.intervals) adds, after training: the share of the observed outcomes inside the
+equal-tailed 90 % posterior predictive interval of N_DRAWS draws, the interval's mean width, and mean, std, median and the 5 % / 95 %
+quantiles of the draws of every weight.
 """
 import argparse
 import os
@@ -44,6 +48,26 @@ def guide_diagnostic_report(model, svi, state, X, y, num_draws, seed=3):
                                  float(res.pareto_k), res.k_threshold, float(res.ess))
 
 
+def intervals_report(model, svi, state, X, y, num_draws, seed=4):
+    """The lines of --intervals (d3p_amd.intervals): the share of the observed y inside the equal-tailed 90 % posterior predictive
+    interval of num_draws draws from the trained guide, the interval's mean width, and the summary of the draws of `w`."""
+    from d3p_amd import intervals
+    from d3p_amd.predictive import posterior_predictive_samples
+    import d3p_amd.random.debug as jax_random
+    key, params = jax_random.PRNGKey(seed), svi.get_params(state)
+    iv = intervals.posterior_predictive_interval(key, num_draws, model, (X,), svi.guide, params, prob=0.9)
+    inside = ((y >= iv["lower"]) & (y <= iv["upper"])).double().mean()
+    width = (iv["upper"].double() - iv["lower"].double()).mean()
+    lines = ["90% predictive interval ({} rows, {} draws): coverage {:.4f}, mean width {:.4f}".format(
+        X.shape[0], num_draws, float(inside), float(width))]
+    draws = posterior_predictive_samples(key, num_draws, model, (X[:1],), svi.guide, params)   # (the same latents: they take no row)
+    s = {k: v.double().cpu() for k, v in intervals.latent_summary({"w": draws["w"]}, prob=0.9)["w"].items()}
+    for j in range(s["mean"].shape[0]):
+        lines.append("w[{}]: mean {:.4f}, std {:.4f}, median {:.4f}, 5% {:.4f}, 95% {:.4f}".format(
+            j, float(s["mean"][j]), float(s["std"][j]), float(s["median"][j]), float(s["lower"][j]), float(s["upper"][j])))
+    return lines
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
@@ -70,6 +94,8 @@ def main(args):
         float(y.mean()), float(y.var()), float(pred.mean()), float(pred.var(dim=1).mean())))
     if getattr(args, "guide_diagnostic", None) is not None:
         print(guide_diagnostic_report(model, svi, state, X, y, args.guide_diagnostic))
+    if getattr(args, "intervals", None) is not None:
+        print("\n".join(intervals_report(model, svi, state, X, y, args.intervals)))
     return first, last, err0, err
 
 
@@ -86,4 +112,7 @@ if __name__ == "__main__":
     parser.add_argument('--guide-diagnostic', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, report the ELBO, the importance-sampling evidence, the Pareto k and the effective sample '
                              'size of N_DRAWS (default 100) draws from the guide on the whole table')
+    parser.add_argument('--intervals', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, report the coverage and the mean width of the 90 %% posterior predictive interval of '
+                             'N_DRAWS (default 100) draws on the whole table, and the summary of the draws of w')
     main(parser.parse_args())

@@ -1068,6 +1068,39 @@ int d3p_vae_logw_rows(void* stream, const float* logits_dev, const float* X_dev,
  * D3P_E_INVALID_ARG before any launch; cols >= 2^31: D3P_E_UNSUPPORTED; cols == 0: D3P_OK, no launch. */
 int d3p_col_stats(void* stream, const float* m_dev, int64_t ld, uint32_t n, uint64_t cols, double* out_dev);
 
+/* Per-column quantiles of a draws x cols matrix m_dev[s * ld + c] of float32 (dtype 0) or int32 (dtype 1) values (model-free;
+ * d3p_amd/intervals.py: credible and predictive intervals; d3p_quantiles.hip); added symbols, ABI 9 unchanged.
+ *   out_dev[q * out_ld + c] = the q-th requested quantile of column c, q < Q
+ * The HOST turns a probability p into a position, the device does no arithmetic on p: h = (n - 1) p in float64, lo_host[q] = floor(h),
+ * g_host[q] = h - lo (p = 1: lo = n - 1, g = 0).  Per column, a = the (lo+1)-th smallest value and b = the (lo+2)-th smallest (b is not
+ * read where g == 0), both EXACT on the stored values through an order-preserving uint32 key (float32: -0 taken as +0; int32: the sign
+ * bit flipped).  Then in float64: g == 0 or a == b: a; exactly one of a, b infinite (float32 only): that infinity; a = -inf and
+ * b = +inf: NaN; otherwise with d = b - a: a + d g where g < 0.5, else b - d (1 - g) -- numpy's method='linear'.  One rounding to
+ * float32: an int32 value above 2^24 in magnitude therefore rounds to the nearest float32.  A NaN anywhere in a float32 column makes
+ * all Q outputs of that column NaN and touches no other column.
+ * Deterministic: no floating-point atomics, and a column's output bits depend on that column's values and on (n, lo, g) alone -- not
+ * on ld, out_ld, the other columns of the launch, or on whether the column's keys were staged in LDS (n <=
+ * d3p_col_quantiles_staged_max() = 895) or streamed from memory in every pass (n above it).
+ * D3P_E_INVALID_ARG before any launch: n outside 1 <= n <= 65535, Q outside 1 <= Q <= 8, a lo >= n, a g outside [0, 1), g != 0 at
+ * lo == n - 1, ld < cols, out_ld < cols, a dtype other than 0 / 1, a null pointer, m_dev or out_dev not aligned to 4 bytes or not
+ * device memory (lo_host and g_host are HOST memory: Q values each).  cols > 32 (2^31 - 1): D3P_E_UNSUPPORTED; cols == 0: D3P_OK, no
+ * launch. */
+int d3p_col_quantiles(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uint32_t n, uint64_t cols, uint32_t Q, const uint32_t* lo_host,
+                      const double* g_host, float* out_dev, int64_t out_ld);
+/* the largest n whose keys d3p_col_quantiles stages in LDS (host only, no device call) */
+uint32_t d3p_col_quantiles_staged_max(void);
+
+/* The conditional mean of the observed site over given posterior draws, as an n x rows matrix (d3p_amd/intervals.py: the matrix
+ * d3p_col_quantiles reduces for a credible interval); added symbol, ABI 9 and d3p_logreg_model unchanged.  With t[s, r] as for
+ * d3p_loglik_rows:
+ *   out_dev[s * out_ld + r] = mu[s, r] = sigmoid(t) | t | exp(t)                       (D3P_FAMILY_LOGREG | LINREG | POISSON)
+ * t and the link are formed exactly as d3p_predict_moments forms them (the intercept added as t + latent[s, b_col]; the logistic value
+ * from one e = expf(-|t|) as 1 / (1 + e) or e / (1 + e)); float32, no clamps: exp(t) = inf stays inf, a NaN t stays NaN.  Grid and
+ * stores are d3p_loglik_rows'.  Arguments, limits and errors are d3p_predict_moments', plus out_ld >= rows (D3P_E_INVALID_ARG):
+ * D3P_E_UNSUPPORTED before any launch for D3P_FAMILY_GAUSS_MEAN and D3P_GUIDE_EXP_SITES; rows == 0: D3P_OK, no launch. */
+int d3p_predict_mean_rows(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, const float* latent_dev,
+                          int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, float* out_dev, int64_t out_ld);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

@@ -12,6 +12,10 @@ their effective sample size (Yao et al. 2018: is the trained guide a usable appr
 --intervals [N_DRAWS] (off by default; d3p_amd.intervals) adds, after training: the share of the observed outcomes inside the
 equal-tailed 90 % posterior predictive interval of N_DRAWS draws, the interval's mean width, and mean, std, median and the 5 % / 95 %
 quantiles of the draws of every weight.
+
+--clipping-profile (off by default; d3p_amd.clipping) adds two lines after training: the quantiles of the per-example gradient norms of
+the whole table at the trained parameters, the share of rows the run's clipping threshold clips with the mean clip factor, and the
+median norm as the suggested threshold (Abadi et al. 2016).  They are computed from the private table without noise.
 """
 import argparse
 import os
@@ -68,6 +72,19 @@ def intervals_report(model, svi, state, X, y, num_draws, seed=4):
     return lines
 
 
+def clipping_profile_report(svi, state, X, y):
+    """The lines of --clipping-profile (d3p_amd.clipping): the quantiles of the per-example gradient norms of the whole table at the
+    trained parameters, the share of rows the run's clipping threshold clips and the mean clip factor, and the median as the suggested
+    threshold.  The numbers come from the private table without noise: they are a diagnostic, not a release."""
+    from d3p_amd import clipping
+    p = clipping.clipping_profile(svi, state, X, y)
+    quant = ", ".join("{:g}% {:.4f}".format(100 * q, v) for q, v in zip(p.probs, p.quantiles))
+    return ["clipping profile ({} rows, {} non-finite): gradient norm quantiles {}; mean {:.4f}, max {:.4f}".format(
+                p.n, p.n_nonfinite, quant, p.mean, p.max),
+            "at C = {:g}: clipped fraction {:.4f}, mean clip factor {:.4f}; suggested threshold (median norm) {:.4f}".format(
+                p.thresholds[0], p.clipped_fraction[0], p.mean_clip_factor[0], clipping.suggest_clipping_threshold(p))]
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
@@ -96,6 +113,8 @@ def main(args):
         print(guide_diagnostic_report(model, svi, state, X, y, args.guide_diagnostic))
     if getattr(args, "intervals", None) is not None:
         print("\n".join(intervals_report(model, svi, state, X, y, args.intervals)))
+    if getattr(args, "clipping_profile", False):
+        print("\n".join(clipping_profile_report(svi, state, X, y)))
     return first, last, err0, err
 
 
@@ -115,4 +134,7 @@ if __name__ == "__main__":
     parser.add_argument('--intervals', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, report the coverage and the mean width of the 90 %% posterior predictive interval of '
                              'N_DRAWS (default 100) draws on the whole table, and the summary of the draws of w')
+    parser.add_argument('--clipping-profile', action='store_true',
+                        help='after training, report the quantiles of the per-example gradient norms on the whole table, the share of '
+                             'rows the clipping threshold clips and the suggested threshold (a diagnostic of the private table, not a release)')
     main(parser.parse_args())

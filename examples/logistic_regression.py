@@ -8,6 +8,10 @@ reference's jit(fori_loop(...)) at :149-160).  `--guide handwritten` is the scri
 'intercept', four parameter leaves with exp scales, one perturbation key per leaf) through the five-stage composition;
 `--guide auto` (default) is AutoDiagonalNormal (README.md:99) on the fused device-resident loop.  As in the reference (:135-137) dp_scale is calibrated for --epsilon, with
 d3p_amd.dputil on the restated Fourier accountant; --sigma gives it directly.
+
+--clipping-profile (off by default; d3p_amd.clipping) adds two lines after training: the quantiles of the per-example gradient norms of
+the whole table at the trained parameters, the share of rows the script's clipping threshold (1.0) clips with the mean clip factor, and the
+median norm as the suggested threshold (Abadi et al. 2016).  They are computed from the private table without noise.
 """
 import argparse
 import os
@@ -39,6 +43,19 @@ def estimate_accuracy(X, y, model, guide, params, rng, num_iterations=100):
     from d3p_amd.modelling import sample_multi_posterior_predictive
     samples = sample_multi_posterior_predictive(rng, num_iterations, model, (X,), guide, (X,), params)
     return float((samples["obs"] == y.to(torch.int32)).float().mean())
+
+
+def clipping_profile_report(svi, state, X, y):
+    """The lines of --clipping-profile (d3p_amd.clipping): the quantiles of the per-example gradient norms of the whole table at the
+    trained parameters, the share of rows the run's clipping threshold clips and the mean clip factor, and the median as the suggested
+    threshold.  The numbers come from the private table without noise: they are a diagnostic, not a release."""
+    from d3p_amd import clipping
+    p = clipping.clipping_profile(svi, state, X, y)
+    quant = ", ".join("{:g}% {:.4f}".format(100 * q, v) for q, v in zip(p.probs, p.quantiles))
+    return ["clipping profile ({} rows, {} non-finite): gradient norm quantiles {}; mean {:.4f}, max {:.4f}".format(
+                p.n, p.n_nonfinite, quant, p.mean, p.max),
+            "at C = {:g}: clipped fraction {:.4f}, mean clip factor {:.4f}; suggested threshold (median norm) {:.4f}".format(
+                p.thresholds[0], p.clipped_fraction[0], p.mean_clip_factor[0], clipping.suggest_clipping_threshold(p))]
 
 
 def main(args):
@@ -100,6 +117,8 @@ def main(args):
         pred = posterior_predictive_samples(jax_random.PRNGKey(1), 100, model, (test[0],), guide, svi.get_params(svi_state))["obs"]
         print("posterior predictive check (100 draws): observed mean {:.4f}, predictive mean {:.4f}".format(
             float(test[1].mean()), float(pred.float().mean())))
+    if getattr(args, "clipping_profile", False):   # both guides: the hand-written one draws its eps per site
+        print("\n".join(clipping_profile_report(svi, svi_state, *train)))
     return accs, train_losses
 
 
@@ -116,4 +135,7 @@ if __name__ == "__main__":
                         help="auto: AutoDiagonalNormal (README.md:99); handwritten: the reference script's own two-site guide (:67-86)")
     parser.add_argument('--predictive-accuracy', action='store_true',
                         help="after training, print the test accuracy of 100 posterior-predictive draws (reference :110-116, :230)")
+    parser.add_argument('--clipping-profile', action='store_true',
+                        help='after training, report the quantiles of the per-example gradient norms on the whole table, the share of '
+                             'rows the clipping threshold clips and the suggested threshold (a diagnostic of the private table, not a release)')
     main(parser.parse_args())

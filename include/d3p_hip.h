@@ -1101,6 +1101,42 @@ uint32_t d3p_col_quantiles_staged_max(void);
 int d3p_predict_mean_rows(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, const float* latent_dev,
                           int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, float* out_dev, int64_t out_ld);
 
+/* Per-example gradient norms without the rows (d3p_amd/clipping.py); added symbols, ABI 9 and d3p_logreg_model unchanged.
+ *   norms_dev[r] = the float32 L2 norm over all P = 2 D entries of the row d3p_logreg_px_grads writes for example r, r < rows,
+ * for the examples at positions pos0 .. pos0 + rows - 1 of ONE batch of B_total examples without a mask: X_dev (rows x d) and y_dev
+ * (rows) hold those examples, and the guide draw of example r is eps_r = normal(px_sample_key(jax_key, B_total, pos0 + r), (D,)) --
+ * the draw d3p_logreg_px_grads(B = B_total) makes for position pos0 + r -- or row r of eps_dev (rows x D) where that is given.
+ * px_loss_dev (nullable, rows): the example's loss as d3p_logreg_px_grads writes it without a mask.  No rows x P tensor exists, in
+ * memory or in the workspace (which holds the 5 D derived columns).  The arithmetic is k_logreg_main's; the bits are a function of
+ * the arguments (no atomics).  No clamps: a sum of squares beyond float32 gives inf, exp(t) = inf (Poisson) inf or NaN; other rows are
+ * unaffected.  Families D3P_FAMILY_LOGREG, _LINREG, _POISSON; guide transforms D3P_GUIDE_SOFTPLUS, _EXP; intercept 0 or 1; d <= 2048.
+ * D3P_E_UNSUPPORTED before any launch: D3P_FAMILY_GAUSS_MEAN, D3P_GUIDE_EXP_SITES (pass the sites' eps through eps_dev with
+ * D3P_GUIDE_EXP and kernel-order parameters), d > 2048, pos0 + rows > B_total.  rows == 0: D3P_OK, nothing is written. */
+size_t d3p_logreg_grad_norms_workspace(const d3p_logreg_model* model, uint32_t rows);
+int d3p_logreg_grad_norms(void* stream, const d3p_logreg_model* model, const float* params_dev, const float* X_dev, const float* y_dev,
+                          uint32_t B_total, uint32_t pos0, uint32_t rows, const float* eps_dev /* rows x D, or NULL */,
+                          const uint32_t* jax_key_dev, float* norms_dev, float* px_loss_dev /* nullable */, void* workspace_dev,
+                          size_t workspace_bytes);
+
+/* The profile of a vector of n >= 1 float32 norms against m <= 8 thresholds C_k (finite, > 0) at Q <= 8 quantile positions; added
+ * symbols, ABI 9 unchanged.  out_dev receives 29 words of 8 bytes:
+ *   [0] n_finite, [1] n_nonfinite (inf or NaN)                                                   uint64
+ *   [2] mean, [3] mean of squares, [4] max of the FINITE values (NaN where there is none)         float64
+ *   [5 + k]  n_clipped[k]: values > C_k (compared in float32) plus every non-finite one           uint64
+ *   [13 + k] mean_clip_factor[k]: the mean over ALL n of min(1, C_k / value) in float64; a non-finite value contributes 0, a value
+ *            <= C_k (zero included) 1                                                             float64
+ *   [21 + q] the quantile at position q: with the FINITE values sorted, a = the (lo + 1)-th smallest, b = the next one, the result
+ *            a + (b - a) g where g < 0.5, else b - (b - a) (1 - g), in float64 on the exactly selected values, rounded to float32 once
+ *            and stored as float64 (numpy's method='linear' for lo = floor(h), g = h - lo, h = (n_finite - 1) p, computed by the
+ *            CALLER: call once with Q = 0 to learn n_finite).  NaN where lo + 1 (or lo + 2 with g != 0) exceeds n_finite.
+ * -0 counts as +0.  The selection is a most-significant-digit radix select over an order-preserving image of the float bits: one pass
+ * over the vector per 8-bit digit with all 2 Q ranks in flight, per-workgroup LDS histograms merged with INTEGER atomics; no sort, no
+ * n-sized temporary.  The float64 sums are strip partials merged in strip order, the strip count a function of n alone: two calls
+ * give identical bits.  thresholds_host, lo_host and g_host are host arrays (g in [0, 1), lo < n); n <= 2^40 (D3P_E_UNSUPPORTED). */
+size_t d3p_norm_profile_workspace(uint64_t n);
+int d3p_norm_profile(void* stream, const float* norms_dev, uint64_t n, uint32_t m, const float* thresholds_host, uint32_t Q,
+                     const uint64_t* lo_host, const double* g_host, void* out_dev, void* workspace_dev, size_t workspace_bytes);
+
 /* Multi-particle ELBO gradients (numpyro Trace_ELBO(num_particles=K)) for the logistic-regression / Gaussian-mean models; added
  * symbols, ABI 9 and d3p_logreg_model unchanged.  For example p of a batch of B with the step's jax key: particle q's key is
  * split(split(jax_key, B)[p], K)[q] (K == 1: split(jax_key, B)[p] itself), the guide draws from it as for one particle.  The

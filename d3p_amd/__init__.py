@@ -17,7 +17,7 @@ def __getattr__(name):
     # assignment for the mixture model) and d3p_amd.mixture_density (log predictive density and responsibilities of the mixture model)
     # and d3p_amd.criteria (waic, posterior_waic, compare) and d3p_amd.diagnostics (whole-table log joint, ELBO and the Pareto k of a
     # guide) and d3p_amd.mixture_diagnostics (the same for the mixture model's guide) and d3p_amd.intervals (credible and predictive
-    # intervals, per-column quantiles, the latent summary) and d3p_amd.clipping (whole-table per-example gradient norms and the
+    # intervals, equal-tailed or highest-density, per-column quantiles, the latent summary) and d3p_amd.clipping (whole-table per-example gradient norms and the
     # clipping profile) without making `import d3p_amd` import torch
     if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "diagnostics", "mixture_diagnostics",
                 "intervals", "clipping"):

@@ -1,0 +1,294 @@
+// Highest-density intervals (d3p_amd/intervals.py, include/d3p_hip.h): numpyro.diagnostics.hpdi per column of a
+// draws x cols matrix, d3p_col_hpdi.  Per column of n draws and per window length L (computed by the host as int(prob n)):
+//   s = the draws sorted ascending;  len[i] = s[i + L] - s[i], i = 0 .. n - L - 1;  i* = the first minimum of len (a NaN length is
+//   below every other, np.argmin's rule);  the interval is (s[i*], s[i* + L]).
+// Unlike d3p_col_quantiles, which selects two order statistics, this needs the whole sorted column: the column is sorted in LDS.
+//
+// k_col_hpdi<COLS>: 256 threads, one workgroup owns COLS adjacent columns, thread t = (draw lane t / COLS, column lane t % COLS); the
+// DL = 256 / COLS draw lanes of a column take the draws (pairs, windows) dl, dl + DL, ...
+//   pass 0   every value once from memory, eight loads in flight per thread: the column's NaN flag, and its order-preserving uint32
+//            key (q_key of d3p_quantiles.hip, restated below) into dynamic LDS as [draw][COLS].
+//   sort     a bitonic network in its all-ascending form, in place on the keys: per size k = 2, 4, .. one "flip" step (i against the
+//            mirror position of its block of k) and then the steps at distance k/4, k/8, .. 1 (i against i + j).  Every
+//            compare-exchange puts the smaller key at the lower index, so positions >= n behave as keys above all others that never
+//            move: a compare-exchange whose partner is >= n is skipped and n needs no padding to a power of two.  One barrier per
+//            step; within a step a thread loads the keys of eight of its pairs before it stores any (the pairs are disjoint).
+//   scan     per L one pass over the n - L windows: each draw lane keeps the minimum of (length, i) as ONE uint64 = rank(length) << 32
+//            | i, the column's lanes merge theirs through LDS (a tree of minima: order-independent, so the bits are a function of the
+//            column's values and (n, L) alone).  rank: float32 lengths are >= +0, +inf or NaN (inf - inf): NaN -> 0, else the bits
+//            + 1; int32 lengths are the exact difference of the keys, at most 2^32 - 1.
+// The forms differ only in COLS: 32 (n <= 1152), 8 (n <= 4608), 2 (n <= 18432 = d3p_col_hpdi_max_n()): 4 n COLS bytes of keys within
+// the 144 KiB of dynamic LDS that k_col_quantiles and k_psis_loo use; the widest form that fits is taken.  No streamed form.
+// No floating-point atomics, no scratch, no workspace; a column past the end stands for n draws of 0 and writes nothing.
+//
+// LDS banks: every access is a 4-byte load or store, served in lane groups of 32 over 32 banks.  A group holds G = 32 /
+// COLS draw lanes with consecutive pair (window) numbers.  COLS = 32: a group is one draw's 32 consecutive words, no conflict at any
+// step.  COLS = 8 (G = 4) and COLS = 2 (G = 16): the bank is (index mod G) COLS + column lane; at a distance j >= G the G lower (upper)
+// indices of a group are consecutive, no conflict; at j < G they are runs of j with gaps of j, which fall two by two on the same
+// banks: a 2-way conflict on the loads of those steps (the last log2(G) steps of every size), none in pass 0 or the scan.
+#include "d3p_device.h"
+#include "d3p_host.h"
+
+#include <mutex>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+namespace d3p {
+
+#define D3P_H_MAX 8                   // window lengths per launch
+#define D3P_H_DYN_MAX 147456          // 144 KiB of dynamic LDS: D3P_Q_DYN_MAX of d3p_quantiles.hip
+#define D3P_H_ILP 8                   // pairs of a network step, and loads of pass 0, a thread has in flight
+#define D3P_H_MAX_N(COLS) (D3P_H_DYN_MAX / (4 * (COLS)))   // 1152 | 4608 | 18432
+
+struct HpdiArgs {
+    const uint32_t* m;   // the matrix's words: float32 or int32
+    int32_t dtype;       // 0: float32, 1: int32
+    int64_t ld;
+    uint32_t n;
+    uint64_t cols;
+    uint32_t Q;
+    uint32_t len[D3P_H_MAX];
+    float* out;
+    int64_t out_ld;
+};
+
+// q_key of d3p_quantiles.hip: the order-preserving uint32 image of a stored word.  float32: -0 taken as +0; int32: the sign bit flipped
+__device__ inline uint32_t h_key(uint32_t u, int32_t dtype)
+{
+    if (dtype) return u ^ 0x80000000u;
+    if ((u << 1) == 0u) u = 0u;
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+// the stored value of a key as float32: exact for float32, one rounding for an int32 count above 2^24
+__device__ inline float h_value(uint32_t k, int32_t dtype)
+{
+    if (dtype) return (float)(int32_t)(k ^ 0x80000000u);
+    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+// rank(length of the window lo .. hi) << 32 | i: smaller is better, a NaN length is lowest
+__device__ inline uint64_t h_window(uint32_t klo, uint32_t khi, uint32_t i, int32_t dtype)
+{
+    uint32_t r;
+    if (dtype) {
+        r = khi - klo;                                     // the exact difference: the keys are the values + 2^31
+    } else {
+        const float d = h_value(khi, 0) - h_value(klo, 0);   // one rounding (fp contract is off): >= +0, +inf, or NaN from inf - inf
+        r = d != d ? 0u : __float_as_uint(d) + 1u;
+    }
+    return ((uint64_t)r << 32) | i;
+}
+
+// One step of the network on the keys [n][COLS] of column lane cl, the pairs dl, dl + DL, .. of the step:
+//   FLIP   lg = log2 k:  pair p of block p / (k/2) is (block k + off, block k + k - 1 - off), off = p mod (k/2)
+//   else   lg = log2 j:  pair p is (i, i + j), i = (p / j) 2 j + p mod j
+// The indices rise with p, so the pairs whose lower index (FLIP) or both indices (else) lie below n are a prefix 0 .. cnt - 1; a flip
+// pair whose upper index is >= n is skipped.  The pairs of a step are disjoint: a thread loads the keys of D3P_H_ILP of its pairs
+// before it stores any, which keeps that many LDS loads in flight where the keys fill the LDS and one wave runs per SIMD.
+template <int COLS, bool FLIP>
+__device__ inline void h_step(uint32_t* keys, int cl, uint32_t dl, uint32_t n, uint32_t lg)
+{
+    constexpr uint32_t DL = 256 / COLS;
+    const uint32_t w = 1u << lg;   // FLIP: k, else: j
+    uint32_t cnt;
+    if (FLIP) {
+        const uint32_t h = w >> 1, r = n & (w - 1u);
+        cnt = (n >> lg) * h + (r < h ? r : h);
+    } else {
+        const uint32_t r = n & (2u * w - 1u);
+        cnt = (n >> (lg + 1)) * w + (r > w ? r - w : 0u);
+    }
+    for (uint32_t p0 = dl; p0 < cnt; p0 += D3P_H_ILP * DL) {
+        uint32_t ia[D3P_H_ILP], ib[D3P_H_ILP], ka[D3P_H_ILP], kb[D3P_H_ILP];
+        bool ok[D3P_H_ILP];
+#pragma unroll
+        for (int u = 0; u < D3P_H_ILP; ++u) {
+            const uint32_t p = p0 + (uint32_t)u * DL;
+            if (FLIP) {
+                const uint32_t base = (p >> (lg - 1)) << lg, off = p & ((w >> 1) - 1u);
+                ia[u] = base + off;
+                ib[u] = base + w - 1u - off;
+                ok[u] = p < cnt && ib[u] < n;
+            } else {
+                ia[u] = ((p >> lg) << (lg + 1)) + (p & (w - 1u));
+                ib[u] = ia[u] + w;
+                ok[u] = p < cnt;
+            }
+            ka[u] = kb[u] = 0u;
+            if (ok[u]) {
+                ka[u] = keys[(size_t)ia[u] * COLS + cl];
+                kb[u] = keys[(size_t)ib[u] * COLS + cl];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < D3P_H_ILP; ++u) {
+            if (ok[u] && ka[u] > kb[u]) {
+                keys[(size_t)ia[u] * COLS + cl] = kb[u];
+                keys[(size_t)ib[u] * COLS + cl] = ka[u];
+            }
+        }
+    }
+}
+
+template <int COLS>
+__global__ __launch_bounds__(256) void k_col_hpdi(HpdiArgs a)
+{
+    constexpr int DL = 256 / COLS;
+    extern __shared__ __align__(16) unsigned char h_smem[];
+    uint32_t* keys = reinterpret_cast<uint32_t*>(h_smem);   // [n][COLS]
+    __shared__ uint64_t r_min[256];                         // [draw lane][column lane]
+
+    const int t = threadIdx.x, cl = t & (COLS - 1), dl = t / COLS;
+    const uint32_t n = a.n;
+    const int32_t dtype = a.dtype;
+    const uint64_t c = (uint64_t)blockIdx.x * COLS + cl;
+    const bool live = c < a.cols;                           // a column past the end stands for n draws of 0 and writes nothing
+    const uint32_t* col = a.m + (live ? c : 0);
+    const size_t ld = (size_t)a.ld;
+#define H_KEY(s) keys[(size_t)(s) * COLS + cl]
+
+    // pass 0: the column's NaN flag and its keys; D3P_H_ILP loads from memory in flight per thread
+    uint32_t nan = 0u;
+    for (uint32_t s0 = dl; s0 < n; s0 += D3P_H_ILP * DL) {
+        uint32_t u[D3P_H_ILP];
+#pragma unroll
+        for (int q = 0; q < D3P_H_ILP; ++q) {
+            const uint32_t s = s0 + (uint32_t)q * DL;
+            u[q] = live && s < n ? col[(size_t)s * ld] : 0u;
+        }
+#pragma unroll
+        for (int q = 0; q < D3P_H_ILP; ++q) {
+            const uint32_t s = s0 + (uint32_t)q * DL;
+            if (s < n) {
+                if (!dtype && (u[q] << 1) > 0xff000000u) nan = 1u;
+                H_KEY(s) = h_key(u[q], dtype);
+            }
+        }
+    }
+    r_min[t] = nan;
+    __syncthreads();
+    for (int w = DL / 2; w > 0; w >>= 1) {
+        if (dl < w) r_min[t] |= r_min[t + w * COLS];
+        __syncthreads();
+    }
+    nan = (uint32_t)r_min[cl];
+    __syncthreads();
+
+    // the sort: sizes k = 2^lk while k / 2 < n (positions >= n never move: a partner there is skipped)
+    for (uint32_t lk = 1; (1u << (lk - 1)) < n; ++lk) {
+        h_step<COLS, true>(keys, cl, dl, n, lk);            // flip within blocks of k = 2^lk
+        __syncthreads();
+        for (uint32_t lj = lk - 1; lj-- > 0;) {             // distance 2^lj = k / 4 .. 1
+            h_step<COLS, false>(keys, cl, dl, n, lj);
+            __syncthreads();
+        }
+    }
+
+    for (uint32_t qi = 0; qi < a.Q; ++qi) {
+        const uint32_t L = a.len[qi];                       // L <= n - 1: at least one window
+        uint64_t best = ~0ull;
+        for (uint32_t i = dl; i + L < n; i += DL) {
+            const uint64_t w = h_window(H_KEY(i), H_KEY(i + L), i, dtype);
+            best = w < best ? w : best;
+        }
+        r_min[t] = best;
+        __syncthreads();
+        for (int w = DL / 2; w > 0; w >>= 1) {
+            if (dl < w) {
+                const uint64_t o = r_min[t + w * COLS];
+                if (o < r_min[t]) r_min[t] = o;
+            }
+            __syncthreads();
+        }
+        if (dl == 0 && live) {
+            const uint32_t i = (uint32_t)r_min[t];
+            float* o = a.out + (size_t)(2u * qi) * (size_t)a.out_ld + c;
+            o[0] = nan ? NAN : h_value(H_KEY(i), dtype);
+            o[(size_t)a.out_ld] = nan ? NAN : h_value(H_KEY(i + L), dtype);
+        }
+        __syncthreads();   // (r_min is free for the next length)
+    }
+#undef H_KEY
+}
+
+template <int COLS>
+static int h_dynamic_lds(const char* what)
+{
+    static std::mutex mu;
+    static std::vector<int> done;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    std::lock_guard<std::mutex> lock(mu);
+    for (int d : done)
+        if (d == dev) return D3P_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_col_hpdi<COLS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)D3P_H_DYN_MAX);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(D3P_E_HIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) on device %d: %s", what, dev, hipGetErrorString(e));
+    }
+    done.push_back(dev);
+    return D3P_OK;
+}
+
+template <int COLS>
+static int h_launch(const char* what, hipStream_t stream, const HpdiArgs& a)
+{
+    const uint64_t groups = (a.cols + COLS - 1) / COLS;
+    if (groups > 0x7fffffffull) return fail(D3P_E_UNSUPPORTED, "%s: cols <= %d (2^31 - 1) at n = %u", what, COLS, a.n);
+    const size_t lds = (size_t)COLS * a.n * 4;
+    if (lds > 48u * 1024u)
+        if (int rc = h_dynamic_lds<COLS>(what)) return rc;
+    hipLaunchKernelGGL((k_col_hpdi<COLS>), dim3((unsigned)groups), dim3(256), lds, stream, a);
+    return check_launch(what);
+}
+
+static inline bool h_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+}  // namespace d3p
+
+using namespace d3p;
+
+extern "C" {
+
+uint32_t d3p_col_hpdi_max_n(void) { return (uint32_t)D3P_H_MAX_N(2); }
+
+uint32_t d3p_col_hpdi_cols_per_group(uint32_t n)
+{
+    if (n < 1 || n > (uint32_t)D3P_H_MAX_N(2)) return 0u;
+    return n <= (uint32_t)D3P_H_MAX_N(32) ? 32u : n <= (uint32_t)D3P_H_MAX_N(8) ? 8u : 2u;
+}
+
+int d3p_col_hpdi(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uint32_t n, uint64_t cols, uint32_t Q, const uint32_t* len_host,
+                 float* out_dev, int64_t out_ld)
+{
+    const char* what = "d3p_col_hpdi";
+    if (!m_dev || !out_dev || !len_host) return fail(D3P_E_INVALID_ARG, "%s: null pointer", what);
+    if (!h_aligned(m_dev) || !h_aligned(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
+    if (dtype != 0 && dtype != 1) return fail(D3P_E_INVALID_ARG, "%s: dtype must be 0 (float32) or 1 (int32), got %d", what, dtype);
+    if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n >= 1 is required", what);
+    if (Q < 1 || Q > D3P_H_MAX) return fail(D3P_E_INVALID_ARG, "%s: 1 <= Q <= 8 (Q = %u)", what, Q);
+    if (is_device_ptr(len_host)) return fail(D3P_E_INVALID_ARG, "%s: len_host must be host memory", what);
+    HpdiArgs a;
+    for (uint32_t q = 0; q < Q; ++q) {
+        if (len_host[q] >= n) return fail(D3P_E_INVALID_ARG, "%s: len[%u] = %u is not below n = %u", what, q, len_host[q], n);
+        a.len[q] = len_host[q];
+    }
+    for (uint32_t q = Q; q < D3P_H_MAX; ++q) a.len[q] = 0u;
+    if (ld < 0 || (uint64_t)ld < cols) return fail(D3P_E_INVALID_ARG, "%s: ld >= cols is required", what);
+    if (out_ld < 0 || (uint64_t)out_ld < cols) return fail(D3P_E_INVALID_ARG, "%s: out_ld >= cols is required", what);
+    const uint32_t form = d3p_col_hpdi_cols_per_group(n);
+    if (!form)
+        return fail(D3P_E_UNSUPPORTED, "%s: n = %u draws; the column is sorted in LDS and n <= %u is served (there is no streamed form)", what, n,
+                    d3p_col_hpdi_max_n());
+    if (cols == 0) return D3P_OK;
+    if (!is_device_ptr(m_dev) || !is_device_ptr(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: the matrix and the output must be device memory", what);
+    a.m = static_cast<const uint32_t*>(m_dev); a.dtype = dtype; a.ld = ld; a.n = n; a.cols = cols; a.Q = Q; a.out = out_dev; a.out_ld = out_ld;
+    if (form == 32u) return h_launch<32>(what, (hipStream_t)stream, a);
+    if (form == 8u) return h_launch<8>(what, (hipStream_t)stream, a);
+    return h_launch<2>(what, (hipStream_t)stream, a);
+}
+
+}  // extern "C"

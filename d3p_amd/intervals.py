@@ -2,11 +2,12 @@
 posterior draws.
 
     quantiles(matrix, probs)                                                                      -> (Q, cols) float32
-    credible_interval(model, posterior_samples, X[, y[, N]], prob=0.9, probs=None, slab_bytes=64 << 20)
-    posterior_credible_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20)
-    predictive_interval(rng_key, model, posterior_samples, X[, y[, N]], prob=0.9, probs=None, slab_bytes=64 << 20)
-    posterior_predictive_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20)
-    latent_summary(posterior_samples, prob=0.9)                             -> {site: {"mean", "std", "median", "lower", "upper"}}
+    hpdi(matrix, prob=0.9)                                                   -> (2, cols) float32, or (Q, 2, cols) for Q probabilities
+    credible_interval(model, posterior_samples, X[, y[, N]], prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed")
+    posterior_credible_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed")
+    predictive_interval(rng_key, model, posterior_samples, X[, y[, N]], prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed")
+    posterior_predictive_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed")
+    latent_summary(posterior_samples, prob=0.9, interval="equal_tailed")    -> {site: {"mean", "std", "median", "lower", "upper"}}
 
 The interval functions return ``{"lower": (rows,), "median": (rows,), "upper": (rows,)}`` float32 on the GPU at the probabilities
 ``((1 - prob) / 2, 0.5, (1 + prob) / 2)``, the equal-tailed interval; with ``probs`` (1 to 8 floats in [0, 1]) they return
@@ -19,6 +20,16 @@ that the device does no arithmetic on ``p`` -- the result lies between the (lo+1
 ``a + (b - a) g`` where ``g < 0.5``, else ``b - (b - a) (1 - g)``, in float64 on the exactly selected values, rounded to float32 once
 (an int32 count above 2^24 therefore rounds).  -0 and +0 are one value; a NaN in a column makes the column's outputs NaN; between
 ``-inf`` and ``+inf`` the result is NaN, between a finite value and an infinity that infinity.  ``n <= 65535``.
+
+``hpdi`` is the highest-density interval (``d3p_col_hpdi``, ``d3p_amd/csrc/d3p_hpdi.hip``), the rule of
+``numpyro.diagnostics.hpdi(x, prob, axis=0)`` and so the "5.0%" / "95.0%" columns of numpyro's ``print_summary``: with the column sorted
+ascending as ``s`` and ``L = int(prob * n)`` -- computed HERE, in Python floats -- the narrowest window ``(s[i], s[i + L])``, the first
+of equal ones.  Both ends are stored values (an int32 count is cast to float32 once); a float32 width is the float32 difference, an int32
+width the exact one; a NaN width (``inf - inf``) is the narrowest, as for ``np.argmin``; -0 and +0 are one value; a NaN in a column
+makes both ends NaN.  The column is sorted in LDS, which bounds the draws: ``n <= d3p_col_hpdi_max_n()`` = 18432, a ``ValueError``
+above.  The four interval functions take ``kind="hpdi"`` and then return ``{"lower", "upper"}`` at ``prob`` (``probs`` is refused);
+``latent_summary`` takes ``interval="hpdi"``: ``lower`` and ``upper`` from ``d3p_col_hpdi``, ``median`` still from
+``d3p_col_quantiles``.  Slabs are as below: the reducer is the only difference.
 
 ``credible_interval`` is over ``mu[s, r] = E[y | x_r, draw s] = sigmoid(t) | t | exp(t)``, the uncertainty of the regression function
 (``LogisticRegression | LinearRegression | PoissonRegression``; ``t`` and the link exactly as ``d3p_amd.prediction`` forms them).
@@ -52,11 +63,12 @@ from . import prediction as PM
 from . import predictive as PS
 from ._lib import check, ptr, stream_ptr
 
-__all__ = ["quantiles", "credible_interval", "posterior_credible_interval", "predictive_interval", "posterior_predictive_interval",
+__all__ = ["quantiles", "hpdi", "credible_interval", "posterior_credible_interval", "predictive_interval", "posterior_predictive_interval",
            "latent_summary"]
 
 MAX_PROBS = 8
 MAX_DRAWS = 65535
+KINDS = ("equal_tailed", "hpdi")
 
 
 def _family(model, what):
@@ -101,6 +113,47 @@ def _check_draws(n, what):
         raise ValueError(f"{what}: {n} draws; the quantile kernel runs at most {MAX_DRAWS} draws (n <= {MAX_DRAWS})")
 
 
+def _kind(kind, probs, name="kind"):
+    """True for the highest-density interval.  An unknown kind is an error, and so is `probs` with kind='hpdi'."""
+    if not isinstance(kind, str) or kind not in KINDS:
+        raise ValueError(f"{name} must be one of {KINDS}, got {kind!r}")
+    if kind == "hpdi" and probs is not None:
+        raise ValueError(f"probs cannot be combined with {name}='hpdi': a highest-density interval is given by prob alone")
+    return kind == "hpdi"
+
+
+def _hpdi_prob(prob):
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 < float(prob) < 1.0:
+        raise ValueError(f"prob must be a float in (0, 1), got {prob!r}")
+    return float(prob)
+
+
+def window_lengths(probs, n):
+    """[L] of the probabilities over n draws: L = int(prob n) in Python floats, numpyro.diagnostics.hpdi's window length."""
+    return [int(float(p) * n) for p in probs]
+
+
+def hpdi_max_draws():
+    """d3p_col_hpdi_max_n(): the largest draw count whose column is sorted in LDS (host only: no device is touched)."""
+    return int(_lib.load().d3p_col_hpdi_max_n())
+
+
+def _check_hpdi_draws(n, what):
+    most = hpdi_max_draws()
+    if n > most:
+        raise ValueError(f"{what}: {n} draws; the highest-density interval sorts a column in LDS and runs at most {most} draws (n <= {most})")
+
+
+def _reduce_hpdi(first, dtype, ld, n, cols, lens, out, out_ld):
+    """d3p_col_hpdi on the (n, cols) matrix that starts at tensor `first`, into out (2 len(lens) rows: lower, upper per length)."""
+    Q = len(lens)
+    check(_lib.load().d3p_col_hpdi(stream_ptr(), ptr(first), 0 if dtype == torch.float32 else 1, ld, n, cols, Q, (C.c_uint32 * Q)(*lens), ptr(out), out_ld))
+
+
+def _ends(q):
+    return {"lower": q[0], "upper": q[1]}
+
+
 def _reduce(first, dtype, ld, n, cols, pos, out, out_ld):
     """d3p_col_quantiles on the (n, cols) matrix that starts at tensor `first`, into out (a tensor at the first output element)."""
     Q = len(pos)
@@ -138,53 +191,100 @@ def quantiles(matrix, probs):
     return out
 
 
-def _mean_slabs(model, fam, X, rows, d, n, latent, pos, chunk):
-    """(Q, rows) float32: the quantiles of mu[:, r] over the draws, the n x rows matrix written and reduced in row slabs of `chunk`."""
+def hpdi(matrix, prob=0.9):
+    """The highest-density interval of every column of ``matrix`` -- as for ``quantiles``: a 2-D CUDA tensor ``(draws, cols)``, float32
+    or int32, any row stride, unit column stride -- numpyro's ``hpdi(x, prob, axis=0)`` (module docstring).  A float ``prob`` in (0, 1)
+    returns ``(2, cols)`` float32, lower and upper; a sequence of 1 to 8 such floats ``(Q, 2, cols)``, all from one sort."""
+    if isinstance(prob, (int, float)):
+        ps, single = (_hpdi_prob(prob),), True
+    else:
+        try:
+            ps = tuple(prob)
+        except TypeError:
+            raise ValueError(f"prob must be a float in (0, 1) or a sequence of 1 to {MAX_PROBS} of them, got {prob!r}") from None
+        if not 1 <= len(ps) <= MAX_PROBS:
+            raise ValueError(f"prob: 1 to {MAX_PROBS} probabilities per call, got {len(ps)}")
+        ps, single = tuple(_hpdi_prob(p) for p in ps), False
+    if not isinstance(matrix, torch.Tensor) or matrix.dim() != 2 or matrix.dtype not in (torch.float32, torch.int32) or not matrix.is_cuda:
+        raise ValueError("hpdi: a 2-D float32 or int32 CUDA tensor (draws, cols) is required")
+    n, cols = int(matrix.shape[0]), int(matrix.shape[1])
+    if cols > 1 and matrix.stride(1) != 1:
+        raise ValueError("hpdi: the matrix's columns must have unit stride (rows may be strided)")
+    if n < 1:
+        raise ValueError("hpdi: at least one draw")
+    _check_hpdi_draws(n, "hpdi")
+    ld = int(matrix.stride(0)) if n > 1 else cols
+    if ld < cols:
+        raise ValueError("hpdi: the matrix's rows overlap (row stride below the column count)")
+    lens = window_lengths(ps, n)
+    _lib.require_device()   # (every check above runs without a device)
+    with torch.cuda.device(matrix.device):
+        out = torch.empty((2 * len(ps), cols), dtype=torch.float32, device=matrix.device)
+        if cols:
+            _reduce_hpdi(matrix, matrix.dtype, ld, n, cols, lens, out, cols)
+    return out if single else out.reshape(len(ps), 2, cols)
+
+
+def _mean_slabs(model, fam, X, rows, d, n, latent, pos, chunk, reduce=_reduce, out_rows=None):
+    """(Q, rows) float32: the quantiles of mu[:, r] over the draws, the n x rows matrix written and reduced in row slabs of `chunk`.
+    With reduce=_reduce_hpdi and out_rows = 2 len(pos), pos holds window lengths and the result the intervals' ends."""
     first, ld, w_off, b_col = latent
     X = M._f32(X, "X")
     lib = _lib.load()
     ms = U._model_struct(model, fam, d)
-    out = torch.empty((len(pos), rows), dtype=torch.float32, device=X.device)
+    out = torch.empty((len(pos) if out_rows is None else out_rows, rows), dtype=torch.float32, device=X.device)
     buf = torch.empty((n * min(chunk, rows),), dtype=torch.float32, device=X.device)
     for lo in range(0, rows, chunk):
         count = min(chunk, rows - lo)
         check(lib.d3p_predict_mean_rows(stream_ptr(), C.byref(ms), ptr(X[lo:lo + count]), count, ptr(first), ld, w_off, b_col, n, ptr(buf), count))
-        _reduce(buf, torch.float32, count, n, count, pos, out[0, lo:], rows)
+        reduce(buf, torch.float32, count, n, count, pos, out[0, lo:], rows)
     return out
 
 
-def credible_interval(model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+_HPDI_SLABS = {"reduce": _reduce_hpdi, "out_rows": 2}
+
+
+def credible_interval(model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed", **kwargs):
     """The equal-tailed ``prob`` interval and the median of ``mu[s, r] = E[y | x_r, draw s]`` over given posterior draws, per row:
     ``{"lower", "median", "upper"}`` (or ``{"quantiles"}`` with ``probs``), float32 on the GPU (module docstring).
 
     ``model_args = (X[, y[, N]])``; ``y`` and ``N`` are accepted and not read.  ``posterior_samples = {"w": (n, d)[, "intercept":
-    (n,) or (n, 1)]}`` as for ``predictive_moments``: packed views are read in place, everything else is packed once."""
+    (n,) or (n, 1)]}`` as for ``predictive_moments``: packed views are read in place, everything else is packed once.
+    ``kind="hpdi"``: the highest-density interval at ``prob`` instead, ``{"lower", "upper"}``."""
     fam = _family(model, "credible_interval")
-    ps, names = _probs(prob, probs)
+    hp = _kind(kind, probs)
+    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
     rows, d = PM._data(model, model_args)
     n, _ = U._sample_shape(model, posterior_samples, d)
     _check_draws(n, "credible_interval")
+    if hp:
+        _check_hpdi_draws(n, "credible_interval")
     chunk = U._loo_chunk(n, slab_bytes)
     if chunk is None:
         raise ValueError("slab_bytes must be an int >= 1, got None")
-    pos = positions(ps, n)
+    pos = window_lengths(ps, n) if hp else positions(ps, n)
     _lib.require_device()   # (every check above runs without a device)
     with torch.cuda.device(M._device()):
-        q = _mean_slabs(model, fam, model_args[0], rows, d, n, U._pack(model, posterior_samples, n, d), pos, chunk)
-    return _result(q, names)
+        q = _mean_slabs(model, fam, model_args[0], rows, d, n, U._pack(model, posterior_samples, n, d), pos, chunk,
+                        **(_HPDI_SLABS if hp else {}))
+    return _ends(q) if hp else _result(q, names)
 
 
-def posterior_credible_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+def posterior_credible_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed",
+                                **kwargs):
     """``credible_interval`` over ``n`` draws from the guide at ``params`` (as ``DPSVI.get_params`` returns them), drawn on the device on
     ``posterior_predictive_moments``' key rule and consumed there.  Guides: ``AutoDiagonalNormal``, ``DiagonalNormalGuide``;
     ``MeanFieldGuide`` for logistic regression."""
     fam = _family(model, "posterior_credible_interval")
     U._check_guide(model, guide)
-    ps, names = _probs(prob, probs)
+    hp = _kind(kind, probs)
+    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
     n = int(n)
     if n < 1:
         raise ValueError("n must be >= 1")
     _check_draws(n, "posterior_credible_interval")
+    if hp:
+        _check_hpdi_draws(n, "posterior_credible_interval")
     rows, d = PM._data(model, model_args)
     chunk = U._loo_chunk(n, slab_bytes)
     if chunk is None:
@@ -193,13 +293,13 @@ def posterior_credible_interval(rng_key, n, model, model_args, guide, params, pr
         raise ValueError("params: the dict DPSVI.get_params returns is required")
     gparams = [(name, M._param(params, name, size)) for name, size in M._guide_param_names(guide, model, d)]
     key = M._check_key(rng_key)
-    pos = positions(ps, n)
+    pos = window_lengths(ps, n) if hp else positions(ps, n)
     _lib.require_device()
     dev = key.device
     with torch.cuda.device(dev):
         latent = U._guide_latents(key, n, model, guide, gparams, d, rows, dev)
-        q = _mean_slabs(model, fam, model_args[0], rows, d, n, latent, pos, chunk)
-    return _result(q, names)
+        q = _mean_slabs(model, fam, model_args[0], rows, d, n, latent, pos, chunk, **(_HPDI_SLABS if hp else {}))
+    return _ends(q) if hp else _result(q, names)
 
 
 def _predictive_family(model, what):
@@ -219,51 +319,61 @@ def _check_whole(n, rows, slab_bytes, what):
                          f"slab_bytes >= {need}, got {slab_bytes}")
 
 
-def _reduce_obs(obs, n, rows, pos, names):
+def _reduce_obs(obs, n, rows, pos, names, hp=False):
     obs = obs.reshape(n, rows)
     with torch.cuda.device(obs.device):
-        q = torch.empty((len(pos), rows), dtype=torch.float32, device=obs.device)
-        _reduce(obs, obs.dtype, rows, n, rows, pos, q, rows)
-    return _result(q, names)
+        q = torch.empty((2 if hp else len(pos), rows), dtype=torch.float32, device=obs.device)
+        (_reduce_hpdi if hp else _reduce)(obs, obs.dtype, rows, n, rows, pos, q, rows)
+    return _ends(q) if hp else _result(q, names)
 
 
-def predictive_interval(rng_key, model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+def predictive_interval(rng_key, model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed", **kwargs):
     """The equal-tailed ``prob`` interval and the median of the outcomes ``obs`` over given posterior draws, per row: the quantiles of
     what ``predictive_samples(rng_key, model, posterior_samples, *model_args)`` returns, without that matrix leaving the device.
-    ``LinearRegression`` and ``PoissonRegression``; the matrix is written whole and must fit ``slab_bytes`` (module docstring)."""
+    ``LinearRegression`` and ``PoissonRegression``; the matrix is written whole and must fit ``slab_bytes`` (module docstring).
+    ``kind="hpdi"``: the highest-density interval at ``prob`` instead, ``{"lower", "upper"}``."""
     _predictive_family(model, "predictive_interval")
-    ps, names = _probs(prob, probs)
+    hp = _kind(kind, probs)
+    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
     rows, d = PS._data(model, model_args, kwargs)
     n, _ = U._sample_shape(model, posterior_samples, d)
     _check_draws(n, "predictive_interval")
+    if hp:
+        _check_hpdi_draws(n, "predictive_interval")
     _check_whole(n, rows, slab_bytes, "predictive_interval")
     M._check_key(rng_key)
-    pos = positions(ps, n)
+    pos = window_lengths(ps, n) if hp else positions(ps, n)
     obs = PS.predictive_samples(rng_key, model, posterior_samples, *model_args, **kwargs)
-    return _reduce_obs(obs, n, rows, pos, names)
+    return _reduce_obs(obs, n, rows, pos, names, hp)
 
 
-def posterior_predictive_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, **kwargs):
+def posterior_predictive_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed",
+                                  **kwargs):
     """``predictive_interval`` over ``n`` draws from the posterior predictive at ``params``: the quantiles of the ``obs`` that
     ``posterior_predictive_samples(rng_key, n, model, model_args, guide, params)`` returns for the same key."""
     _predictive_family(model, "posterior_predictive_interval")
     U._check_guide(model, guide)
-    ps, names = _probs(prob, probs)
+    hp = _kind(kind, probs)
+    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
     n = PS._count(n)
     _check_draws(n, "posterior_predictive_interval")
+    if hp:
+        _check_hpdi_draws(n, "posterior_predictive_interval")
     rows, d = PS._data(model, model_args, kwargs)
     _check_whole(n, rows, slab_bytes, "posterior_predictive_interval")
-    pos = positions(ps, n)
+    pos = window_lengths(ps, n) if hp else positions(ps, n)
     obs = PS.posterior_predictive_samples(rng_key, n, model, model_args, guide, params, **kwargs)["obs"]
-    return _reduce_obs(obs, n, rows, pos, names)
+    return _reduce_obs(obs, n, rows, pos, names, hp)
 
 
-def latent_summary(posterior_samples, prob=0.9):
+def latent_summary(posterior_samples, prob=0.9, interval="equal_tailed"):
     """Per site of ``posterior_samples`` (``w``, ``intercept``; each viewed as an ``n x D`` matrix of draws): ``{"mean", "std", "median",
     "lower", "upper"}``, each of the site's shape without the draw axis -- the columns of numpyro's ``print_summary`` without ``n_eff``
     and ``r_hat``, which are meaningless for independent draws from a guide.  ``mean`` and ``std`` are float64 from ``d3p_col_stats``
     (the ``n - 1`` variance: ``n == 1`` gives a NaN ``std``); the three quantiles are float32 from ``d3p_col_quantiles`` at ``((1 -
-    prob) / 2, 0.5, (1 + prob) / 2)``."""
+    prob) / 2, 0.5, (1 + prob) / 2)``.  ``interval="hpdi"``: ``lower`` and ``upper`` are the highest-density interval at ``prob`` from
+    ``d3p_col_hpdi`` -- what ``print_summary`` reports -- and ``median`` still comes from ``d3p_col_quantiles``."""
+    hp = _kind(interval, None, "interval")
     ps, names = _probs(prob, None)
     if not isinstance(posterior_samples, dict) or not posterior_samples:
         raise ValueError("posterior_samples: a dict of sites (n draws each) is required")
@@ -273,6 +383,8 @@ def latent_summary(posterior_samples, prob=0.9):
         if len(shp) < 1 or shp[0] < 1 or M._numel(v) == 0:
             raise ValueError(f"posterior_samples['{name}']: at least one draw along the first axis is required")
         _check_draws(shp[0], "latent_summary")
+        if hp:
+            _check_hpdi_draws(shp[0], "latent_summary")
         shapes[name] = shp
     _lib.require_device()   # (every check above runs without a device)
     lib = _lib.load()
@@ -293,8 +405,12 @@ def latent_summary(posterior_samples, prob=0.9):
                 stats = torch.empty((4, cols), dtype=torch.float64, device=m.device)
                 check(lib.d3p_col_stats(stream_ptr(), ptr(m), ld, n, cols, ptr(stats)))
                 q = torch.empty((3, cols), dtype=torch.float32, device=m.device)
-                _reduce(m, torch.float32, ld, n, cols, positions(ps, n), q, cols)
+                if hp:   # rows 0 and 1: the interval's ends; row 2: the median
+                    _reduce_hpdi(m, torch.float32, ld, n, cols, window_lengths((float(prob),), n), q, cols)
+                    _reduce(m, torch.float32, ld, n, cols, positions(ps[1:2], n), q[2], cols)
+                else:
+                    _reduce(m, torch.float32, ld, n, cols, positions(ps, n), q, cols)
         site = {"mean": stats[0], "std": torch.sqrt(stats[1])}
-        site.update({nm: q[i] for i, nm in enumerate(names)})
+        site.update({nm: q[i] for i, nm in enumerate(("lower", "upper", "median") if hp else names)})
         out[name] = {k: t.reshape(shp[1:]) for k, t in site.items()}
     return out

@@ -19,6 +19,9 @@ their effective sample size (Yao et al. 2018: is the trained guide a usable appr
 --intervals [N_DRAWS] (off by default; d3p_amd.intervals) adds, after training: the share of the observed counts inside the equal-tailed
 90 % posterior predictive interval of N_DRAWS draws, the interval's mean width, and mean, std, median and the 5 % / 95 % quantiles of
 the draws of every weight.
+--interval-kind {equal-tailed,hpdi} (default equal-tailed; read only with --intervals): with hpdi the coverage and width lines are those
+of the 90 % highest-density interval (numpyro's hpdi, kind="hpdi") and the summary of `w` reports that interval's ends
+(latent_summary(interval="hpdi")), as numpyro's print_summary does; the lines say which kind they are.
 
 --clipping-profile (off by default; d3p_amd.clipping) adds two lines after training: the quantiles of the per-example gradient norms of
 the whole table at the trained parameters, the share of rows the run's clipping threshold clips with the mean clip factor, and the
@@ -95,22 +98,25 @@ def guide_diagnostic_report(model, svi, state, X, y, num_draws, seed=3):
                                  float(res.pareto_k), res.k_threshold, float(res.ess))
 
 
-def intervals_report(model, svi, state, X, y, num_draws, seed=4):
+def intervals_report(model, svi, state, X, y, num_draws, seed=4, kind="equal_tailed"):
     """The lines of --intervals (d3p_amd.intervals): the share of the observed y inside the equal-tailed 90 % posterior predictive
-    interval of num_draws draws from the trained guide, the interval's mean width, and the summary of the draws of `w`."""
+    interval of num_draws draws from the trained guide, the interval's mean width, and the summary of the draws of `w`.
+    kind="hpdi" (--interval-kind hpdi): the same of the highest-density interval, and the lines say so."""
     from d3p_amd import intervals
     from d3p_amd.predictive import posterior_predictive_samples
     import d3p_amd.random.debug as jax_random
     key, params = jax_random.PRNGKey(seed), svi.get_params(state)
-    iv = intervals.posterior_predictive_interval(key, num_draws, model, (X,), svi.guide, params, prob=0.9)
+    hp = kind == "hpdi"
+    iv = intervals.posterior_predictive_interval(key, num_draws, model, (X,), svi.guide, params, prob=0.9, **({"kind": "hpdi"} if hp else {}))
     inside = ((y >= iv["lower"]) & (y <= iv["upper"])).double().mean()
     width = (iv["upper"].double() - iv["lower"].double()).mean()
-    lines = ["90% predictive interval ({} rows, {} draws): coverage {:.4f}, mean width {:.4f}".format(
-        X.shape[0], num_draws, float(inside), float(width))]
+    lines = ["90% {}predictive interval ({} rows, {} draws): coverage {:.4f}, mean width {:.4f}".format(
+        "highest-density " if hp else "", X.shape[0], num_draws, float(inside), float(width))]
     draws = posterior_predictive_samples(key, num_draws, model, (X[:1],), svi.guide, params)   # (the same latents: they take no row)
-    s = {k: v.double().cpu() for k, v in intervals.latent_summary({"w": draws["w"]}, prob=0.9)["w"].items()}
+    s = {k: v.double().cpu() for k, v in intervals.latent_summary({"w": draws["w"]}, prob=0.9, **({"interval": "hpdi"} if hp else {}))["w"].items()}
+    ends = "90% hpdi {:.4f} .. {:.4f}" if hp else "5% {:.4f}, 95% {:.4f}"
     for j in range(s["mean"].shape[0]):
-        lines.append("w[{}]: mean {:.4f}, std {:.4f}, median {:.4f}, 5% {:.4f}, 95% {:.4f}".format(
+        lines.append(("w[{}]: mean {:.4f}, std {:.4f}, median {:.4f}, " + ends).format(
             j, float(s["mean"][j]), float(s["std"][j]), float(s["median"][j]), float(s["lower"][j]), float(s["upper"][j])))
     return lines
 
@@ -178,7 +184,8 @@ def main(args):
     if getattr(args, "guide_diagnostic", None) is not None:
         print(guide_diagnostic_report(model, svi, state, X, y, args.guide_diagnostic))
     if getattr(args, "intervals", None) is not None:
-        print("\n".join(intervals_report(model, svi, state, X, y, args.intervals)))
+        kind = (getattr(args, "interval_kind", None) or "equal-tailed").replace("-", "_")
+        print("\n".join(intervals_report(model, svi, state, X, y, args.intervals, kind=kind)))
     if getattr(args, "clipping_profile", False):
         print("\n".join(clipping_profile_report(svi, state, X, y)))
     return first, last, err0, err
@@ -204,6 +211,8 @@ if __name__ == "__main__":
     parser.add_argument('--intervals', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, report the coverage and the mean width of the 90 %% posterior predictive interval of '
                              'N_DRAWS (default 100) draws on the whole table, and the summary of the draws of w')
+    parser.add_argument('--interval-kind', choices=('equal-tailed', 'hpdi'), default='equal-tailed',
+                        help='with --intervals: the equal-tailed interval (quantiles) or the highest-density interval (numpyro hpdi)')
     parser.add_argument('--clipping-profile', action='store_true',
                         help='after training, report the quantiles of the per-example gradient norms on the whole table, the share of '
                              'rows the clipping threshold clips and the suggested threshold (a diagnostic of the private table, not a release)')

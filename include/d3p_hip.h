@@ -1090,6 +1090,34 @@ int d3p_col_quantiles(void* stream, const void* m_dev, int32_t dtype, int64_t ld
 /* the largest n whose keys d3p_col_quantiles stages in LDS (host only, no device call) */
 uint32_t d3p_col_quantiles_staged_max(void);
 
+/* Highest-density intervals per column of a draws x cols matrix m_dev[s * ld + c] of float32 (dtype 0) or int32 (dtype 1) values
+ * (model-free; d3p_amd/intervals.py; d3p_hpdi.hip); added symbols, ABI 9 unchanged.  The rule is
+ * numpyro.diagnostics.hpdi(x, prob, axis=0), per column of n draws and per window length L = len_host[q] (the HOST computes L =
+ * int(prob n), the device does no arithmetic on prob; 0 <= L <= n - 1):
+ *   s = the draws sorted ascending;  len[i] = s[i + L] - s[i] for i = 0 .. n - L - 1;  i* = argmin(len), the first minimum;
+ *   out_dev[(2 q) * out_ld + c] = s[i*] (the lower end),  out_dev[(2 q + 1) * out_ld + c] = s[i* + L] (the upper end), float32.
+ * Both ends are STORED values: no interpolation, and no rounding for float32 input; an int32 count is cast to float32 once (above 2^24
+ * in magnitude it rounds to the nearest float32, as d3p_col_quantiles' does).  The order is that of d3p_col_quantiles' uint32 key
+ * (float32: -0 taken as +0, so a zero end is +0; int32: the sign bit flipped).  A float32 length is the float32 difference s[i + L] -
+ * s[i], one rounding, no contraction -- what numpy computes on a float32 array; an int32 length is the exact integer difference.
+ * Ties: the smallest i among the minimal lengths.  A NaN length (inf - inf) is below every other length and the first one wins --
+ * np.argmin's rule: [-inf, -inf, 1, 2, inf, inf] gives i* = 0 at every L.  A NaN anywhere in a float32 column makes all 2 Q outputs of
+ * that column NaN and touches no other column (the rule of d3p_col_quantiles, not numpy's sort-last).
+ * One sort serves all Q lengths.  The column's n keys are sorted in LDS (bitonic network, all-ascending form, exact), one workgroup
+ * per d3p_col_hpdi_cols_per_group(n) adjacent columns: 32 (n <= 1152), 8 (n <= 4608), 2 (n <= 18432 = d3p_col_hpdi_max_n()).  There
+ * is no streamed form: a larger n is D3P_E_UNSUPPORTED.  Deterministic: no floating-point atomics, no workspace, no host
+ * synchronisation; a column's output bits depend on that column's values and on (n, L) alone -- not on ld, out_ld, the other columns
+ * of the launch or the form.
+ * D3P_E_INVALID_ARG before any launch: n < 1, Q outside 1 <= Q <= 8, a len >= n, ld < cols, out_ld < cols, a dtype other than 0 / 1, a
+ * null pointer, m_dev or out_dev not aligned to 4 bytes or not device memory, len_host not host memory (Q values).  n >
+ * d3p_col_hpdi_max_n(), or more than 2^31 - 1 column groups: D3P_E_UNSUPPORTED; cols == 0: D3P_OK, no launch. */
+int d3p_col_hpdi(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uint32_t n, uint64_t cols, uint32_t Q, const uint32_t* len_host,
+                 float* out_dev, int64_t out_ld);
+/* the largest n d3p_col_hpdi serves: 18432 (host only, no device call) */
+uint32_t d3p_col_hpdi_max_n(void);
+/* the columns one workgroup of d3p_col_hpdi owns at n draws: 32, 8, 2, or 0 where n is not served (host only, no device call) */
+uint32_t d3p_col_hpdi_cols_per_group(uint32_t n);
+
 /* The conditional mean of the observed site over given posterior draws, as an n x rows matrix (d3p_amd/intervals.py: the matrix
  * d3p_col_quantiles reduces for a credible interval); added symbol, ABI 9 and d3p_logreg_model unchanged.  With t[s, r] as for
  * d3p_loglik_rows:

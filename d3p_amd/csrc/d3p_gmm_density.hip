@@ -55,12 +55,8 @@
 //   out[s]     = the strip sums added in ascending strip order, starting from strip 0's (k_gmm_draw_sums_merge, a second launch).
 // No floating-point atomics, no arrival order; a draw's sum does not depend on the other draws of the launch.  Nothing is clamped:
 // a draw with ll = -inf in some row sums to -inf, a NaN row of obs makes every draw NaN, a NaN in a draw's latents that draw only.
-#include <mutex>
-#include <utility>
-#include <vector>
-
+#include "d3p_colreduce.h"
 #include "d3p_device.h"
-#include "d3p_host.h"
 #include "d3p_shifted_sums.h"
 
 namespace d3p {
@@ -289,27 +285,6 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
     }
 }
 
-static inline bool gd_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-
-// the attribute is per function and per device (d3p_dpvi.hip's ensure_dynamic_lds, restated: that file's text is pinned)
-static int gd_dynamic_lds(const void* fn, const char* what)
-{
-    static std::mutex mu;
-    static std::vector<std::pair<const void*, int>> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    std::lock_guard<std::mutex> lock(mu);
-    for (const auto& e : done)
-        if (e.first == fn && e.second == dev) return D3P_OK;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)D3P_GD_LDS_MAX);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(D3P_E_HIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize, %d) on device %d: %s", what, (int)D3P_GD_LDS_MAX, dev, hipGetErrorString(e));
-    }
-    done.emplace_back(fn, dev);
-    return D3P_OK;
-}
-
 // four waves split the draws where their four latent copies fit beside the row tile, otherwise two: a function of (k, d) alone.
 // Returns the bytes of LDS of the staging.
 static size_t gd_waves(int k, int d, int* W)
@@ -327,7 +302,7 @@ template <int KMAX, int REDUCE>
 static int gd_launch(const char* what, hipStream_t s, const GmmDensityArgs& g, int W, size_t lds, uint32_t grid)
 {
     const void* fn = reinterpret_cast<const void*>(&k_gmm_density<KMAX, REDUCE>);
-    if (int rc = gd_dynamic_lds(fn, what)) return rc;
+    if (int rc = dynamic_lds_opt_in(fn, D3P_GD_LDS_MAX, what)) return rc;
     hipLaunchKernelGGL((k_gmm_density<KMAX, REDUCE>), dim3(grid), dim3(64 * W), lds, s, g);
     return check_launch(what);
 }
@@ -340,7 +315,7 @@ static int gd_entry(const char* what, void* stream, const float* obs, uint64_t r
     if (REDUCE == 2 && (!lppd || !pwaic)) return fail(D3P_E_INVALID_ARG, "%s: null lppd / pwaic pointer", what);
     if (REDUCE ? (!lppd && !resp) : !ll)
         return fail(D3P_E_INVALID_ARG, REDUCE ? "%s: at least one of the two outputs is required" : "%s: null output pointer", what);
-    if (!gd_aligned(obs) || !gd_aligned(latent) || !gd_aligned(ll) || !gd_aligned(lppd) || !gd_aligned(resp) || !gd_aligned(pwaic))
+    if (!aligned4(obs) || !aligned4(latent) || !aligned4(ll) || !aligned4(lppd) || !aligned4(resp) || !aligned4(pwaic))
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (k < 1 || d < 1) return fail(D3P_E_INVALID_ARG, "%s: k and d must be >= 1 (k = %d, d = %d)", what, k, d);
     if (k > 32 || d > 256 || (k > 16 && d > 128))
@@ -429,7 +404,7 @@ int d3p_gmm_loglik_draw_sums(void* stream, const float* obs_dev, uint64_t rows, 
     // gd_entry's checks in its order, then the output's and the workspace's; all of them before any launch
     if (!obs_dev || !latent_dev) return fail(D3P_E_INVALID_ARG, "%s: null obs / latent pointer", what);
     if (!out_dev) return fail(D3P_E_INVALID_ARG, "%s: null output pointer", what);
-    if (!gd_aligned(obs_dev) || !gd_aligned(latent_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
+    if (!aligned4(obs_dev) || !aligned4(latent_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (k < 1 || d < 1) return fail(D3P_E_INVALID_ARG, "%s: k and d must be >= 1 (k = %d, d = %d)", what, k, d);
     if (k > 32 || d > 256 || (k > 16 && d > 128))
         return fail(D3P_E_UNSUPPORTED, "%s: supported shapes are k <= 16 with d <= 256 and k <= 32 with d <= 128 (k = %d, d = %d)", what, k, d);

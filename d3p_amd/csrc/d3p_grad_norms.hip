@@ -13,14 +13,15 @@
 // rows, the wave reads it back by lane -- 6 threefry calls per 64 rows per lane instead of 6 per row.
 // No atomics, no clamps: a sum of squares beyond float32 gives inf, exp(t) = inf a non-finite norm.
 //
-// k_norm_pass / k_norm_final.  One pass over the vector per 8-bit digit of an order-preserving uint32 key (q_key of
-// d3p_quantiles.hip, float32 only), most significant first, with all 2 Q wanted ranks in flight: ranks that still share a prefix share
+// k_norm_pass / k_norm_final.  One pass over the vector per 8-bit digit of an order-preserving uint32 key (key_f32 of
+// d3p_colreduce.h), most significant first, with all 2 Q wanted ranks in flight: ranks that still share a prefix share
 // one histogram.  Workgroup b owns strip b of the vector (the strip count is a function of n alone); it builds its histograms in LDS
 // with integer atomics and adds them to the launch's with 64-bit integer atomics -- order-independent, hence deterministic.  The
 // prefix of a pass is derived from the previous pass's histogram by every workgroup at its start.  Pass 0 also forms the strip's
 // counts and float64 sums (a thread's elements in index order, the lanes by an xor butterfly, the four waves in order); k_norm_final
 // merges the strips in strip order, finishes the selection and interpolates in float64, rounding to float32 once.  Only NON-finite
 // values are left out of the selection; no float atomics anywhere.
+#include "d3p_colreduce.h"
 #include "d3p_logreg_kernel.h"
 
 #pragma clang fp contract(off)
@@ -179,13 +180,6 @@ struct NormProfArgs {
     unsigned long long* out;     // 29 words
 };
 
-__device__ inline uint32_t np_key(uint32_t u)   // q_key of d3p_quantiles.hip, float32
-{
-    if ((u << 1) == 0u) u = 0u;
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ inline float np_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
 struct NpShared {
     unsigned long long prev[D3P_NP_RANKS * D3P_NP_HSTRIDE];   // the previous pass's histograms; afterwards this pass's (uint32)
     NpState st[D3P_NP_RANKS];
@@ -282,8 +276,8 @@ __global__ void __launch_bounds__(256) k_norm_pass(NormProfArgs a)
     for (int k = 0; k < D3P_NP_MAX; ++k) { ncl[k] = 0ull; cf[k] = 0.0; }
     for (unsigned long long i = lo + (unsigned)t; i < hi; i += 256) {
         const uint32_t u = a.v[i];
-        const bool fin = (u << 1) < 0xff000000u;
-        const uint32_t key = np_key(u);
+        const bool fin = word_is_finite(u);
+        const uint32_t key = key_f32(u);
         if (P == 0) {
             const float x = __uint_as_float(u);
             if (fin) {
@@ -377,22 +371,15 @@ __global__ void __launch_bounds__(256) k_norm_final(NormProfArgs a, uint32_t str
         a.out[1] = tot[1];
         put(2, nf ? __longlong_as_double((long long)tot[2]) / (double)nf : nan);
         put(3, nf ? __longlong_as_double((long long)tot[3]) / (double)nf : nan);
-        put(4, nf ? (double)np_value((uint32_t)tot[4]) : nan);
+        put(4, nf ? (double)f32_of_key((uint32_t)tot[4]) : nan);
     }
     if (t < D3P_NP_MAX) {
         a.out[5 + t] = (uint32_t)t < a.m ? tot[5 + t] : 0ull;
         put(13 + t, (uint32_t)t < a.m ? __longlong_as_double((long long)tot[13 + t]) / (double)a.n : 0.0);
         double res = nan;
         if ((uint32_t)t < a.Q && sh.st[2 * t].valid && sh.st[2 * t + 1].valid) {
-            const double va = (double)np_value(sh.st[2 * t].prefix), vb = (double)np_value(sh.st[2 * t + 1].prefix);
-            const double g = a.g[t];
-            if (g == 0.0 || va == vb) {
-                res = va;
-            } else {
-                const double dd = vb - va;
-                res = g < 0.5 ? va + dd * g : vb - dd * (1.0 - g);
-            }
-            res = (double)(float)res;   // rounded to float32 once
+            const double va = (double)f32_of_key(sh.st[2 * t].prefix), vb = (double)f32_of_key(sh.st[2 * t + 1].prefix);
+            res = (double)(float)lerp_linear(va, vb, a.g[t]);   // rounded to float32 once
         }
         put(21 + t, (uint32_t)t < a.Q ? res : 0.0);
     }

@@ -7,7 +7,7 @@
 // k_col_hpdi<COLS>: 256 threads, one workgroup owns COLS adjacent columns, thread t = (draw lane t / COLS, column lane t % COLS); the
 // DL = 256 / COLS draw lanes of a column take the draws (pairs, windows) dl, dl + DL, ...
 //   pass 0   every value once from memory, eight loads in flight per thread: the column's NaN flag, and its order-preserving uint32
-//            key (q_key of d3p_quantiles.hip, restated below) into dynamic LDS as [draw][COLS].
+//            key (key_of, d3p_colreduce.h) into dynamic LDS as [draw][COLS].
 //   sort     a bitonic network in its all-ascending form, in place on the keys: per size k = 2, 4, .. one "flip" step (i against the
 //            mirror position of its block of k) and then the steps at distance k/4, k/8, .. 1 (i against i + j).  Every
 //            compare-exchange puts the smaller key at the lower index, so positions >= n behave as keys above all others that never
@@ -26,20 +26,16 @@
 // step.  COLS = 8 (G = 4) and COLS = 2 (G = 16): the bank is (index mod G) COLS + column lane; at a distance j >= G the G lower (upper)
 // indices of a group are consecutive, no conflict; at j < G they are runs of j with gaps of j, which fall two by two on the same
 // banks: a 2-way conflict on the loads of those steps (the last log2(G) steps of every size), none in pass 0 or the scan.
+#include "d3p_colreduce.h"
 #include "d3p_device.h"
-#include "d3p_host.h"
-
-#include <mutex>
-#include <vector>
 
 #pragma clang fp contract(off)
 
 namespace d3p {
 
 #define D3P_H_MAX 8                   // window lengths per launch
-#define D3P_H_DYN_MAX 147456          // 144 KiB of dynamic LDS: D3P_Q_DYN_MAX of d3p_quantiles.hip
 #define D3P_H_ILP 8                   // pairs of a network step, and loads of pass 0, a thread has in flight
-#define D3P_H_MAX_N(COLS) (D3P_H_DYN_MAX / (4 * (COLS)))   // 1152 | 4608 | 18432
+#define D3P_H_MAX_N(COLS) (D3P_DYN_LDS_MAX / (4 * (COLS)))   // 1152 | 4608 | 18432
 
 struct HpdiArgs {
     const uint32_t* m;   // the matrix's words: float32 or int32
@@ -53,20 +49,8 @@ struct HpdiArgs {
     int64_t out_ld;
 };
 
-// q_key of d3p_quantiles.hip: the order-preserving uint32 image of a stored word.  float32: -0 taken as +0; int32: the sign bit flipped
-__device__ inline uint32_t h_key(uint32_t u, int32_t dtype)
-{
-    if (dtype) return u ^ 0x80000000u;
-    if ((u << 1) == 0u) u = 0u;
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
 // the stored value of a key as float32: exact for float32, one rounding for an int32 count above 2^24
-__device__ inline float h_value(uint32_t k, int32_t dtype)
-{
-    if (dtype) return (float)(int32_t)(k ^ 0x80000000u);
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
+__device__ inline float h_value(uint32_t k, int32_t dtype) { return dtype ? (float)i32_of_key(k) : f32_of_key(k); }
 
 // rank(length of the window lo .. hi) << 32 | i: smaller is better, a NaN length is lowest
 __device__ inline uint64_t h_window(uint32_t klo, uint32_t khi, uint32_t i, int32_t dtype)
@@ -162,8 +146,8 @@ __global__ __launch_bounds__(256) void k_col_hpdi(HpdiArgs a)
         for (int q = 0; q < D3P_H_ILP; ++q) {
             const uint32_t s = s0 + (uint32_t)q * DL;
             if (s < n) {
-                if (!dtype && (u[q] << 1) > 0xff000000u) nan = 1u;
-                H_KEY(s) = h_key(u[q], dtype);
+                if (!dtype && word_is_nan(u[q])) nan = 1u;
+                H_KEY(s) = key_of(u[q], dtype);
             }
         }
     }
@@ -214,38 +198,16 @@ __global__ __launch_bounds__(256) void k_col_hpdi(HpdiArgs a)
 }
 
 template <int COLS>
-static int h_dynamic_lds(const char* what)
-{
-    static std::mutex mu;
-    static std::vector<int> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    std::lock_guard<std::mutex> lock(mu);
-    for (int d : done)
-        if (d == dev) return D3P_OK;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_col_hpdi<COLS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)D3P_H_DYN_MAX);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(D3P_E_HIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) on device %d: %s", what, dev, hipGetErrorString(e));
-    }
-    done.push_back(dev);
-    return D3P_OK;
-}
-
-template <int COLS>
 static int h_launch(const char* what, hipStream_t stream, const HpdiArgs& a)
 {
     const uint64_t groups = (a.cols + COLS - 1) / COLS;
     if (groups > 0x7fffffffull) return fail(D3P_E_UNSUPPORTED, "%s: cols <= %d (2^31 - 1) at n = %u", what, COLS, a.n);
     const size_t lds = (size_t)COLS * a.n * 4;
     if (lds > 48u * 1024u)
-        if (int rc = h_dynamic_lds<COLS>(what)) return rc;
+        if (int rc = dynamic_lds_opt_in(reinterpret_cast<const void*>(&k_col_hpdi<COLS>), D3P_DYN_LDS_MAX, what)) return rc;
     hipLaunchKernelGGL((k_col_hpdi<COLS>), dim3((unsigned)groups), dim3(256), lds, stream, a);
     return check_launch(what);
 }
-
-static inline bool h_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 }  // namespace d3p
 
@@ -266,7 +228,7 @@ int d3p_col_hpdi(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uin
 {
     const char* what = "d3p_col_hpdi";
     if (!m_dev || !out_dev || !len_host) return fail(D3P_E_INVALID_ARG, "%s: null pointer", what);
-    if (!h_aligned(m_dev) || !h_aligned(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
+    if (!aligned4(m_dev) || !aligned4(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (dtype != 0 && dtype != 1) return fail(D3P_E_INVALID_ARG, "%s: dtype must be 0 (float32) or 1 (int32), got %d", what, dtype);
     if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n >= 1 is required", what);
     if (Q < 1 || Q > D3P_H_MAX) return fail(D3P_E_INVALID_ARG, "%s: 1 <= Q <= 8 (Q = %u)", what, Q);

@@ -25,8 +25,8 @@
 // half, which touch at most TP + 1 rows.  Both words of every call are used, whatever the shape; a workgroup covers
 // D3P_PGM_ROW_TILE = 2 TP rows of the output.  Lane l of a wave walks pairs l, l + 256, ...: a store is 64 consecutive floats of the
 // row-major (rows, d) output, in the lower and in the upper range alike.  u, z and eps never reach memory (z only through zs_out).
+#include "d3p_colreduce.h"
 #include "d3p_device.h"
-#include "d3p_host.h"
 
 namespace d3p {
 
@@ -314,7 +314,6 @@ static int pgm_limits(int32_t k, int32_t d, const char* what)
     return D3P_OK;
 }
 
-static inline bool pgm_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 }  // namespace d3p
 
@@ -328,8 +327,8 @@ int d3p_predict_gmm_draws(void* stream, const uint32_t* key_dev, uint32_t n, int
 {
     const char* what = "d3p_predict_gmm_draws";
     if (!key_dev || !latent_dev || !obs_keys_dev) return fail(D3P_E_INVALID_ARG, "%s: null key / latent / obs_keys pointer", what);
-    if (!pgm_aligned(key_dev) || !pgm_aligned(latent_dev) || !pgm_aligned(obs_keys_dev) || !pgm_aligned(alpha_log_dev) ||
-        !pgm_aligned(mus_loc_dev) || !pgm_aligned(pis_value_dev) || !pgm_aligned(mus_value_dev) || !pgm_aligned(sigs_value_dev))
+    if (!aligned4(key_dev) || !aligned4(latent_dev) || !aligned4(obs_keys_dev) || !aligned4(alpha_log_dev) ||
+        !aligned4(mus_loc_dev) || !aligned4(pis_value_dev) || !aligned4(mus_value_dev) || !aligned4(sigs_value_dev))
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (int rc = pgm_limits(k, d, what)) return rc;
     if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
@@ -365,7 +364,7 @@ int d3p_predict_gmm_obs(void* stream, const float* latent_dev, int64_t latent_ld
 {
     const char* what = "d3p_predict_gmm_obs";
     if (!latent_dev || !obs_keys_dev || !obs_dev) return fail(D3P_E_INVALID_ARG, "%s: null latent / obs_keys / obs pointer", what);
-    if (!pgm_aligned(latent_dev) || !pgm_aligned(obs_keys_dev) || !pgm_aligned(obs_dev) || !pgm_aligned(zs_out_dev))
+    if (!aligned4(latent_dev) || !aligned4(obs_keys_dev) || !aligned4(obs_dev) || !aligned4(zs_out_dev))
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (int rc = pgm_limits(k, d, what)) return rc;
     if (n < 1) return fail(D3P_E_INVALID_ARG, "%s: n must be >= 1", what);
@@ -397,8 +396,8 @@ int d3p_gmm_assign(void* stream, const float* obs_dev, uint64_t rows, int32_t d,
     const char* what = "d3p_gmm_assign";
     if (!obs_dev || !mus_dev || !sigs_dev || !pis_dev) return fail(D3P_E_INVALID_ARG, "%s: null obs / mus / sigs / pis pointer", what);
     if (!a_out_dev && !argmax_out_dev) return fail(D3P_E_INVALID_ARG, "%s: at least one of the two outputs is required", what);
-    if (!pgm_aligned(obs_dev) || !pgm_aligned(mus_dev) || !pgm_aligned(sigs_dev) || !pgm_aligned(pis_dev) || !pgm_aligned(a_out_dev) ||
-        !pgm_aligned(argmax_out_dev))
+    if (!aligned4(obs_dev) || !aligned4(mus_dev) || !aligned4(sigs_dev) || !aligned4(pis_dev) || !aligned4(a_out_dev) ||
+        !aligned4(argmax_out_dev))
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (int rc = pgm_limits(k, d, what)) return rc;
     if (rows > 0xFFFFFFFFull || rows * (uint64_t)d > 0xFFFFFFFFull) return fail(D3P_E_UNSUPPORTED, "%s: rows d < 2^32", what);

@@ -18,12 +18,9 @@
 //                are 64 strided partials (lane l: j = l, l + 64, ...) merged by an xor butterfly 32, 16, .., 1.
 // All arithmetic after the loads is float64, the three outputs are rounded once.  Nothing is atomic in floating point, every order
 // above is fixed and a row meets no other row's values: identical bits between calls and for any set of other rows in the launch.
-#include "d3p_host.h"
+#include "d3p_colreduce.h"
 
 #include <float.h>
-#include <mutex>
-#include <utility>
-#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -33,7 +30,6 @@ namespace d3p {
 #define D3P_PS_DL 8
 #define D3P_PS_WAVES 4
 #define D3P_PS_HSTRIDE 257            // 256 bins + 1: the 32 row lanes of a histogram update fall on 32 banks
-#define D3P_PS_DYN_MAX 147456          // 144 KiB of dynamic LDS (M = 768 needs 132 KiB) beside 9 KiB of static: within a compute unit's 160 KiB
 #define D3P_PS_LOG_DBL_MIN (-708.3964185322641)   // log(DBL_MIN), as correctly rounded
 
 struct PsisArgs {
@@ -52,16 +48,6 @@ __host__ __device__ inline size_t ps_region_bytes(uint32_t M)
 
 // [E: 4 waves x M float64][histogram, later the 32 rows' tails: 32 x M float32][S: 4 waves x M float32]
 inline size_t ps_lds_bytes(uint32_t M) { return (size_t)D3P_PS_WAVES * M * 8 + ps_region_bytes(M) + (size_t)D3P_PS_WAVES * M * 4; }
-
-// order-preserving uint32 image of a float32 (-0 taken as +0: they are one value)
-__device__ inline uint32_t ps_key(float v)
-{
-    if (v == 0.0f) v = 0.0f;
-    const uint32_t u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
-__device__ inline float ps_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
 __device__ inline double ps_wave_sum(double v)
 {
@@ -122,7 +108,7 @@ __global__ __launch_bounds__(256) void k_psis_loo(PsisArgs a)
         double sum = 0.0;
         for (uint32_t s = dl; s < n; s += D3P_PS_DL) {
             const float v = PS_LOAD(s);
-            const uint32_t key = ps_key(v);
+            const uint32_t key = key_f32(__float_as_uint(v));
             if (p == 0) {
                 sum += exp((double)v - mxd);
                 atomicAdd(&hist[rl * D3P_PS_HSTRIDE + (key >> 24)], 1u);
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(256) void k_psis_loo(PsisArgs a)
     }
 
     // pass 6: the tail into LDS (over the histogram), the rest into the two sums that need no smoothing
-    const double cut = fmax(mnd - (double)ps_unkey(s_prefix[rl]), D3P_PS_LOG_DBL_MIN);
+    const double cut = fmax(mnd - (double)f32_of_key(s_prefix[rl]), D3P_PS_LOG_DBL_MIN);
     {
         double dnt = 0.0, nnt = 0.0;
         for (uint32_t s = dl; s < n; s += D3P_PS_DL) {
@@ -271,27 +257,6 @@ __global__ __launch_bounds__(256) void k_psis_loo(PsisArgs a)
     }
 }
 
-static int ps_dynamic_lds(const char* what)
-{
-    static std::mutex mu;
-    static std::vector<int> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    std::lock_guard<std::mutex> lock(mu);
-    for (int d : done)
-        if (d == dev) return D3P_OK;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_psis_loo), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)D3P_PS_DYN_MAX);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(D3P_E_HIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) on device %d: %s", what, dev, hipGetErrorString(e));
-    }
-    done.push_back(dev);
-    return D3P_OK;
-}
-
-static inline bool ps_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-
 }  // namespace d3p
 
 using namespace d3p;
@@ -301,7 +266,7 @@ extern "C" int d3p_psis_loo(void* stream, const float* ll_dev, int64_t ll_ld, ui
 {
     const char* what = "d3p_psis_loo";
     if (!ll_dev || !elpd_rows_dev || !lppd_rows_dev || !k_rows_dev) return fail(D3P_E_INVALID_ARG, "%s: null pointer", what);
-    if (!ps_aligned(ll_dev) || !ps_aligned(elpd_rows_dev) || !ps_aligned(lppd_rows_dev) || !ps_aligned(k_rows_dev))
+    if (!aligned4(ll_dev) || !aligned4(elpd_rows_dev) || !aligned4(lppd_rows_dev) || !aligned4(k_rows_dev))
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (n < 1 || n > 65535u) return fail(D3P_E_INVALID_ARG, "%s: 1 <= n <= 65535 (n = %u)", what, n);
     if (ll_ld < 0 || (uint64_t)ll_ld < rows) return fail(D3P_E_INVALID_ARG, "%s: ll_ld >= rows is required", what);
@@ -315,9 +280,9 @@ extern "C" int d3p_psis_loo(void* stream, const float* ll_dev, int64_t ll_ld, ui
     a.M = (uint32_t)ceil(dn / 5.0 < by_sqrt ? dn / 5.0 : by_sqrt);   // relative efficiency 1: M <= 768 at n <= 65535
     a.rank = a.M + 1 < n ? a.M + 1 : n;
     const size_t lds = ps_lds_bytes(a.M);
-    if (lds > (size_t)D3P_PS_DYN_MAX) return fail(D3P_E_UNSUPPORTED, "%s: %zu bytes of LDS needed (M = %u)", what, lds, a.M);
+    if (lds > (size_t)D3P_DYN_LDS_MAX) return fail(D3P_E_UNSUPPORTED, "%s: %zu bytes of LDS needed (M = %u)", what, lds, a.M);
     if (lds > 48u * 1024u)
-        if (int rc = ps_dynamic_lds(what)) return rc;
+        if (int rc = dynamic_lds_opt_in(reinterpret_cast<const void*>(&k_psis_loo), D3P_DYN_LDS_MAX, what)) return rc;
     hipLaunchKernelGGL(k_psis_loo, dim3((unsigned)((rows + D3P_PS_ROWS - 1) / D3P_PS_ROWS)), dim3(256), lds, (hipStream_t)stream, a);
     return check_launch(what);
 }

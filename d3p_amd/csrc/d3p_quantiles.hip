@@ -4,7 +4,7 @@
 //
 // k_col_quantiles knows nothing of the model.  The host hands it, per requested probability, a position (lo, g): the result lies
 // between the (lo+1)-th and the (lo+2)-th smallest value of the column, a fraction g of the way (numpy's method='linear').  Both order
-// statistics are found EXACTLY on the stored values through an order-preserving uint32 key (float32: ps_key's map of d3p_psis.hip, -0
+// statistics are found EXACTLY on the stored values through an order-preserving uint32 key (key_of, d3p_colreduce.h: float32 with -0
 // taken as +0; int32: u ^ 0x80000000), so the only arithmetic is the interpolation, in float64, rounded to float32 once.
 //
 // One workgroup of 256 threads owns D3P_Q_COLS = 32 adjacent columns (one 128-byte line of every draw's row of the matrix), k_psis_loo's
@@ -24,12 +24,9 @@
 //
 // k_mean_rows is the sixth user of the draws x rows product tile (d3p_glm_tile.h) with k_loglik's rows-form grid (row tiles x draw
 // tiles) and store (64 consecutive floats per wave), and k_moments' link, text for text: mu = sigmoid(t) | t | exp(t).
+#include "d3p_colreduce.h"
 #include "d3p_device.h"
 #include "d3p_glm_tile.h"
-#include "d3p_host.h"
-
-#include <mutex>
-#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -39,9 +36,8 @@ namespace d3p {
 #define D3P_Q_DL 8
 #define D3P_Q_HSTRIDE 257             // 256 bins + 1: the 32 column lanes of a histogram update fall on 32 banks
 #define D3P_Q_MAX 8                   // probabilities per launch
-#define D3P_Q_DYN_MAX 147456           // 144 KiB of dynamic LDS, as k_psis_loo: beside 3 KiB of static within a compute unit's 160 KiB
 #define D3P_Q_HIST_BYTES (D3P_Q_COLS * D3P_Q_HSTRIDE * 4)
-#define D3P_Q_STAGED_MAX ((D3P_Q_DYN_MAX - D3P_Q_HIST_BYTES) / (D3P_Q_COLS * 4))   // 895 draws
+#define D3P_Q_STAGED_MAX ((D3P_DYN_LDS_MAX - D3P_Q_HIST_BYTES) / (D3P_Q_COLS * 4))   // 895 draws
 
 struct QuantArgs {
     const uint32_t* m;   // the matrix's words: float32 or int32
@@ -56,19 +52,8 @@ struct QuantArgs {
     int64_t out_ld;
 };
 
-// order-preserving uint32 image of a stored word.  float32: ps_key's map (d3p_psis.hip), -0 taken as +0; int32: the sign bit flipped
-__device__ inline uint32_t q_key(uint32_t u, int32_t dtype)
-{
-    if (dtype) return u ^ 0x80000000u;
-    if ((u << 1) == 0u) u = 0u;
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
-__device__ inline double q_value(uint32_t k, int32_t dtype)
-{
-    if (dtype) return (double)(int32_t)(k ^ 0x80000000u);
-    return (double)__uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
+// the stored value of a key in float64: exact for both types
+__device__ inline double q_value(uint32_t k, int32_t dtype) { return dtype ? (double)i32_of_key(k) : (double)f32_of_key(k); }
 
 template <bool STAGED>
 __global__ __launch_bounds__(256) void k_col_quantiles(QuantArgs a)
@@ -88,14 +73,14 @@ __global__ __launch_bounds__(256) void k_col_quantiles(QuantArgs a)
     const uint32_t* col = a.m + (live ? c : 0);
     const size_t ld = (size_t)a.ld;
 #define Q_LOAD(s) (live ? col[(size_t)(s) * ld] : 0u)
-#define Q_KEY(s) (STAGED ? keys[(size_t)(s) * D3P_Q_COLS + cl] : q_key(Q_LOAD(s), dtype))
+#define Q_KEY(s) (STAGED ? keys[(size_t)(s) * D3P_Q_COLS + cl] : key_of(Q_LOAD(s), dtype))
 
     // pass 0: the column's NaN flag; the staged form keeps the keys
     uint32_t nan = 0u;
     for (uint32_t s = dl; s < n; s += D3P_Q_DL) {
         const uint32_t u = Q_LOAD(s);
-        if (!dtype && (u << 1) > 0xff000000u) nan = 1u;
-        if (STAGED) keys[(size_t)s * D3P_Q_COLS + cl] = q_key(u, dtype);
+        if (!dtype && word_is_nan(u)) nan = 1u;
+        if (STAGED) keys[(size_t)s * D3P_Q_COLS + cl] = key_of(u, dtype);
     }
     r_u0[dl][cl] = nan;
     __syncthreads();
@@ -158,15 +143,7 @@ __global__ __launch_bounds__(256) void k_col_quantiles(QuantArgs a)
         }
         if (dl == 0 && live) {
             const double va = q_value(ka, dtype), vb = q_value(kb, dtype);
-            double res;
-            if (g == 0.0 || va == vb) {
-                res = va;
-            } else if (fabs(va) == (double)INFINITY || fabs(vb) == (double)INFINITY) {
-                res = fabs(va) != (double)INFINITY ? vb : fabs(vb) != (double)INFINITY ? va : (double)NAN;   // (-inf, +inf): NaN
-            } else {
-                const double d = vb - va;
-                res = g < 0.5 ? va + d * g : vb - d * (1.0 - g);
-            }
+            const double res = lerp_linear(va, vb, g);
             a.out[(size_t)qi * (size_t)a.out_ld + c] = nan ? NAN : (float)res;
         }
         __syncthreads();   // (r_u0 / r_u1, s_prefix and s_rank are free for the next probability)
@@ -174,27 +151,6 @@ __global__ __launch_bounds__(256) void k_col_quantiles(QuantArgs a)
 #undef Q_KEY
 #undef Q_LOAD
 }
-
-static int q_dynamic_lds(const char* what)
-{
-    static std::mutex mu;
-    static std::vector<int> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    std::lock_guard<std::mutex> lock(mu);
-    for (int d : done)
-        if (d == dev) return D3P_OK;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_col_quantiles<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)D3P_Q_DYN_MAX);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(D3P_E_HIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) on device %d: %s", what, dev, hipGetErrorString(e));
-    }
-    done.push_back(dev);
-    return D3P_OK;
-}
-
-static inline bool q_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 // ---- the conditional mean over posterior draws, rows form -------------------------------------------------------------------------
 struct MeanRowsArgs {
@@ -262,7 +218,7 @@ int d3p_col_quantiles(void* stream, const void* m_dev, int32_t dtype, int64_t ld
 {
     const char* what = "d3p_col_quantiles";
     if (!m_dev || !out_dev || !lo_host || !g_host) return fail(D3P_E_INVALID_ARG, "%s: null pointer", what);
-    if (!q_aligned(m_dev) || !q_aligned(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
+    if (!aligned4(m_dev) || !aligned4(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (dtype != 0 && dtype != 1) return fail(D3P_E_INVALID_ARG, "%s: dtype must be 0 (float32) or 1 (int32), got %d", what, dtype);
     if (n < 1 || n > 65535u) return fail(D3P_E_INVALID_ARG, "%s: 1 <= n <= 65535 (n = %u)", what, n);
     if (Q < 1 || Q > D3P_Q_MAX) return fail(D3P_E_INVALID_ARG, "%s: 1 <= Q <= 8 (Q = %u)", what, Q);
@@ -288,7 +244,7 @@ int d3p_col_quantiles(void* stream, const void* m_dev, int32_t dtype, int64_t ld
     if (n <= D3P_Q_STAGED_MAX) {
         const size_t lds = (size_t)D3P_Q_HIST_BYTES + (size_t)D3P_Q_COLS * n * 4;
         if (lds > 48u * 1024u)
-            if (int rc = q_dynamic_lds(what)) return rc;
+            if (int rc = dynamic_lds_opt_in(reinterpret_cast<const void*>(&k_col_quantiles<true>), D3P_DYN_LDS_MAX, what)) return rc;
         hipLaunchKernelGGL((k_col_quantiles<true>), grid, dim3(256), lds, (hipStream_t)stream, a);
     } else {
         hipLaunchKernelGGL((k_col_quantiles<false>), grid, dim3(256), (size_t)D3P_Q_HIST_BYTES, (hipStream_t)stream, a);

@@ -79,23 +79,24 @@ def _family(model, what):
     return fam
 
 
-def _probs(prob, probs):
-    """(the probabilities as a tuple of floats, the result's names or None) after the host checks."""
-    if probs is not None:
-        try:
-            ps = tuple(float(p) for p in probs)
-        except TypeError:
-            raise ValueError("probs: a sequence of 1 to 8 floats in [0, 1] is required") from None
-        if not 1 <= len(ps) <= MAX_PROBS:
-            raise ValueError(f"probs: 1 to {MAX_PROBS} probabilities per call, got {len(ps)}")
-        for p in ps:
-            if not 0.0 <= p <= 1.0:   # (a NaN fails both comparisons)
-                raise ValueError(f"probs: every probability must lie in [0, 1], got {p!r}")
-        return ps, None
+def _prob(prob):
     if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 < float(prob) < 1.0:
         raise ValueError(f"prob must be a float in (0, 1), got {prob!r}")
-    prob = float(prob)
-    return ((1.0 - prob) / 2.0, 0.5, (1.0 + prob) / 2.0), ("lower", "median", "upper")
+    return float(prob)
+
+
+def _probs(probs):
+    """`probs` as a tuple of 1 to 8 floats in [0, 1]."""
+    try:
+        ps = tuple(float(p) for p in probs)
+    except TypeError:
+        raise ValueError("probs: a sequence of 1 to 8 floats in [0, 1] is required") from None
+    if not 1 <= len(ps) <= MAX_PROBS:
+        raise ValueError(f"probs: 1 to {MAX_PROBS} probabilities per call, got {len(ps)}")
+    for p in ps:
+        if not 0.0 <= p <= 1.0:   # (a NaN fails both comparisons)
+            raise ValueError(f"probs: every probability must lie in [0, 1], got {p!r}")
+    return ps
 
 
 def positions(probs, n):
@@ -108,26 +109,6 @@ def positions(probs, n):
     return out
 
 
-def _check_draws(n, what):
-    if n > MAX_DRAWS:
-        raise ValueError(f"{what}: {n} draws; the quantile kernel runs at most {MAX_DRAWS} draws (n <= {MAX_DRAWS})")
-
-
-def _kind(kind, probs, name="kind"):
-    """True for the highest-density interval.  An unknown kind is an error, and so is `probs` with kind='hpdi'."""
-    if not isinstance(kind, str) or kind not in KINDS:
-        raise ValueError(f"{name} must be one of {KINDS}, got {kind!r}")
-    if kind == "hpdi" and probs is not None:
-        raise ValueError(f"probs cannot be combined with {name}='hpdi': a highest-density interval is given by prob alone")
-    return kind == "hpdi"
-
-
-def _hpdi_prob(prob):
-    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 < float(prob) < 1.0:
-        raise ValueError(f"prob must be a float in (0, 1), got {prob!r}")
-    return float(prob)
-
-
 def window_lengths(probs, n):
     """[L] of the probabilities over n draws: L = int(prob n) in Python floats, numpyro.diagnostics.hpdi's window length."""
     return [int(float(p) * n) for p in probs]
@@ -138,57 +119,112 @@ def hpdi_max_draws():
     return int(_lib.load().d3p_col_hpdi_max_n())
 
 
+def _check_draws(n, what):
+    if n > MAX_DRAWS:
+        raise ValueError(f"{what}: {n} draws; the quantile kernel runs at most {MAX_DRAWS} draws (n <= {MAX_DRAWS})")
+
+
 def _check_hpdi_draws(n, what):
     most = hpdi_max_draws()
     if n > most:
         raise ValueError(f"{what}: {n} draws; the highest-density interval sorts a column in LDS and runs at most {most} draws (n <= {most})")
 
 
-def _reduce_hpdi(first, dtype, ld, n, cols, lens, out, out_ld):
-    """d3p_col_hpdi on the (n, cols) matrix that starts at tensor `first`, into out (2 len(lens) rows: lower, upper per length)."""
-    Q = len(lens)
-    check(_lib.load().d3p_col_hpdi(stream_ptr(), ptr(first), 0 if dtype == torch.float32 else 1, ld, n, cols, Q, (C.c_uint32 * Q)(*lens), ptr(out), out_ld))
+def _position_args(probs, n):
+    pos = positions(probs, n)
+    return (C.c_uint32 * len(pos))(*[p[0] for p in pos]), (C.c_double * len(pos))(*[p[1] for p in pos])
 
 
-def _ends(q):
-    return {"lower": q[0], "upper": q[1]}
+def _window_args(probs, n):
+    return ((C.c_uint32 * len(probs))(*window_lengths(probs, n)),)
 
 
-def _reduce(first, dtype, ld, n, cols, pos, out, out_ld):
-    """d3p_col_quantiles on the (n, cols) matrix that starts at tensor `first`, into out (a tensor at the first output element)."""
-    Q = len(pos)
-    lo = (C.c_uint32 * Q)(*[p[0] for p in pos])
-    g = (C.c_double * Q)(*[p[1] for p in pos])
-    check(_lib.load().d3p_col_quantiles(stream_ptr(), ptr(first), 0 if dtype == torch.float32 else 1, ld, n, cols, Q, lo, g, ptr(out), out_ld))
+class _Rule:
+    """One reduction of the columns of a (draws, cols) matrix, built once per call: the probabilities, the names of the result's rows
+    (None: one "quantiles" matrix), the entry of libd3p_hip that reduces, the output rows it writes, its per-n host arrays (a function of
+    (probs, n)) and its extra limit on the draws (None: the quantile kernel's alone)."""
+    __slots__ = ("probs", "names", "entry", "out_rows", "per_n", "limit")
+
+    def __init__(self, probs, names, entry, rows_per_prob, per_n, limit):
+        self.probs, self.names, self.entry, self.per_n, self.limit = probs, names, entry, per_n, limit
+        self.out_rows = rows_per_prob * len(probs)
+
+    def check_draws(self, n, what):
+        _check_draws(n, what)   # (the quantile kernel's limit is named first whatever the rule)
+        if self.limit is not None:
+            self.limit(n, what)
+
+    def args(self, n):
+        return self.per_n(self.probs, n)
+
+    def reduce(self, first, dtype, ld, n, cols, args, out, out_ld):
+        """The (n, cols) matrix that starts at tensor `first`, reduced into out (a tensor at the first output element): out_rows rows."""
+        check(getattr(_lib.load(), self.entry)(stream_ptr(), ptr(first), 0 if dtype == torch.float32 else 1, ld, n, cols, len(self.probs), *args,
+                                               ptr(out), out_ld))
+
+    def result(self, q):
+        return {"quantiles": q} if self.names is None else {name: q[i] for i, name in enumerate(self.names)}
 
 
-def _result(q, names):
-    return {"quantiles": q} if names is None else {name: q[i] for i, name in enumerate(names)}
+def _equal_tailed(probs, names=None):     # one row per probability, from the positions (lo, g)
+    return _Rule(probs, names, "d3p_col_quantiles", 1, _position_args, None)
+
+
+def _highest_density(probs, names=None):  # lower and upper per probability, from the window lengths
+    return _Rule(probs, names, "d3p_col_hpdi", 2, _window_args, _check_hpdi_draws)
+
+
+def _rule(kind, prob, probs, name="kind"):
+    """The rule of an interval function.  An unknown kind is an error, and so is `probs` with kind='hpdi'."""
+    if not isinstance(kind, str) or kind not in KINDS:
+        raise ValueError(f"{name} must be one of {KINDS}, got {kind!r}")
+    if kind == "hpdi":
+        if probs is not None:
+            raise ValueError(f"probs cannot be combined with {name}='hpdi': a highest-density interval is given by prob alone")
+        return _highest_density((_prob(prob),), ("lower", "upper"))
+    if probs is not None:
+        return _equal_tailed(_probs(probs))
+    prob = _prob(prob)
+    return _equal_tailed(((1.0 - prob) / 2.0, 0.5, (1.0 + prob) / 2.0), ("lower", "median", "upper"))
+
+
+def _row_stride(m, n, cols):
+    return int(m.stride(0)) if n > 1 else cols
+
+
+def _check_matrix(matrix, what, check_draws):
+    """(n, cols, ld) of a reducer's matrix after the host checks; `what` names the caller in the messages."""
+    if not isinstance(matrix, torch.Tensor) or matrix.dim() != 2 or matrix.dtype not in (torch.float32, torch.int32) or not matrix.is_cuda:
+        raise ValueError(f"{what}: a 2-D float32 or int32 CUDA tensor (draws, cols) is required")
+    n, cols = int(matrix.shape[0]), int(matrix.shape[1])
+    if cols > 1 and matrix.stride(1) != 1:
+        raise ValueError(f"{what}: the matrix's columns must have unit stride (rows may be strided)")
+    if n < 1:
+        raise ValueError(f"{what}: at least one draw")
+    check_draws(n, what)
+    ld = _row_stride(matrix, n, cols)
+    if ld < cols:
+        raise ValueError(f"{what}: the matrix's rows overlap (row stride below the column count)")
+    return n, cols, ld
+
+
+def _reduce_matrix(rule, matrix, what):
+    """(rule.out_rows, cols) float32 on the matrix's device.  The draws are held to the reducer's own limit alone."""
+    n, cols, ld = _check_matrix(matrix, what, rule.limit or _check_draws)
+    args = rule.args(n)
+    _lib.require_device()   # (every check above runs without a device)
+    with torch.cuda.device(matrix.device):
+        out = torch.empty((rule.out_rows, cols), dtype=torch.float32, device=matrix.device)
+        if cols:
+            rule.reduce(matrix, matrix.dtype, ld, n, cols, args, out, cols)
+    return out
 
 
 def quantiles(matrix, probs):
     """The quantiles of every column of ``matrix`` -- a 2-D CUDA tensor ``(draws, cols)``, float32 or int32, any row stride, unit column
     stride -- at ``probs`` (1 to 8 floats in [0, 1]): ``(Q, cols)`` float32 on the matrix's device, numpy's ``method='linear'`` on the
     exactly selected order statistics (module docstring)."""
-    ps, _ = _probs(None, probs if probs is not None else ())
-    if not isinstance(matrix, torch.Tensor) or matrix.dim() != 2 or matrix.dtype not in (torch.float32, torch.int32) or not matrix.is_cuda:
-        raise ValueError("quantiles: a 2-D float32 or int32 CUDA tensor (draws, cols) is required")
-    n, cols = int(matrix.shape[0]), int(matrix.shape[1])
-    if cols > 1 and matrix.stride(1) != 1:
-        raise ValueError("quantiles: the matrix's columns must have unit stride (rows may be strided)")
-    if n < 1:
-        raise ValueError("quantiles: at least one draw")
-    _check_draws(n, "quantiles")
-    ld = int(matrix.stride(0)) if n > 1 else cols
-    if ld < cols:
-        raise ValueError("quantiles: the matrix's rows overlap (row stride below the column count)")
-    pos = positions(ps, n)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(matrix.device):
-        out = torch.empty((len(ps), cols), dtype=torch.float32, device=matrix.device)
-        if cols:
-            _reduce(matrix, matrix.dtype, ld, n, cols, pos, out, cols)
-    return out
+    return _reduce_matrix(_equal_tailed(_probs(probs if probs is not None else ())), matrix, "quantiles")
 
 
 def hpdi(matrix, prob=0.9):
@@ -196,7 +232,7 @@ def hpdi(matrix, prob=0.9):
     or int32, any row stride, unit column stride -- numpyro's ``hpdi(x, prob, axis=0)`` (module docstring).  A float ``prob`` in (0, 1)
     returns ``(2, cols)`` float32, lower and upper; a sequence of 1 to 8 such floats ``(Q, 2, cols)``, all from one sort."""
     if isinstance(prob, (int, float)):
-        ps, single = (_hpdi_prob(prob),), True
+        ps, single = (_prob(prob),), True
     else:
         try:
             ps = tuple(prob)
@@ -204,44 +240,26 @@ def hpdi(matrix, prob=0.9):
             raise ValueError(f"prob must be a float in (0, 1) or a sequence of 1 to {MAX_PROBS} of them, got {prob!r}") from None
         if not 1 <= len(ps) <= MAX_PROBS:
             raise ValueError(f"prob: 1 to {MAX_PROBS} probabilities per call, got {len(ps)}")
-        ps, single = tuple(_hpdi_prob(p) for p in ps), False
-    if not isinstance(matrix, torch.Tensor) or matrix.dim() != 2 or matrix.dtype not in (torch.float32, torch.int32) or not matrix.is_cuda:
-        raise ValueError("hpdi: a 2-D float32 or int32 CUDA tensor (draws, cols) is required")
-    n, cols = int(matrix.shape[0]), int(matrix.shape[1])
-    if cols > 1 and matrix.stride(1) != 1:
-        raise ValueError("hpdi: the matrix's columns must have unit stride (rows may be strided)")
-    if n < 1:
-        raise ValueError("hpdi: at least one draw")
-    _check_hpdi_draws(n, "hpdi")
-    ld = int(matrix.stride(0)) if n > 1 else cols
-    if ld < cols:
-        raise ValueError("hpdi: the matrix's rows overlap (row stride below the column count)")
-    lens = window_lengths(ps, n)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(matrix.device):
-        out = torch.empty((2 * len(ps), cols), dtype=torch.float32, device=matrix.device)
-        if cols:
-            _reduce_hpdi(matrix, matrix.dtype, ld, n, cols, lens, out, cols)
-    return out if single else out.reshape(len(ps), 2, cols)
+        ps, single = tuple(_prob(p) for p in ps), False
+    out = _reduce_matrix(_highest_density(ps), matrix, "hpdi")
+    return out if single else out.reshape(len(ps), 2, out.shape[1])
 
 
-def _mean_slabs(model, fam, X, rows, d, n, latent, pos, chunk, reduce=_reduce, out_rows=None):
-    """(Q, rows) float32: the quantiles of mu[:, r] over the draws, the n x rows matrix written and reduced in row slabs of `chunk`.
-    With reduce=_reduce_hpdi and out_rows = 2 len(pos), pos holds window lengths and the result the intervals' ends."""
+def _mean_slabs(model, fam, X, rows, d, n, latent, rule, chunk):
+    """(rule.out_rows, rows) float32: mu[:, r] reduced over the draws, the n x rows matrix written and reduced in row slabs of `chunk`."""
     first, ld, w_off, b_col = latent
     X = M._f32(X, "X")
     lib = _lib.load()
     ms = U._model_struct(model, fam, d)
-    out = torch.empty((len(pos) if out_rows is None else out_rows, rows), dtype=torch.float32, device=X.device)
+    args = None
+    out = torch.empty((rule.out_rows, rows), dtype=torch.float32, device=X.device)
     buf = torch.empty((n * min(chunk, rows),), dtype=torch.float32, device=X.device)
     for lo in range(0, rows, chunk):
         count = min(chunk, rows - lo)
         check(lib.d3p_predict_mean_rows(stream_ptr(), C.byref(ms), ptr(X[lo:lo + count]), count, ptr(first), ld, w_off, b_col, n, ptr(buf), count))
-        reduce(buf, torch.float32, count, n, count, pos, out[0, lo:], rows)
+        args = args or rule.args(n)   # (once, behind the first launch: the host builds them while the kernel runs)
+        rule.reduce(buf, torch.float32, count, n, count, args, out[0, lo:], rows)
     return out
-
-
-_HPDI_SLABS = {"reduce": _reduce_hpdi, "out_rows": 2}
 
 
 def credible_interval(model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed", **kwargs):
@@ -252,22 +270,17 @@ def credible_interval(model, posterior_samples, *model_args, prob=0.9, probs=Non
     (n,) or (n, 1)]}`` as for ``predictive_moments``: packed views are read in place, everything else is packed once.
     ``kind="hpdi"``: the highest-density interval at ``prob`` instead, ``{"lower", "upper"}``."""
     fam = _family(model, "credible_interval")
-    hp = _kind(kind, probs)
-    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
+    rule = _rule(kind, prob, probs)
     rows, d = PM._data(model, model_args)
     n, _ = U._sample_shape(model, posterior_samples, d)
-    _check_draws(n, "credible_interval")
-    if hp:
-        _check_hpdi_draws(n, "credible_interval")
+    rule.check_draws(n, "credible_interval")
     chunk = U._loo_chunk(n, slab_bytes)
     if chunk is None:
         raise ValueError("slab_bytes must be an int >= 1, got None")
-    pos = window_lengths(ps, n) if hp else positions(ps, n)
     _lib.require_device()   # (every check above runs without a device)
     with torch.cuda.device(M._device()):
-        q = _mean_slabs(model, fam, model_args[0], rows, d, n, U._pack(model, posterior_samples, n, d), pos, chunk,
-                        **(_HPDI_SLABS if hp else {}))
-    return _ends(q) if hp else _result(q, names)
+        q = _mean_slabs(model, fam, model_args[0], rows, d, n, U._pack(model, posterior_samples, n, d), rule, chunk)
+    return rule.result(q)
 
 
 def posterior_credible_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed",
@@ -277,14 +290,11 @@ def posterior_credible_interval(rng_key, n, model, model_args, guide, params, pr
     ``MeanFieldGuide`` for logistic regression."""
     fam = _family(model, "posterior_credible_interval")
     U._check_guide(model, guide)
-    hp = _kind(kind, probs)
-    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
+    rule = _rule(kind, prob, probs)
     n = int(n)
     if n < 1:
         raise ValueError("n must be >= 1")
-    _check_draws(n, "posterior_credible_interval")
-    if hp:
-        _check_hpdi_draws(n, "posterior_credible_interval")
+    rule.check_draws(n, "posterior_credible_interval")
     rows, d = PM._data(model, model_args)
     chunk = U._loo_chunk(n, slab_bytes)
     if chunk is None:
@@ -293,13 +303,12 @@ def posterior_credible_interval(rng_key, n, model, model_args, guide, params, pr
         raise ValueError("params: the dict DPSVI.get_params returns is required")
     gparams = [(name, M._param(params, name, size)) for name, size in M._guide_param_names(guide, model, d)]
     key = M._check_key(rng_key)
-    pos = window_lengths(ps, n) if hp else positions(ps, n)
     _lib.require_device()
     dev = key.device
     with torch.cuda.device(dev):
         latent = U._guide_latents(key, n, model, guide, gparams, d, rows, dev)
-        q = _mean_slabs(model, fam, model_args[0], rows, d, n, latent, pos, chunk, **(_HPDI_SLABS if hp else {}))
-    return _ends(q) if hp else _result(q, names)
+        q = _mean_slabs(model, fam, model_args[0], rows, d, n, latent, rule, chunk)
+    return rule.result(q)
 
 
 def _predictive_family(model, what):
@@ -319,12 +328,12 @@ def _check_whole(n, rows, slab_bytes, what):
                          f"slab_bytes >= {need}, got {slab_bytes}")
 
 
-def _reduce_obs(obs, n, rows, pos, names, hp=False):
+def _reduce_obs(obs, n, rows, rule):
     obs = obs.reshape(n, rows)
     with torch.cuda.device(obs.device):
-        q = torch.empty((2 if hp else len(pos), rows), dtype=torch.float32, device=obs.device)
-        (_reduce_hpdi if hp else _reduce)(obs, obs.dtype, rows, n, rows, pos, q, rows)
-    return _ends(q) if hp else _result(q, names)
+        q = torch.empty((rule.out_rows, rows), dtype=torch.float32, device=obs.device)
+        rule.reduce(obs, obs.dtype, rows, n, rows, rule.args(n), q, rows)
+    return rule.result(q)
 
 
 def predictive_interval(rng_key, model, posterior_samples, *model_args, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed", **kwargs):
@@ -333,18 +342,14 @@ def predictive_interval(rng_key, model, posterior_samples, *model_args, prob=0.9
     ``LinearRegression`` and ``PoissonRegression``; the matrix is written whole and must fit ``slab_bytes`` (module docstring).
     ``kind="hpdi"``: the highest-density interval at ``prob`` instead, ``{"lower", "upper"}``."""
     _predictive_family(model, "predictive_interval")
-    hp = _kind(kind, probs)
-    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
+    rule = _rule(kind, prob, probs)
     rows, d = PS._data(model, model_args, kwargs)
     n, _ = U._sample_shape(model, posterior_samples, d)
-    _check_draws(n, "predictive_interval")
-    if hp:
-        _check_hpdi_draws(n, "predictive_interval")
+    rule.check_draws(n, "predictive_interval")
     _check_whole(n, rows, slab_bytes, "predictive_interval")
     M._check_key(rng_key)
-    pos = window_lengths(ps, n) if hp else positions(ps, n)
     obs = PS.predictive_samples(rng_key, model, posterior_samples, *model_args, **kwargs)
-    return _reduce_obs(obs, n, rows, pos, names, hp)
+    return _reduce_obs(obs, n, rows, rule)
 
 
 def posterior_predictive_interval(rng_key, n, model, model_args, guide, params, prob=0.9, probs=None, slab_bytes=64 << 20, kind="equal_tailed",
@@ -353,17 +358,13 @@ def posterior_predictive_interval(rng_key, n, model, model_args, guide, params, 
     ``posterior_predictive_samples(rng_key, n, model, model_args, guide, params)`` returns for the same key."""
     _predictive_family(model, "posterior_predictive_interval")
     U._check_guide(model, guide)
-    hp = _kind(kind, probs)
-    ps, names = ((_hpdi_prob(prob),), None) if hp else _probs(prob, probs)
+    rule = _rule(kind, prob, probs)
     n = PS._count(n)
-    _check_draws(n, "posterior_predictive_interval")
-    if hp:
-        _check_hpdi_draws(n, "posterior_predictive_interval")
+    rule.check_draws(n, "posterior_predictive_interval")
     rows, d = PS._data(model, model_args, kwargs)
     _check_whole(n, rows, slab_bytes, "posterior_predictive_interval")
-    pos = window_lengths(ps, n) if hp else positions(ps, n)
     obs = PS.posterior_predictive_samples(rng_key, n, model, model_args, guide, params, **kwargs)["obs"]
-    return _reduce_obs(obs, n, rows, pos, names, hp)
+    return _reduce_obs(obs, n, rows, rule)
 
 
 def latent_summary(posterior_samples, prob=0.9, interval="equal_tailed"):
@@ -373,8 +374,8 @@ def latent_summary(posterior_samples, prob=0.9, interval="equal_tailed"):
     (the ``n - 1`` variance: ``n == 1`` gives a NaN ``std``); the three quantiles are float32 from ``d3p_col_quantiles`` at ``((1 -
     prob) / 2, 0.5, (1 + prob) / 2)``.  ``interval="hpdi"``: ``lower`` and ``upper`` are the highest-density interval at ``prob`` from
     ``d3p_col_hpdi`` -- what ``print_summary`` reports -- and ``median`` still comes from ``d3p_col_quantiles``."""
-    hp = _kind(interval, None, "interval")
-    ps, names = _probs(prob, None)
+    # hpdi: rows 0 and 1 are the interval's ends, row 2 the median
+    rules = [_rule(interval, prob, None, "interval")] + ([_equal_tailed((0.5,), ("median",))] if interval == "hpdi" else [])
     if not isinstance(posterior_samples, dict) or not posterior_samples:
         raise ValueError("posterior_samples: a dict of sites (n draws each) is required")
     shapes = {}
@@ -382,9 +383,7 @@ def latent_summary(posterior_samples, prob=0.9, interval="equal_tailed"):
         shp = tuple(v.shape) if hasattr(v, "shape") else ()
         if len(shp) < 1 or shp[0] < 1 or M._numel(v) == 0:
             raise ValueError(f"posterior_samples['{name}']: at least one draw along the first axis is required")
-        _check_draws(shp[0], "latent_summary")
-        if hp:
-            _check_hpdi_draws(shp[0], "latent_summary")
+        rules[0].check_draws(shp[0], "latent_summary")
         shapes[name] = shp
     _lib.require_device()   # (every check above runs without a device)
     lib = _lib.load()
@@ -398,19 +397,17 @@ def latent_summary(posterior_samples, prob=0.9, interval="equal_tailed"):
             cols = int(m.shape[1])
             if cols > 1 and m.stride(1) != 1:
                 m = m.contiguous()
-            ld = int(m.stride(0)) if n > 1 else cols
+            ld = _row_stride(m, n, cols)
             if ld < cols:
                 m, ld = m.contiguous(), cols
             with torch.cuda.device(m.device):
                 stats = torch.empty((4, cols), dtype=torch.float64, device=m.device)
                 check(lib.d3p_col_stats(stream_ptr(), ptr(m), ld, n, cols, ptr(stats)))
                 q = torch.empty((3, cols), dtype=torch.float32, device=m.device)
-                if hp:   # rows 0 and 1: the interval's ends; row 2: the median
-                    _reduce_hpdi(m, torch.float32, ld, n, cols, window_lengths((float(prob),), n), q, cols)
-                    _reduce(m, torch.float32, ld, n, cols, positions(ps[1:2], n), q[2], cols)
-                else:
-                    _reduce(m, torch.float32, ld, n, cols, positions(ps, n), q, cols)
-        site = {"mean": stats[0], "std": torch.sqrt(stats[1])}
-        site.update({nm: q[i] for i, nm in enumerate(("lower", "upper", "median") if hp else names)})
+                site, row = {"mean": stats[0], "std": torch.sqrt(stats[1])}, 0
+                for rule in rules:
+                    rule.reduce(m, torch.float32, ld, n, cols, rule.args(n), q[row], cols)
+                    site.update(rule.result(q[row:]))
+                    row += rule.out_rows
         out[name] = {k: t.reshape(shp[1:]) for k, t in site.items()}
     return out

@@ -44,10 +44,12 @@ def kernel_alone(reps):
         count = SLAB // (4 * n)
         buf = torch.randn((n, count), device="cuda", generator=g)
         out, q = torch.empty((2, count), device="cuda"), torch.empty((len(PROBS), count), device="cuda")
-        lens, pos = IV.window_lengths((0.9,), n), IV.positions(PROBS, n)
-        t_h, t_t, t_q = _time_alternating([lambda: IV._reduce_hpdi(buf, torch.float32, count, n, count, lens, out, count),
+        lens = IV.window_lengths((0.9,), n)
+        hd, et = IV._highest_density((0.9,)), IV._equal_tailed(PROBS)
+        hd_args, et_args = hd.args(n), et.args(n)
+        t_h, t_t, t_q = _time_alternating([lambda: hd.reduce(buf, torch.float32, count, n, count, hd_args, out, count),
                                            lambda: _torch_hpdi(buf, lens[0]),
-                                           lambda: IV._reduce(buf, torch.float32, count, n, count, pos, q, count)], reps)
+                                           lambda: et.reduce(buf, torch.float32, count, n, count, et_args, q, count)], reps)
         same = bool(torch.equal(out, _torch_hpdi(buf, lens[0])))      # (continuous values: argmin's tie rule is not exercised)
         form = int(lib.d3p_col_hpdi_cols_per_group(n))
         _line(f"d3p_col_hpdi alone ({form}-column form), n={n} cols={count} L={lens[0]}", t_h,

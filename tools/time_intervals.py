@@ -50,8 +50,11 @@ def _torch_quantiles(m, pos):
     return torch.stack(out)
 
 
-def _quantiles_into(buf, n, count, pos, out):
-    IV._reduce(buf, torch.float32, count, n, count, pos, out, count)
+RULE = IV._equal_tailed(PROBS)
+
+
+def _quantiles_into(buf, n, count, args, out):
+    RULE.reduce(buf, torch.float32, count, n, count, args, out, count)
 
 
 def kernel_alone(reps):
@@ -62,8 +65,8 @@ def kernel_alone(reps):
         count = U._loo_chunk(n, SLAB)
         buf = torch.randn((n, count), device="cuda", generator=g)
         out = torch.empty((len(PROBS), count), device="cuda")
-        pos = IV.positions(PROBS, n)
-        t_k, t_t = _time_alternating([lambda: _quantiles_into(buf, n, count, pos, out), lambda: _torch_quantiles(buf, pos)], reps)
+        pos, args = IV.positions(PROBS, n), RULE.args(n)
+        t_k, t_t = _time_alternating([lambda: _quantiles_into(buf, n, count, args, out), lambda: _torch_quantiles(buf, pos)], reps)
         same = bool(torch.equal(out, _torch_quantiles(buf.double(), pos).float()))
         form = "staged" if n <= staged_max else "streamed"
         _line(f"d3p_col_quantiles alone ({form}), n={n} cols={count} Q=3", t_k,
@@ -87,7 +90,7 @@ def regression_cases(reps, shapes):
             ms = U._model_struct(model, U._family(model), d)
             s = {"w": lat[:, :d], "intercept": lat[:, d]}
             shape = f"{family} d={d} rows={rows} n={n}"
-            pos = IV.positions(PROBS, n)
+            pos, args = IV.positions(PROBS, n), RULE.args(n)
             t_ci, t_waic = _time_alternating([lambda: IV.credible_interval(model, s, X, probs=PROBS), lambda: CR.waic(model, s, X, y)], reps)
             _line(f"intervals.credible_interval {shape}", t_ci, {"over_waic": round(t_ci[0] / t_waic[0], 2)})
             _line(f"criteria.waic {shape}", t_waic)
@@ -98,7 +101,7 @@ def regression_cases(reps, shapes):
 
             def pair():
                 check(lib.d3p_predict_mean_rows(stream_ptr(), C.byref(ms), ptr(X), count, ptr(lat), d + 1, 0, d, n, ptr(buf), count))
-                _quantiles_into(buf, n, count, pos, out)
+                _quantiles_into(buf, n, count, args, out)
 
             def mean_rows_only():
                 check(lib.d3p_predict_mean_rows(stream_ptr(), C.byref(ms), ptr(X), count, ptr(lat), d + 1, 0, d, n, ptr(buf), count))

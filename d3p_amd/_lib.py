@@ -10,8 +10,8 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libd3p_hip.so")
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip")]
-_DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip")]
+_DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
 D3P_BATCH_EXPLICIT, D3P_BATCH_FEISTEL, D3P_BATCH_POISSON = 0, 1, 2
@@ -323,6 +323,10 @@ SIGNATURES = {
     "d3p_col_hpdi": (C.c_int, [_V, _V, _I32, C.c_int64, _U32, _U64, _U32, C.POINTER(C.c_uint32), _V, C.c_int64]),
     "d3p_col_hpdi_max_n": (C.c_uint32, []),
     "d3p_col_hpdi_cols_per_group": (C.c_uint32, [_U32]),
+    # CRPS and rank (PIT) counts per column of a draws x cols matrix against an observation (d3p_amd/scoring.py): added symbols, ABI 9 unchanged
+    "d3p_col_crps": (C.c_int, [_V, _V, _I32, C.c_int64, _U32, _U64, _V, _V, C.c_int64, _V, C.c_int64]),
+    "d3p_col_crps_max_n": (C.c_uint32, []),
+    "d3p_col_crps_cols_per_group": (C.c_uint32, [_U32]),
     # per-example gradient norms without the rows and the profile of a vector of norms (d3p_amd/clipping.py): added symbols, ABI 9 unchanged
     "d3p_logreg_grad_norms_workspace": (_SZ, [_PM, _U32]),
     "d3p_logreg_grad_norms": (C.c_int, [_V, _PM, _V, _V, _V, _U32, _U32, _U32, _V, _V, _V, _V, _V, _SZ]),

@@ -1,7 +1,9 @@
 // What the model-free reducers over a draws x columns matrix share: d3p_psis.hip, d3p_quantiles.hip, d3p_hpdi.hip and
 // d3p_grad_norms.hip select or sort on ONE order-preserving uint32 key and interpolate by ONE rule; they and the mixture's files
 // (d3p_gmm_density.hip, d3p_predict_gmm.hip) share the host checks below.  A new column reducer includes this header and defines no
-// key map of its own.  The training translation units do not include it.
+// key map of its own; one that needs the whole sorted column (k_col_hpdi, and k_col_crps of d3p_crps_kernel.h, both compiled in
+// d3p_hpdi.hip) uses d3p_colsort.h behind this header and defines no sort, no key staging and no form rule of its own either.  The
+// training translation units do not include it.
 #pragma once
 #include "d3p_host.h"
 
@@ -44,7 +46,7 @@ __device__ inline double lerp_linear(double va, double vb, double g)
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
-// 144 KiB of dynamic LDS: what the key buffers of k_psis_loo, k_col_quantiles and k_col_hpdi may take beside at most 9 KiB of static
+// 144 KiB of dynamic LDS: what the key buffers of k_psis_loo, k_col_quantiles, k_col_hpdi and k_col_crps may take beside at most 9 KiB of static
 // LDS within a compute unit's 160 KiB
 #define D3P_DYN_LDS_MAX 147456
 

@@ -7,12 +7,8 @@
 // k_col_hpdi<COLS>: 256 threads, one workgroup owns COLS adjacent columns, thread t = (draw lane t / COLS, column lane t % COLS); the
 // DL = 256 / COLS draw lanes of a column take the draws (pairs, windows) dl, dl + DL, ...
 //   pass 0   every value once from memory, eight loads in flight per thread: the column's NaN flag, and its order-preserving uint32
-//            key (key_of, d3p_colreduce.h) into dynamic LDS as [draw][COLS].
-//   sort     a bitonic network in its all-ascending form, in place on the keys: per size k = 2, 4, .. one "flip" step (i against the
-//            mirror position of its block of k) and then the steps at distance k/4, k/8, .. 1 (i against i + j).  Every
-//            compare-exchange puts the smaller key at the lower index, so positions >= n behave as keys above all others that never
-//            move: a compare-exchange whose partner is >= n is skipped and n needs no padding to a power of two.  One barrier per
-//            step; within a step a thread loads the keys of eight of its pairs before it stores any (the pairs are disjoint).
+//            key (key_of, d3p_colreduce.h) into dynamic LDS as [draw][COLS] (h_stage, d3p_colsort.h).
+//   sort     the shared bitonic network (h_sort, d3p_colsort.h), in place on the keys.
 //   scan     per L one pass over the n - L windows: each draw lane keeps the minimum of (length, i) as ONE uint64 = rank(length) << 32
 //            | i, the column's lanes merge theirs through LDS (a tree of minima: order-independent, so the bits are a function of the
 //            column's values and (n, L) alone).  rank: float32 lengths are >= +0, +inf or NaN (inf - inf): NaN -> 0, else the bits
@@ -27,6 +23,7 @@
 // indices of a group are consecutive, no conflict; at j < G they are runs of j with gaps of j, which fall two by two on the same
 // banks: a 2-way conflict on the loads of those steps (the last log2(G) steps of every size), none in pass 0 or the scan.
 #include "d3p_colreduce.h"
+#include "d3p_colsort.h"
 #include "d3p_device.h"
 
 #pragma clang fp contract(off)
@@ -34,8 +31,6 @@
 namespace d3p {
 
 #define D3P_H_MAX 8                   // window lengths per launch
-#define D3P_H_ILP 8                   // pairs of a network step, and loads of pass 0, a thread has in flight
-#define D3P_H_MAX_N(COLS) (D3P_DYN_LDS_MAX / (4 * (COLS)))   // 1152 | 4608 | 18432
 
 struct HpdiArgs {
     const uint32_t* m;   // the matrix's words: float32 or int32
@@ -65,57 +60,6 @@ __device__ inline uint64_t h_window(uint32_t klo, uint32_t khi, uint32_t i, int3
     return ((uint64_t)r << 32) | i;
 }
 
-// One step of the network on the keys [n][COLS] of column lane cl, the pairs dl, dl + DL, .. of the step:
-//   FLIP   lg = log2 k:  pair p of block p / (k/2) is (block k + off, block k + k - 1 - off), off = p mod (k/2)
-//   else   lg = log2 j:  pair p is (i, i + j), i = (p / j) 2 j + p mod j
-// The indices rise with p, so the pairs whose lower index (FLIP) or both indices (else) lie below n are a prefix 0 .. cnt - 1; a flip
-// pair whose upper index is >= n is skipped.  The pairs of a step are disjoint: a thread loads the keys of D3P_H_ILP of its pairs
-// before it stores any, which keeps that many LDS loads in flight where the keys fill the LDS and one wave runs per SIMD.
-template <int COLS, bool FLIP>
-__device__ inline void h_step(uint32_t* keys, int cl, uint32_t dl, uint32_t n, uint32_t lg)
-{
-    constexpr uint32_t DL = 256 / COLS;
-    const uint32_t w = 1u << lg;   // FLIP: k, else: j
-    uint32_t cnt;
-    if (FLIP) {
-        const uint32_t h = w >> 1, r = n & (w - 1u);
-        cnt = (n >> lg) * h + (r < h ? r : h);
-    } else {
-        const uint32_t r = n & (2u * w - 1u);
-        cnt = (n >> (lg + 1)) * w + (r > w ? r - w : 0u);
-    }
-    for (uint32_t p0 = dl; p0 < cnt; p0 += D3P_H_ILP * DL) {
-        uint32_t ia[D3P_H_ILP], ib[D3P_H_ILP], ka[D3P_H_ILP], kb[D3P_H_ILP];
-        bool ok[D3P_H_ILP];
-#pragma unroll
-        for (int u = 0; u < D3P_H_ILP; ++u) {
-            const uint32_t p = p0 + (uint32_t)u * DL;
-            if (FLIP) {
-                const uint32_t base = (p >> (lg - 1)) << lg, off = p & ((w >> 1) - 1u);
-                ia[u] = base + off;
-                ib[u] = base + w - 1u - off;
-                ok[u] = p < cnt && ib[u] < n;
-            } else {
-                ia[u] = ((p >> lg) << (lg + 1)) + (p & (w - 1u));
-                ib[u] = ia[u] + w;
-                ok[u] = p < cnt;
-            }
-            ka[u] = kb[u] = 0u;
-            if (ok[u]) {
-                ka[u] = keys[(size_t)ia[u] * COLS + cl];
-                kb[u] = keys[(size_t)ib[u] * COLS + cl];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < D3P_H_ILP; ++u) {
-            if (ok[u] && ka[u] > kb[u]) {
-                keys[(size_t)ia[u] * COLS + cl] = kb[u];
-                keys[(size_t)ib[u] * COLS + cl] = ka[u];
-            }
-        }
-    }
-}
-
 template <int COLS>
 __global__ __launch_bounds__(256) void k_col_hpdi(HpdiArgs a)
 {
@@ -135,22 +79,9 @@ __global__ __launch_bounds__(256) void k_col_hpdi(HpdiArgs a)
 
     // pass 0: the column's NaN flag and its keys; D3P_H_ILP loads from memory in flight per thread
     uint32_t nan = 0u;
-    for (uint32_t s0 = dl; s0 < n; s0 += D3P_H_ILP * DL) {
-        uint32_t u[D3P_H_ILP];
-#pragma unroll
-        for (int q = 0; q < D3P_H_ILP; ++q) {
-            const uint32_t s = s0 + (uint32_t)q * DL;
-            u[q] = live && s < n ? col[(size_t)s * ld] : 0u;
-        }
-#pragma unroll
-        for (int q = 0; q < D3P_H_ILP; ++q) {
-            const uint32_t s = s0 + (uint32_t)q * DL;
-            if (s < n) {
-                if (!dtype && word_is_nan(u[q])) nan = 1u;
-                H_KEY(s) = key_of(u[q], dtype);
-            }
-        }
-    }
+    h_stage<COLS>(keys, col, ld, live, cl, (uint32_t)dl, n, dtype, [&](uint32_t u, uint32_t) {
+        if (!dtype && word_is_nan(u)) nan = 1u;
+    });
     r_min[t] = nan;
     __syncthreads();
     for (int w = DL / 2; w > 0; w >>= 1) {
@@ -160,15 +91,7 @@ __global__ __launch_bounds__(256) void k_col_hpdi(HpdiArgs a)
     nan = (uint32_t)r_min[cl];
     __syncthreads();
 
-    // the sort: sizes k = 2^lk while k / 2 < n (positions >= n never move: a partner there is skipped)
-    for (uint32_t lk = 1; (1u << (lk - 1)) < n; ++lk) {
-        h_step<COLS, true>(keys, cl, dl, n, lk);            // flip within blocks of k = 2^lk
-        __syncthreads();
-        for (uint32_t lj = lk - 1; lj-- > 0;) {             // distance 2^lj = k / 4 .. 1
-            h_step<COLS, false>(keys, cl, dl, n, lj);
-            __syncthreads();
-        }
-    }
+    h_sort<COLS>(keys, cl, (uint32_t)dl, n);
 
     for (uint32_t qi = 0; qi < a.Q; ++qi) {
         const uint32_t L = a.len[qi];                       // L <= n - 1: at least one window
@@ -219,8 +142,7 @@ uint32_t d3p_col_hpdi_max_n(void) { return (uint32_t)D3P_H_MAX_N(2); }
 
 uint32_t d3p_col_hpdi_cols_per_group(uint32_t n)
 {
-    if (n < 1 || n > (uint32_t)D3P_H_MAX_N(2)) return 0u;
-    return n <= (uint32_t)D3P_H_MAX_N(32) ? 32u : n <= (uint32_t)D3P_H_MAX_N(8) ? 8u : 2u;
+    return h_cols_per_group(n);
 }
 
 int d3p_col_hpdi(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uint32_t n, uint64_t cols, uint32_t Q, const uint32_t* len_host,
@@ -254,3 +176,6 @@ int d3p_col_hpdi(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uin
 }
 
 }  // extern "C"
+
+// k_col_crps, the second reducer over a sorted column, is compiled here: it shares the sort above and the keys of d3p_colreduce.h
+#include "d3p_crps_kernel.h"

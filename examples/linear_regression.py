@@ -19,6 +19,10 @@ of the 90 % highest-density interval (numpyro's hpdi, kind="hpdi") and the summa
 --clipping-profile (off by default; d3p_amd.clipping) adds two lines after training: the quantiles of the per-example gradient norms of
 the whole table at the trained parameters, the share of rows the run's clipping threshold clips with the mean clip factor, and the
 median norm as the suggested threshold (Abadi et al. 2016).  They are computed from the private table without noise.
+--crps [N_DRAWS] (off by default; d3p_amd.scoring) adds, after training, on a held-out test split -- 2000 fresh rows from the process
+that generated the training table -- three lines: the mean CRPS of N_DRAWS posterior predictive draws against the observed outcomes +- its
+standard error, with its two parts (mae = E|X - y|, spread = 1/2 E|X - X'|); and the ten-bin PIT histogram as a density (1 in every bin:
+calibrated; a U shape: the predictive is too narrow; a hump: too wide).
 """
 import argparse
 import os
@@ -91,6 +95,26 @@ def clipping_profile_report(svi, state, X, y):
                 p.thresholds[0], p.clipped_fraction[0], p.mean_clip_factor[0], clipping.suggest_clipping_threshold(p))]
 
 
+def create_test_data(w_true, rows, obs_scale, seed=321):
+    """The held-out test split of --crps: fresh rows from the process of create_toy_data at the same w_true, on a seed of their own."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    X = torch.randn(rows, w_true.shape[0], generator=g, device="cuda")
+    y = X @ w_true + obs_scale * torch.randn(rows, generator=g, device="cuda")
+    return X.contiguous(), y.to(torch.float32).contiguous()
+
+
+def crps_report(model, svi, state, X_test, y_test, num_draws, seed=5):
+    """The lines of --crps (d3p_amd.scoring): mean CRPS +- its standard error with mae and spread, and the ten-bin PIT histogram as a
+    density, of num_draws posterior predictive draws against the test split's observed outcomes."""
+    from d3p_amd import scoring
+    import d3p_amd.random.debug as jax_random
+    res = scoring.posterior_predictive_crps(jax_random.PRNGKey(seed), num_draws, model, (X_test, y_test), svi.guide, svi.get_params(state))
+    density = (res.pit_histogram / res.n_rows * res.pit_histogram.shape[0]).cpu().tolist()
+    return ["CRPS on the test split ({} rows, {} draws): {:.4f} +- {:.4f}".format(res.n_rows, res.n_draws, float(res.crps), float(res.se)),
+            "mae {:.4f}, spread {:.4f}".format(float(res.mae), float(res.spread)),
+            "PIT histogram (density, 10 bins): " + " ".join("{:.3f}".format(v) for v in density)]
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
@@ -122,6 +146,9 @@ def main(args):
         print("\n".join(intervals_report(model, svi, state, X, y, args.intervals, kind=kind)))
     if getattr(args, "clipping_profile", False):
         print("\n".join(clipping_profile_report(svi, state, X, y)))
+    if getattr(args, "crps", None) is not None:
+        X_test, y_test = create_test_data(w_true, 2000, args.obs_scale)
+        print("\n".join(crps_report(model, svi, state, X_test, y_test, args.crps)))
     return first, last, err0, err
 
 
@@ -146,4 +173,7 @@ if __name__ == "__main__":
     parser.add_argument('--clipping-profile', action='store_true',
                         help='after training, report the quantiles of the per-example gradient norms on the whole table, the share of '
                              'rows the clipping threshold clips and the suggested threshold (a diagnostic of the private table, not a release)')
+    parser.add_argument('--crps', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, report the mean CRPS with mae and spread and the PIT histogram of N_DRAWS (default 100) '
+                             'posterior predictive draws on a held-out test split')
     main(parser.parse_args())

@@ -1118,6 +1118,35 @@ uint32_t d3p_col_hpdi_max_n(void);
 /* the columns one workgroup of d3p_col_hpdi owns at n draws: 32, 8, 2, or 0 where n is not served (host only, no device call) */
 uint32_t d3p_col_hpdi_cols_per_group(uint32_t n);
 
+/* CRPS and rank (PIT) counts of the draws of every column against an observation (model-free; d3p_amd/scoring.py; d3p_crps.hip, d3p_crps_kernel.h;
+ * DESIGN.md 4q); added symbols, ABI 9 unchanged.  m_dev[s * ld + c] is a draws x cols matrix of float32 (dtype 0) or int32 (dtype 1)
+ * values, y_dev cols words of the same dtype.  Per column of n draws x_s, sorted ascending as s_0 <= .. <= s_{n-1}, and y = y_dev[c],
+ * with d_i = (double)s_i - (double)y, A = sum_i |d_i| and G = sum_i (2 i - n + 1) d_i (= 1/2 sum_i sum_j |x_i - x_j|) in float64:
+ *   out_dev[0 * out_ld + c] = crps      = A / n - G / n^2          (the ECDF form: properscoring.crps_ensemble, scoringRules::crps_sample)
+ *   out_dev[1 * out_ld + c] = crps_fair = A / n - G / (n (n - 1))  (NaN at n = 1: 0 / 0 is the rule)
+ *   out_dev[2 * out_ld + c] = mae       = A / n
+ *   out_dev[3 * out_ld + c] = spread    = G / n^2                  (1/2 E|X - X'| over the empirical distribution)
+ *   counts_dev[0 * counts_ld + c] = below = #{s : x_s < y},   counts_dev[1 * counts_ld + c] = equal = #{s : x_s == y}
+ * each float output rounded to float32 once.  The counts are exact and use IEEE comparison of the values: a NaN draw counts in neither,
+ * a NaN y gives 0 and 0, -0 equals +0.  A NaN or +-inf draw, or a non-finite y, makes the column's four float outputs NaN and touches
+ * no other column; int32 is never non-finite.  For 0/1 draws crps = (p - y)^2 with p the draws' frequency of 1 (the Brier score).
+ * The column is sorted in LDS by d3p_col_hpdi's network, one workgroup per d3p_col_crps_cols_per_group(n) adjacent columns: 32 (n <=
+ * 1152), 8 (n <= 4608), 2 (n <= 18432 = d3p_col_crps_max_n()); there is no streamed form: a larger n is D3P_E_UNSUPPORTED.
+ * Deterministic: a draw lane adds its terms i = dl, dl + DL, .. in ascending i, the DL = 256 / form lanes of a column merge in one
+ * fixed tree; no floating-point atomics, no workspace, no host synchronisation.  A column's output bits depend on that column's
+ * values, y and n alone -- not on the order of its draws, ld, out_ld, counts_ld or the other columns of the launch.
+ * D3P_E_INVALID_ARG before any launch: a null pointer, a pointer not aligned to 4 bytes, a dtype other than 0 / 1, n < 1, ld < cols,
+ * out_ld < cols, counts_ld < cols, m_dev / y_dev / out_dev / counts_dev not device memory.  n > d3p_col_crps_max_n(), or more than
+ * 2^31 - 1 column groups: D3P_E_UNSUPPORTED; cols == 0: D3P_OK, no launch. */
+int d3p_col_crps(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uint32_t n, uint64_t cols,
+                 const void* y_dev,            /* cols words of the matrix's dtype */
+                 float* out_dev, int64_t out_ld,        /* 4 rows: crps, crps_fair, mae, spread */
+                 uint32_t* counts_dev, int64_t counts_ld /* 2 rows: below, equal */);
+/* the largest n d3p_col_crps serves: 18432 (host only, no device call) */
+uint32_t d3p_col_crps_max_n(void);
+/* the columns one workgroup of d3p_col_crps owns at n draws: 32, 8, 2, or 0 where n is not served (host only, no device call) */
+uint32_t d3p_col_crps_cols_per_group(uint32_t n);
+
 /* The conditional mean of the observed site over given posterior draws, as an n x rows matrix (d3p_amd/intervals.py: the matrix
  * d3p_col_quantiles reduces for a credible interval); added symbol, ABI 9 and d3p_logreg_model unchanged.  With t[s, r] as for
  * d3p_loglik_rows:

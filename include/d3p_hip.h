@@ -92,6 +92,18 @@ int d3p_tf_randint(void* stream, const uint32_t* key_dev, uint64_t n, int32_t mi
                    int32_t* out_dev);
 
 /* ---------------------------------------------------------------------------------------------
+ * Workspaces (every entry below that takes `workspace_dev, workspace_bytes`; its size is the `d3p_*_workspace()` function
+ * declared beside it, called with the same arguments).  The contents on entry are unspecified: whatever an entry reads --
+ * accumulators, counters, flags, tagged words, status words -- it has initialised in the same call.  An entry writes nothing
+ * outside [workspace_dev, workspace_dev + d3p_*_workspace()), however much larger workspace_bytes is.  A buffer shorter than
+ * that size is refused with D3P_E_WORKSPACE before anything is launched: outputs, state and the buffer stay as they were.
+ * What one run leaves in a workspace never changes what the next computes: the same arguments give the same output bits on a
+ * fresh buffer, on one filled with anything, and on one another run has used.  For the entries of a sequence the caller
+ * drives (begin -> prepare -> step ... -> end; local_sums -> finalize / apply) this holds for the sequence as a whole, which
+ * keeps its schedule, prepared batch and accumulators in the workspace from one of its calls to the next.
+ * ------------------------------------------------------------------------------------------- */
+
+/* ---------------------------------------------------------------------------------------------
  * Minibatch samplers
  * ------------------------------------------------------------------------------------------- */
 /* sample_from_array(key, arange(capacity), n, 0): 10-round Feistel permutation with cycle walking,

@@ -9,7 +9,7 @@ from .version import __version__  # noqa: F401
 
 __all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "loo", "posterior_loo", "LOOResult",
            "diagnostics", "log_likelihood_total", "log_joint", "guide_diagnostic", "GuideDiagnostic", "mixture_diagnostics", "intervals", "clipping",
-           "scoring"]
+           "scoring", "model_weights"]
 
 
 def __getattr__(name):
@@ -19,9 +19,10 @@ def __getattr__(name):
     # and d3p_amd.criteria (waic, posterior_waic, compare) and d3p_amd.diagnostics (whole-table log joint, ELBO and the Pareto k of a
     # guide) and d3p_amd.mixture_diagnostics (the same for the mixture model's guide) and d3p_amd.intervals (credible and predictive
     # intervals, equal-tailed or highest-density, per-column quantiles, the latent summary) and d3p_amd.clipping (whole-table per-example gradient norms and the
-    # clipping profile) and d3p_amd.scoring (CRPS and PIT calibration of predictive draws) without making `import d3p_amd` import torch
+    # clipping profile) and d3p_amd.scoring (CRPS and PIT calibration of predictive draws) and d3p_amd.model_weights (stacking and
+    # pseudo-BMA(+) weights of M models, the comparison table) without making `import d3p_amd` import torch
     if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "diagnostics", "mixture_diagnostics",
-                "intervals", "clipping", "scoring"):
+                "intervals", "clipping", "scoring", "model_weights"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("loo", "posterior_loo", "LOOResult"):   # PSIS-LOO (d3p_amd.criteria), under the same lazy rule

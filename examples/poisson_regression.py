@@ -30,6 +30,11 @@ median norm as the suggested threshold (Abadi et al. 2016).  They are computed f
 that generated the training table -- three lines: the mean CRPS of N_DRAWS posterior predictive draws against the observed counts +- its
 standard error, with its two parts (mae = E|X - y|, spread = 1/2 E|X - X'|); and the ten-bin PIT histogram as a density (1 in every bin:
 calibrated; a U shape: the predictive is too narrow; a hump: too wide).
+--compare-models [N_DRAWS] (off by default; d3p_amd.model_weights) fits four candidates on the same counts with the same settings --
+Poisson and linear regression, each with and without an intercept -- takes the PSIS-LOO of each under N_DRAWS draws from its guide, and
+prints the comparison table sorted by elpd_loo (rank, elpd_loo, p_loo, elpd_diff and dse against the best model, the stacking weight,
+se, and whether a Pareto k warns) with the stacking run's iteration count and duality gap, then the pseudo-BMA+ weights of 1000
+Bayesian-bootstrap replicates with the bootstrap standard error of each model's elpd.
 """
 import argparse
 import os
@@ -158,6 +163,23 @@ def crps_report(model, svi, state, X_test, y_test, num_draws, seed=5):
             "PIT histogram (density, 10 bins): " + " ".join("{:.3f}".format(v) for v in density)]
 
 
+def compare_models_report(fits, X, y, num_draws, seed=6):
+    """The lines of --compare-models: `fits` maps a name to (model, svi, state); PSIS-LOO of each on loo_report's draws, the table with
+    stacking weights (d3p_amd.model_weights.compare_models) and the pseudo-BMA+ weights of 1000 bootstrap replicates."""
+    from d3p_amd import model_weights
+    import d3p_amd.random.debug as jax_random
+    results = {name: loo_report(model, svi, state, X, y, num_draws) for name, (model, svi, state) in fits.items()}
+    table = model_weights.compare_models(results, method="stacking")
+    mw = table.weights
+    lines = ["model comparison ({} rows, {} posterior draws each), stacking weights:".format(X.shape[0], num_draws), table.table(),
+             "stacking: {} EM updates, converged {}, duality gap {:.2e}, stacked elpd {:.2f}".format(
+                 mw.n_iter, mw.converged, float(mw.gap), float(mw.stacked_elpd))]
+    plus = model_weights.pseudo_bma_weights(results, rng_key=jax_random.PRNGKey(seed), n_boot=1000)
+    lines.append("pseudo-BMA+ (1000 bootstrap replicates): " + ", ".join(
+        "{} {:.3f} (se_boot {:.2f})".format(name, w, se) for name, w, se in zip(plus.names, plus.weights.tolist(), plus.se_boot.tolist())))
+    return lines
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
@@ -215,6 +237,12 @@ def main(args):
     if getattr(args, "crps", None) is not None:
         X_test, y_test = create_test_data(w_true, 2000)
         print("\n".join(crps_report(model, svi, state, X_test, y_test, args.crps)))
+    if getattr(args, "compare_models", None) is not None:
+        fits = {"poisson+1": (model, svi, state)}
+        for name, cls, intercept in (("poisson", PoissonRegression, False), ("linear+1", LinearRegression, True), ("linear", LinearRegression, False)):
+            other = cls(d, prior_scale=1.0, intercept=intercept)
+            fits[name] = (other,) + tuple(linear_fit if name == "linear+1" and linear_fit else fit(other, X, y, args))
+        print("\n".join(compare_models_report(fits, X, y, args.compare_models)))
     return first, last, err0, err
 
 
@@ -246,4 +274,8 @@ if __name__ == "__main__":
     parser.add_argument('--crps', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, report the mean CRPS with mae and spread and the PIT histogram of N_DRAWS (default 100) '
                              'posterior predictive draws on a held-out test split')
+    parser.add_argument('--compare-models', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, fit the Poisson and the linear family with and without an intercept on the same counts and '
+                             'print the PSIS-LOO comparison table of N_DRAWS (default 100) draws each with stacking weights, and the '
+                             'pseudo-BMA+ weights')
     main(parser.parse_args())

@@ -1245,6 +1245,54 @@ int d3p_logreg_evaluate_sites_particles(void* stream, const d3p_logreg_model* mo
 int d3p_px_eps_sites_particles(void* stream, const uint32_t* jax_key_dev, uint32_t B_total, uint32_t pos0, uint32_t B_local,
                                uint32_t num_particles, const int32_t* site_sizes_host, int32_t n_sites, float* eps_dev);
 
+/* Model weights for M candidate models from their pointwise elpd vectors (model-free; d3p_amd/model_weights.py; d3p_model_weights.hip;
+ * DESIGN.md 4r); added symbols, ABI 9 unchanged.  e_dev[m * ld + r] is a models x rows float32 matrix: row m is model m's pointwise
+ * elpd (elpd_loo or elpd_waic), 1 <= M <= 16, 1 <= rows <= 2^32 - 1, ld >= rows; nothing in [rows, ld) is read into a result.  Every
+ * value is widened to float64 on load and all arithmetic is float64.  Special values, both entries: a -inf in some models of a row is
+ * legitimate (that model's density of the row is 0); a NaN anywhere, a +inf anywhere, or a row that is -inf in every model makes
+ * EVERY output NaN.  No floating-point atomics, no cooperative launch, no kernel that waits on another workgroup; the output bits are
+ * a function of the arguments alone (not of ld, the device, or what the workspace held).
+ * D3P_E_INVALID_ARG before the device is touched: a null pointer, e_dev not aligned to 4 bytes, an output or the workspace not aligned
+ * to 8 bytes, M outside 1..16, rows < 1, ld < rows, B outside 1..65535, tol not > 0 (NaN included), max_iter < 1, then pointers that
+ * are not device memory; rows > 2^32 - 1: D3P_E_UNSUPPORTED; a workspace shorter than the size function's: D3P_E_WORKSPACE.
+ *
+ * Stacking of predictive distributions (Yao, Vehtari, Simpson & Gelman 2018): maximise f(w) = sum_r log sum_m w_m exp(e[m, r]) over
+ * the simplex by the EM fixed point from w = 1 / M.  With mx_r = max_m e[m, r] and p[m, r] = exp(e[m, r] - mx_r), evaluation j = 0,
+ * 1, .. at the current w computes
+ *   den_r = sum_k w_k p[k, r] (k ascending),  g_m = (sum_r p[m, r] / den_r) / rows,  f = sum_r (mx_r + log den_r),  gap = max_m g_m - 1
+ * and stops with converged = 1 where gap <= tol, with converged = 0 where gap is NaN or j == max_iter; otherwise w_m <- w_m g_m.
+ * n_iter = j, the number of updates applied: w_out, gap and f always belong together.  By concavity (f(w*) - f(w)) / rows <= gap.
+ * w is not renormalised.  One evaluation is two launches: a strip kernel (the strip count a function of rows alone; a lane adds its
+ * rows in ascending order, the 256 lanes merge in one fixed tree) and a one-workgroup kernel that adds the strips' partials in strip
+ * order and writes g, gap, f, the new w, the count and a `done` flag to the workspace.  Every launch reads `done` first and returns
+ * without writing when it is set.  The host enqueues evaluations in chunks (128; d3p_stacking_set_chunk) and reads the flag once per
+ * chunk; the outputs do not depend on the chunk size.  p is recomputed in every evaluation: no rows x M array is written.
+ *   w_out_dev: M float64;  info_out_dev: 4 float64 {n_iter, converged, gap, f}. */
+size_t d3p_stacking_workspace(uint64_t rows, uint32_t M);
+int d3p_stacking_weights(void* stream, const float* e_dev, int64_t ld, uint64_t rows, uint32_t M, double tol, uint32_t max_iter,
+                         double* w_out_dev, double* info_out_dev, void* workspace_dev, size_t workspace_bytes);
+/* test aid: evaluations enqueued between two reads of the flag; n >= 64, or 0 for the default (128).  Returns the value in force
+ * before the call, or -1 (D3P_E_INVALID_ARG) for 0 < n < 64.  Host only, no device call. */
+int d3p_stacking_set_chunk(int32_t n);
+/* the rows one strip of the stacking kernel covers at least (256: one row per lane); rows / strips grows beyond it (host only) */
+uint32_t d3p_stacking_strip_rows(void);
+
+/* Pseudo-BMA+ weights: pseudo-BMA stabilised by the Bayesian bootstrap over the rows, B replicates, 1 <= B <= 65535.  key_dev is a
+ * threefry key (2 x uint32, device memory).  Replicate b weighs row r with
+ *   g[b, r] = -log(1 - u[b, r]),  u[b, r] = the float32 uniform in [0, 1) of jax.random.uniform's rule applied to
+ *   word (r & 1) of threefry2x32(key, (c0, c1) = (r >> 1, b))
+ * -- a function of (key, b, r) alone, not of B, rows, ld or the grid.  1 - u is exact in float32; the logarithm is the float64 log of
+ * that value.  Per replicate in float64, rows ascending within a strip and strips in ascending order:
+ *   S_b = sum_r g[b, r],  T_bm = sum_r g[b, r] e[m, r] (one fused multiply-add per term; a term with g = 0 contributes 0 also where
+ *   e = -inf),  z[b, m] = (rows T_bm) / S_b,  w_b = softmax_m z[b, .] (exp(z - max z) over its sum, m ascending)
+ *   z_out_dev[b * M + m] = z[b, m];  w_out_dev[m] = (sum_b w_b[m]) / B  (lane t adds b = t, t + 256, .. ascending, one fixed tree)
+ * The B x rows matrix is never written: the workspace holds the strips' partials and the B x M replicate weights. */
+size_t d3p_bb_pseudo_bma_workspace(uint64_t rows, uint32_t M, uint32_t B);
+int d3p_bb_pseudo_bma(void* stream, const uint32_t* key_dev, const float* e_dev, int64_t ld, uint64_t rows, uint32_t M, uint32_t B,
+                      double* w_out_dev, double* z_out_dev, void* workspace_dev, size_t workspace_bytes);
+/* the rows of one staged chunk of the bootstrap kernel, the least a strip covers (256) (host only, no device call) */
+uint32_t d3p_bb_pseudo_bma_strip_rows(void);
+
 #ifdef __cplusplus
 }
 #endif

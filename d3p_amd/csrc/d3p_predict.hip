@@ -15,6 +15,7 @@
 #include "d3p_device.h"
 #include "d3p_glm_tile.h"
 #include "d3p_host.h"
+#include "d3p_outcome.h"
 
 namespace d3p {
 
@@ -56,12 +57,7 @@ __device__ __forceinline__ void seed_site_key(const uint32_t (&chain)[2], int in
     }
 }
 
-// BernoulliLogits.probs = expit(logits) = 1 / (1 + exp(-logits))
-__device__ __forceinline__ float sigmoid_probs(float logit) { return 1.0f / (1.0f + expf(-logit)); }
-
-// numpyro Bernoulli.sample = jax.random.bernoulli(key, probs, shape) = uniform(key, shape) < probs, returned as int32; `bits` is
-// word j of the site's threefry stream (jax's array layout: flat index j = row * width + col)
-__device__ __forceinline__ int32_t bernoulli_draw(uint32_t bits, float p) { return bits_to_uniform(bits, 0.0f, 1.0f) < p ? 1 : 0; }
+// (sigmoid_probs and bernoulli_draw: d3p_outcome.h, shared with k_predict_stats)
 
 // ---- latent draws ------------------------------------------------------------------------------------------------------------
 #define D3P_PREDICT_MAX_SITES 8

@@ -114,9 +114,11 @@ def predictive_samples(rng_key, model, posterior_samples, *model_args, **kwargs)
     return obs[0] if single else obs
 
 
-def _draw(key, n, model, fam, X, rows, d, guide, gparams, substitutes):
-    """n draws of the latent sites and of obs for the linear / Poisson families: one d3p_predict_draws launch with the multi form's
-    key split -- exactly the launch modelling makes for a LogisticRegression of the same layout -- then the outcome kernel."""
+def _latents(key, n, model, rows, d, guide, gparams, substitutes):
+    """n draws of the latent sites and the obs keys: one d3p_predict_draws launch with the multi form's key split -- exactly the
+    launch modelling makes for a LogisticRegression of the same layout.  Returns ({"w"[, "intercept"]} as views of the packed buffer,
+    the kernels' latent tuple (first, ld, w_off, b_col), the obs keys (n, 2) or None, the obs Site).  The half of _draw that
+    d3p_amd.ppc shares: there the outcomes are reduced (d3p_predict_stats) instead of stored."""
     dev = key.device
     posterior = guide is not None
     stand_in = _stand_in(model, d)
@@ -128,7 +130,9 @@ def _draw(key, n, model, fam, X, rows, d, guide, gparams, substitutes):
         for st in plan:
             if st.chain != "guide":
                 continue
-            if isinstance(guide, DiagonalNormalGuide):
+            if isinstance(guide, MeanFieldGuide):   # (logistic regression only: _check_guide)
+                loc, sc = gp[st.name + "_loc"], gp[st.name + "_std_log"]
+            elif isinstance(guide, DiagonalNormalGuide):
                 loc, sc = gp[guide.site + "_loc"], gp[guide.site + "_std_log"]
             else:
                 loc, sc = gp["auto_loc"], gp["auto_scale"]
@@ -147,11 +151,18 @@ def _draw(key, n, model, fam, X, rows, d, guide, gparams, substitutes):
     out = {"w": latent[:, w_cols]}
     if b_idx is not None:
         out["intercept"] = latent[:, b_idx]
+    return out, (latent, latent.shape[1], w_cols.start, -1 if b_idx is None else b_idx), obs_keys, obs_site
+
+
+def _draw(key, n, model, fam, X, rows, d, guide, gparams, substitutes):
+    """n draws of the latent sites and of obs for the linear / Poisson families: _latents, then the outcome kernel."""
+    out, latent, obs_keys, obs_site = _latents(key, n, model, rows, d, guide, gparams, substitutes)
     if obs_site.substituted:
+        dev = key.device
         o = torch.as_tensor(substitutes["obs"]).to(dev)
         out["obs"] = o.reshape((1,) + tuple(o.shape)).expand((n,) + tuple(o.shape))
     else:
-        out["obs"] = _outcomes(model, fam, X, rows, d, n, (latent, latent.shape[1], w_cols.start, -1 if b_idx is None else b_idx), obs_keys)
+        out["obs"] = _outcomes(model, fam, X, rows, d, n, latent, obs_keys)
     return out
 
 

@@ -23,6 +23,10 @@ median norm as the suggested threshold (Abadi et al. 2016).  They are computed f
 that generated the training table -- three lines: the mean CRPS of N_DRAWS posterior predictive draws against the observed outcomes +- its
 standard error, with its two parts (mae = E|X - y|, spread = 1/2 E|X - X'|); and the ten-bin PIT histogram as a density (1 in every bin:
 calibrated; a U shape: the predictive is too narrow; a hump: too wide).
+--ppc [N_DRAWS] (off by default; d3p_amd.ppc) adds, after training, one line per statistic -- mean, sd, min, max, zeros -- of the
+posterior predictive check on the training table: the statistic of the observed outcomes, its mean and central 90 % range over N_DRAWS
+data sets replicated from the trained guide, and the tail shares p_ge = P(T(y_rep) >= T(y)) and p_le.  The replicated data sets are
+reduced as they are drawn; they are never written.
 """
 import argparse
 import os
@@ -115,6 +119,15 @@ def crps_report(model, svi, state, X_test, y_test, num_draws, seed=5):
             "PIT histogram (density, 10 bins): " + " ".join("{:.3f}".format(v) for v in density)]
 
 
+def ppc_report(model, guide, params, X, y, num_draws, seed=7, statistics=("mean", "sd", "min", "max", "zeros")):
+    """The lines of --ppc (d3p_amd.ppc): per statistic the observed value, the replicated mean and central 90 % range, p_ge and p_le
+    of num_draws data sets replicated from the trained guide on the whole table."""
+    from d3p_amd import ppc
+    import d3p_amd.random.debug as jax_random
+    res = ppc.posterior_predictive_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), guide, params, statistics=statistics)
+    return ["posterior predictive check ({} rows, {} replicated data sets):".format(res.n_rows, res.n_draws)] + res.lines()
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
@@ -149,6 +162,8 @@ def main(args):
     if getattr(args, "crps", None) is not None:
         X_test, y_test = create_test_data(w_true, 2000, args.obs_scale)
         print("\n".join(crps_report(model, svi, state, X_test, y_test, args.crps)))
+    if getattr(args, "ppc", None) is not None:
+        print("\n".join(ppc_report(model, svi.guide, svi.get_params(state), X, y, args.ppc)))
     return first, last, err0, err
 
 
@@ -176,4 +191,7 @@ if __name__ == "__main__":
     parser.add_argument('--crps', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, report the mean CRPS with mae and spread and the PIT histogram of N_DRAWS (default 100) '
                              'posterior predictive draws on a held-out test split')
+    parser.add_argument('--ppc', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, print the posterior predictive check of N_DRAWS (default 100) replicated data sets: per '
+                             'statistic the observed value, the replicated mean and 90 %% range, p_ge and p_le')
     main(parser.parse_args())

@@ -12,6 +12,10 @@ d3p_amd.dputil on the restated Fourier accountant; --sigma gives it directly.
 --clipping-profile (off by default; d3p_amd.clipping) adds two lines after training: the quantiles of the per-example gradient norms of
 the whole table at the trained parameters, the share of rows the script's clipping threshold (1.0) clips with the mean clip factor, and the
 median norm as the suggested threshold (Abadi et al. 2016).  They are computed from the private table without noise.
+--ppc [N_DRAWS] (off by default; d3p_amd.ppc) adds, after training, one line per statistic -- mean, sd, min, max, zeros -- of the
+posterior predictive check on the training table: the statistic of the observed outcomes, its mean and central 90 % range over N_DRAWS
+data sets replicated from the trained guide, and the tail shares p_ge = P(T(y_rep) >= T(y)) and p_le.  The replicated data sets are
+reduced as they are drawn; they are never written.
 """
 import argparse
 import os
@@ -56,6 +60,15 @@ def clipping_profile_report(svi, state, X, y):
                 p.n, p.n_nonfinite, quant, p.mean, p.max),
             "at C = {:g}: clipped fraction {:.4f}, mean clip factor {:.4f}; suggested threshold (median norm) {:.4f}".format(
                 p.thresholds[0], p.clipped_fraction[0], p.mean_clip_factor[0], clipping.suggest_clipping_threshold(p))]
+
+
+def ppc_report(model, guide, params, X, y, num_draws, seed=7, statistics=("mean", "sd", "min", "max", "zeros")):
+    """The lines of --ppc (d3p_amd.ppc): per statistic the observed value, the replicated mean and central 90 % range, p_ge and p_le
+    of num_draws data sets replicated from the trained guide on the whole table."""
+    from d3p_amd import ppc
+    import d3p_amd.random.debug as jax_random
+    res = ppc.posterior_predictive_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), guide, params, statistics=statistics)
+    return ["posterior predictive check ({} rows, {} replicated data sets):".format(res.n_rows, res.n_draws)] + res.lines()
 
 
 def main(args):
@@ -119,6 +132,8 @@ def main(args):
             float(test[1].mean()), float(pred.float().mean())))
     if getattr(args, "clipping_profile", False):   # both guides: the hand-written one draws its eps per site
         print("\n".join(clipping_profile_report(svi, svi_state, *train)))
+    if getattr(args, "ppc", None) is not None:   # both guides
+        print("\n".join(ppc_report(model, guide, svi.get_params(svi_state), *train, args.ppc)))
     return accs, train_losses
 
 
@@ -138,4 +153,7 @@ if __name__ == "__main__":
     parser.add_argument('--clipping-profile', action='store_true',
                         help='after training, report the quantiles of the per-example gradient norms on the whole table, the share of '
                              'rows the clipping threshold clips and the suggested threshold (a diagnostic of the private table, not a release)')
+    parser.add_argument('--ppc', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, print the posterior predictive check of N_DRAWS (default 100) replicated data sets: per '
+                             'statistic the observed value, the replicated mean and 90 %% range, p_ge and p_le')
     main(parser.parse_args())

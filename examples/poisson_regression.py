@@ -35,6 +35,12 @@ Poisson and linear regression, each with and without an intercept -- takes the P
 prints the comparison table sorted by elpd_loo (rank, elpd_loo, p_loo, elpd_diff and dse against the best model, the stacking weight,
 se, and whether a Pareto k warns) with the stacking run's iteration count and duality gap, then the pseudo-BMA+ weights of 1000
 Bayesian-bootstrap replicates with the bootstrap standard error of each model's elpd.
+--ppc [N_DRAWS] (off by default; d3p_amd.ppc) adds, after training, one line per statistic -- mean, sd, min, max, zeros, dispersion
+(variance over mean) -- of the posterior predictive check: the statistic of the observed counts, its mean and central 90 % range over
+N_DRAWS data sets replicated from the trained guide, and the tail shares p_ge = P(T(y_rep) >= T(y)) and p_le.  The replicated data
+sets are reduced as they are drawn; they are never written.
+--zero-inflate SHARE (default 0: the data are unchanged) sets that share of the training counts to 0 before fitting, so that --ppc has
+something to find: the Poisson family cannot reproduce the excess zeros (p_ge of `zeros` and of `dispersion` go to 0).
 """
 import argparse
 import os
@@ -180,10 +186,33 @@ def compare_models_report(fits, X, y, num_draws, seed=6):
     return lines
 
 
+def ppc_report(model, svi, state, X, y, num_draws, seed=7, statistics=("mean", "sd", "min", "max", "zeros", "dispersion")):
+    """The lines of --ppc (d3p_amd.ppc): per statistic the observed value, the replicated mean and central 90 % range, p_ge and p_le
+    of num_draws data sets replicated from the trained guide on the whole table."""
+    from d3p_amd import ppc
+    import d3p_amd.random.debug as jax_random
+    res = ppc.posterior_predictive_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), svi.guide, svi.get_params(state),
+                                         statistics=statistics)
+    head = "posterior predictive check ({} rows, {} replicated data sets{}):".format(
+        res.n_rows, res.n_draws, ", {} with a marker".format(res.n_marked) if res.n_marked else "")
+    return [head] + res.lines()
+
+
+def zero_inflate(y, share, seed=99):
+    """y with `share` of its entries set to 0, chosen by a generator of its own (--zero-inflate)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return torch.where(torch.rand(y.shape[0], generator=g, device="cuda") < share, torch.zeros_like(y), y).contiguous()
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
     X, y, w_true = create_toy_data(N, d)
+    share = float(getattr(args, "zero_inflate", 0.0) or 0.0)
+    if not 0.0 <= share <= 1.0:
+        raise ValueError("--zero-inflate: a share in [0, 1]")
+    if share > 0.0:
+        y = zero_inflate(y, share)
     model = PoissonRegression(d, prior_scale=1.0, intercept=True)
     svi = DPSVI(model, AutoDiagonalNormal(model), Adam(args.learning_rate), Trace_ELBO(), dp_scale=args.sigma,
                 clipping_threshold=args.clip_threshold, num_obs_total=N, rng_suite=rng_suite)
@@ -243,6 +272,8 @@ def main(args):
             other = cls(d, prior_scale=1.0, intercept=intercept)
             fits[name] = (other,) + tuple(linear_fit if name == "linear+1" and linear_fit else fit(other, X, y, args))
         print("\n".join(compare_models_report(fits, X, y, args.compare_models)))
+    if getattr(args, "ppc", None) is not None:
+        print("\n".join(ppc_report(model, svi, state, X, y, args.ppc)))
     return first, last, err0, err
 
 
@@ -278,4 +309,9 @@ if __name__ == "__main__":
                         help='after training, fit the Poisson and the linear family with and without an intercept on the same counts and '
                              'print the PSIS-LOO comparison table of N_DRAWS (default 100) draws each with stacking weights, and the '
                              'pseudo-BMA+ weights')
+    parser.add_argument('--ppc', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, print the posterior predictive check of N_DRAWS (default 100) replicated data sets: per '
+                             'statistic the observed value, the replicated mean and 90 %% range, p_ge and p_le')
+    parser.add_argument('--zero-inflate', default=0.0, type=float, metavar='SHARE',
+                        help='set this share of the training counts to 0 before fitting (default 0: unchanged), for --ppc to find')
     main(parser.parse_args())

@@ -1293,6 +1293,46 @@ int d3p_bb_pseudo_bma(void* stream, const uint32_t* key_dev, const float* e_dev,
 /* the rows of one staged chunk of the bootstrap kernel, the least a strip covers (256) (host only, no device call) */
 uint32_t d3p_bb_pseudo_bma_strip_rows(void);
 
+/* Per-draw statistics of a replicated data set over its ROWS (d3p_amd/ppc.py: posterior predictive checks; d3p_rep_stats.hip, DESIGN.md
+ * 4s); added symbols, ABI 9 and d3p_logreg_model unchanged.  Every other reduction of this library over a draws x rows matrix runs over
+ * the draws, once per row; this one runs over the rows, once per draw.
+ * For draw s over the values v[s, r], r < rows (float32 or int32, taken to float64 exactly), and a host-given float64 `shift` c, with
+ * out_dev of 5 n float64:
+ *   out_dev[0 n + s] = sum_r e,  e = fl64(v - c)
+ *   out_dev[1 n + s] = sum_r fl64(e e)           the product and the addition are two roundings, never a fused multiply-add
+ *   out_dev[2 n + s] = min_r v     out_dev[3 n + s] = max_r v
+ *   out_dev[4 n + s] = the number of r with v == 0 (-0.0 counts, NaN does not), an exactly representable float64
+ * Summation order of outputs 0 and 1, fixed and exactly d3p_loglik_draw_sums' (no floating-point atomics; the output bits are a function
+ * of the arguments only, identical between calls):
+ *   tiles = ceil(rows / 128);  per = ceil(tiles / 512);  strips = ceil(tiles / per)                    (a function of rows alone)
+ * A tile is four quarters of 32 consecutive rows.  A quarter's accumulator runs over the strip's tiles ascending and rows ascending,
+ * starting from 0.0; strip partial = ((q0 + q1) + q2) + q3; the strips are merged in ascending order, starting from strip 0's partial, by
+ * a second small launch on the same stream.
+ * min and max compare by value; which of +0 / -0 comes back is unspecified.  A NaN anywhere in a draw makes that draw's outputs 0 to 3
+ * NaN.  Nothing is clamped.  A draw's result does not depend on the other draws, on ld or on n.  The Poisson family's markers (-1 for a
+ * NaN predictor, 2147483647 for saturation) are values like any other: they show up in min and max.
+ * Workspace (the contract of "Workspaces": contents on entry unspecified, nothing written outside): d3p_rep_stats_workspace(rows, n) =
+ * strips x 5 x n float64 (0 for rows == 0 or rows >= 2^32), shared by both entries.
+ *
+ * d3p_rep_stats: the model-free form over a matrix that exists, m_dev[s * ld + r], dtype 0 = float32 and 1 = int32 as in
+ * d3p_col_quantiles.  Before any launch: D3P_E_INVALID_ARG for a null, misaligned (matrix 4 bytes, out and workspace 8) or non-device
+ * pointer, n < 1, rows == 0 (min and max of nothing are undefined), ld < rows, a dtype other than 0 / 1, a non-finite shift or a workspace
+ * smaller than the size above; D3P_E_UNSUPPORTED for rows >= 2^32 or n > 128 x 65535.
+ *
+ * d3p_predict_stats: the fused form, v[s, r] = BIT FOR BIT the outcome d3p_predict_glm (D3P_FAMILY_LINREG: float32, D3P_FAMILY_POISSON:
+ * int32) or d3p_predict_logreg (D3P_FAMILY_LOGREG: int32) stores for the same arguments -- the same product tile, intercept add, outcome
+ * rule and obs keys -- reduced without the n x rows matrix ever being written.  Arguments, limits and refusals are d3p_predict_glm's for
+ * the three families (D3P_E_UNSUPPORTED for D3P_FAMILY_GAUSS_MEAN and D3P_GUIDE_EXP_SITES; D3P_E_INVALID_ARG for d != model->d, a null
+ * or non-device X / latent / obs_keys / out, n < 1, a latent layout that does not fit, b_col against model->intercept, Poisson with
+ * 2 rows >= 2^32), then rows == 0, an out not aligned to 8 bytes, a non-finite shift and the workspace as above: D3P_E_INVALID_ARG.
+ * The outputs equal d3p_rep_stats' of the stored matrix by value, and bit for bit in outputs 0 and 1. */
+size_t d3p_rep_stats_workspace(uint64_t rows, uint32_t n);
+int d3p_rep_stats(void* stream, const void* m_dev, int32_t dtype, int64_t ld, uint32_t n, uint64_t rows, double shift, double* out_dev,
+                  void* workspace_dev, size_t workspace_bytes);
+int d3p_predict_stats(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, int32_t d, const float* latent_dev,
+                      int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, const uint32_t* obs_keys_dev, double shift,
+                      double* out_dev, void* workspace_dev, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

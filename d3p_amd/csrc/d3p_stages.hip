@@ -11,6 +11,9 @@ __device__ __forceinline__ void adam_update(float& x, float& m, float& v, float 
     // jax.example_libraries.optimizers.adam as wrapped by numpyro.optim.Adam
     m = (1.0f - h.b1) * g + h.b1 * m;
     v = (1.0f - h.b2) * g * g + h.b2 * v;
+    // the reference squares first, (1 - b2) * square(g): where g * g leaves float32 its v is +inf, which ((1 - b2) * g) * g misses
+    const float gg = g * g;
+    if (!__builtin_isfinite(gg)) v += (1.0f - h.b2) * gg;
     const float mhat = m / (1.0f - powf(h.b1, (float)(i + 1)));
     const float vhat = v / (1.0f - powf(h.b2, (float)(i + 1)));
     x = x - h.lr * mhat / (sqrtf(vhat) + h.adam_eps);
@@ -359,10 +362,12 @@ __global__ void k_gmm_log_prob(const float* __restrict__ x, uint32_t B, int d, c
         }
     }
     float best = -INFINITY;
+    bool nan = false;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
         if (k < K) {
             comp[k] = wave_sum(comp[k]) + logf(pis[k]);
+            nan |= comp[k] != comp[k];
             best = fmaxf(best, comp[k]);
         }
     }
@@ -370,7 +375,9 @@ __global__ void k_gmm_log_prob(const float* __restrict__ x, uint32_t B, int d, c
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
         if (k < K) acc += expf(comp[k] - best);
-    if (lane == 0) out[i] = best + logf(acc);
+    // every component -inf (an infinite coordinate, or z * z beyond float32): the row is -inf as jax's logsumexp gives it, not
+    // -inf - -inf = NaN; a NaN component still makes the row NaN
+    if (lane == 0) out[i] = (best == -INFINITY && !nan) ? -INFINITY : best + logf(acc);
 }
 
 __global__ void k_incr_i32(int32_t* p) { *p += 1; }

@@ -224,7 +224,9 @@ int d3p_logreg_evaluate(void* stream, const d3p_logreg_model* model, const float
                         float* loss_dev, void* workspace_dev, size_t workspace_bytes);
 
 /* GaussianMixture(locs, scales, pis).log_prob(x) for B rows of x (d3p/gmm.py:71-86; BASELINE config 3's
- * density).  x: B x d, locs/scales: K x d, pis: K (a simplex; validated by the host layer), K <= 64. */
+ * density).  x: B x d, locs/scales: K x d, pis: K (a simplex; validated by the host layer), K <= 64.
+ * Special values follow jax's logsumexp: a row whose every component is -inf (an infinite coordinate, or a finite one so far out
+ * that z * z leaves float32) is -inf, not NaN; a row with a NaN component is NaN; pis_k = 0 drops component k. */
 int d3p_gmm_log_prob(void* stream, const float* x_dev, uint32_t B, int32_t d, const float* locs_dev,
                      const float* scales_dev, const float* pis_dev, int32_t K, float* out_dev);
 
@@ -279,7 +281,8 @@ int d3p_perturb_apply(void* stream, const float* avg_dev, const float* noise_dev
                       float dp_scale, float c, const float* meta_dev, float obs_scale, float* out_dev);
 
 /* numpyro.optim.Adam step (svi.py:379-393; examples/logistic_regression.py:141).
- * step_dev: int32 device counter (incremented). */
+ * step_dev: int32 device counter (incremented).  Where g * g leaves float32 the second moment is +inf, as the reference's
+ * (1 - b2) * square(g), and the parameter keeps its value. */
 int d3p_adam_step(void* stream, float* params_dev, float* m_dev, float* v_dev, int32_t* step_dev,
                   const float* grads_dev, uint32_t P, float lr, float b1, float b2, float eps);
 

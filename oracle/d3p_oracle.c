@@ -700,7 +700,9 @@ D3P_API void d3po_adam(float* x, float* m, float* v, const float* g, int P, int 
     float c1 = 1.0f - powf(b1, (float)(i + 1)), c2 = 1.0f - powf(b2, (float)(i + 1));
     for (int j = 0; j < P; ++j) {
         m[j] = (1.0f - b1) * g[j] + b1 * m[j];
+        const float gg = g[j] * g[j];
         v[j] = (1.0f - b2) * g[j] * g[j] + b2 * v[j];
+        if (!isfinite(gg)) v[j] += (1.0f - b2) * gg;   /* the reference squares first: v = +inf where g * g overflows */
         float mhat = m[j] / c1, vhat = v[j] / c2;
         x[j] = x[j] - lr * mhat / (sqrtf(vhat) + eps);
     }
@@ -953,6 +955,7 @@ D3P_API void d3po_gmm_log_prob(const float* x, int B, int d, const float* locs, 
 #pragma omp parallel for schedule(static)
     for (int i = 0; i < B; ++i) {
         double best = -INFINITY;
+        int nan = 0;
         double* comp = (double*)malloc((size_t)K * sizeof(double));
         for (int k = 0; k < K; ++k) {
             double s = log((double)pis[k]);
@@ -961,11 +964,13 @@ D3P_API void d3po_gmm_log_prob(const float* x, int B, int d, const float* locs, 
                 s += -0.5 * z * z - log(sc) - (double)HALF_LOG_2PI;
             }
             comp[k] = s;
+            nan |= s != s;
             if (s > best) best = s;
         }
         double acc = 0.0;
         for (int k = 0; k < K; ++k) acc += exp(comp[k] - best);
-        out[i] = (float)(best + log(acc));
+        /* every component -inf: -inf as jax's logsumexp gives it, not -inf - -inf = NaN; a NaN component stays NaN */
+        out[i] = (best == -INFINITY && !nan) ? -INFINITY : (float)(best + log(acc));
         free(comp);
     }
 }

@@ -1,6 +1,7 @@
 // The draws x rows product tile of the regression kernels: t[s, r] = X[r] . w_s on a workgroup tile of 128 draws x 128 rows, used by
 //   k_predict_logreg (d3p_predict.hip)   k_loglik (d3p_loglik.hip)   k_moments (d3p_moments.hip)   k_predict_glm (d3p_predict_glm.hip)
 //   k_draw_sums (d3p_draw_sums.hip)   k_mean_rows (d3p_quantiles.hip)   k_predict_stats (d3p_rep_stats.hip)
+//   k_predict_discrepancy (d3p_discrepancy.hip)
 // which differ only in what they do with t.  One copy of the staging, the matrix-core loop and the accumulator scatter, and one
 // copy of the argument checks their C entries share (measurements: docs/experiments_glm_tile.md).
 //

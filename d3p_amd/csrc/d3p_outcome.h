@@ -1,7 +1,7 @@
 // The outcome rules of the regression families' observed site, one definition each, shared by the kernels that STORE the outcomes
 //   k_predict_logreg (d3p_predict.hip)   k_predict_vae_obs (d3p_predict.hip)   k_predict_glm (d3p_predict_glm.hip)
-// and the kernel that REDUCES them per draw without storing them
-//   k_predict_stats (d3p_rep_stats.hip)
+// and the kernels that REDUCE them per draw without storing them
+//   k_predict_stats (d3p_rep_stats.hip)   k_predict_discrepancy (d3p_discrepancy.hip)
 // The linear family's rule, normal_site_value, lives beside the tile (d3p_glm_tile.h).  Which numpyro / jax function each restates:
 // the file comments of d3p_predict.hip and d3p_predict_glm.hip, DESIGN.md section 4b.
 #pragma once

@@ -27,6 +27,10 @@ calibrated; a U shape: the predictive is too narrow; a hump: too wide).
 posterior predictive check on the training table: the statistic of the observed outcomes, its mean and central 90 % range over N_DRAWS
 data sets replicated from the trained guide, and the tail shares p_ge = P(T(y_rep) >= T(y)) and p_le.  The replicated data sets are
 reduced as they are drawn; they are never written.
+--discrepancy [N_DRAWS] (off by default; d3p_amd.discrepancy) adds, after training, the realized-discrepancy check of Gelman, Meng &
+Stern (1996) on the training table: per draw from the trained guide the Pearson chi-square of the observed outcomes and of that draw's
+own replicate, the share p_ge of draws whose replicate is at least as far from the mean as the data, the dispersion chi2_obs / rows
+(near 1 where --obs-scale is the noise of the data), and the Bayesian R^2 (both kinds), RMSE and bias per draw.
 """
 import argparse
 import os
@@ -128,6 +132,15 @@ def ppc_report(model, guide, params, X, y, num_draws, seed=7, statistics=("mean"
     return ["posterior predictive check ({} rows, {} replicated data sets):".format(res.n_rows, res.n_draws)] + res.lines()
 
 
+def discrepancy_report(model, guide, params, X, y, num_draws, seed=8):
+    """The lines of --discrepancy (d3p_amd.discrepancy): the paired p-values of the chi-square discrepancy, then mean and central 90 %
+    range over num_draws draws from the trained guide of chi2_obs, chi2_rep, dispersion, both R^2 kinds, RMSE and bias."""
+    from d3p_amd import discrepancy
+    import d3p_amd.random.debug as jax_random
+    res = discrepancy.discrepancy_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), guide, params)
+    return ["realized discrepancy check ({} rows, {} draws):".format(res.n_rows, res.n_draws)] + res.lines()
+
+
 def main(args):
     L.require_device()
     N, d = args.num_samples, args.dimensions
@@ -164,6 +177,8 @@ def main(args):
         print("\n".join(crps_report(model, svi, state, X_test, y_test, args.crps)))
     if getattr(args, "ppc", None) is not None:
         print("\n".join(ppc_report(model, svi.guide, svi.get_params(state), X, y, args.ppc)))
+    if getattr(args, "discrepancy", None) is not None:
+        print("\n".join(discrepancy_report(model, svi.guide, svi.get_params(state), X, y, args.discrepancy)))
     return first, last, err0, err
 
 
@@ -194,4 +209,7 @@ if __name__ == "__main__":
     parser.add_argument('--ppc', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, print the posterior predictive check of N_DRAWS (default 100) replicated data sets: per '
                              'statistic the observed value, the replicated mean and 90 %% range, p_ge and p_le')
+    parser.add_argument('--discrepancy', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, print the chi-square realized-discrepancy check of N_DRAWS (default 100) draws: p_ge, p_le, '
+                             'the dispersion, the Bayesian R^2, RMSE and bias per draw')
     main(parser.parse_args())

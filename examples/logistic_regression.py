@@ -16,6 +16,10 @@ median norm as the suggested threshold (Abadi et al. 2016).  They are computed f
 posterior predictive check on the training table: the statistic of the observed outcomes, its mean and central 90 % range over N_DRAWS
 data sets replicated from the trained guide, and the tail shares p_ge = P(T(y_rep) >= T(y)) and p_le.  The replicated data sets are
 reduced as they are drawn; they are never written.
+--discrepancy [N_DRAWS] (off by default; d3p_amd.discrepancy) adds, after training, the realized-discrepancy check of Gelman, Meng &
+Stern (1996) on the training table: per draw from the trained guide the Pearson chi-square of the observed outcomes and of that draw's
+own replicate, the share p_ge of draws whose replicate is at least as far from the mean as the data, the dispersion chi2_obs / rows
+(near 1 for labels the model explains), and the Bayesian R^2 (both kinds), RMSE and bias per draw.
 """
 import argparse
 import os
@@ -69,6 +73,15 @@ def ppc_report(model, guide, params, X, y, num_draws, seed=7, statistics=("mean"
     import d3p_amd.random.debug as jax_random
     res = ppc.posterior_predictive_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), guide, params, statistics=statistics)
     return ["posterior predictive check ({} rows, {} replicated data sets):".format(res.n_rows, res.n_draws)] + res.lines()
+
+
+def discrepancy_report(model, guide, params, X, y, num_draws, seed=8):
+    """The lines of --discrepancy (d3p_amd.discrepancy): the paired p-values of the chi-square discrepancy, then mean and central 90 %
+    range over num_draws draws from the trained guide of chi2_obs, chi2_rep, dispersion, both R^2 kinds, RMSE and bias."""
+    from d3p_amd import discrepancy
+    import d3p_amd.random.debug as jax_random
+    res = discrepancy.discrepancy_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), guide, params)
+    return ["realized discrepancy check ({} rows, {} draws):".format(res.n_rows, res.n_draws)] + res.lines()
 
 
 def main(args):
@@ -134,6 +147,8 @@ def main(args):
         print("\n".join(clipping_profile_report(svi, svi_state, *train)))
     if getattr(args, "ppc", None) is not None:   # both guides
         print("\n".join(ppc_report(model, guide, svi.get_params(svi_state), *train, args.ppc)))
+    if getattr(args, "discrepancy", None) is not None:   # both guides
+        print("\n".join(discrepancy_report(model, guide, svi.get_params(svi_state), *train, args.discrepancy)))
     return accs, train_losses
 
 
@@ -156,4 +171,7 @@ if __name__ == "__main__":
     parser.add_argument('--ppc', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, print the posterior predictive check of N_DRAWS (default 100) replicated data sets: per '
                              'statistic the observed value, the replicated mean and 90 %% range, p_ge and p_le')
+    parser.add_argument('--discrepancy', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, print the chi-square realized-discrepancy check of N_DRAWS (default 100) draws: p_ge, p_le, '
+                             'the dispersion, the Bayesian R^2, RMSE and bias per draw')
     main(parser.parse_args())

@@ -41,6 +41,10 @@ N_DRAWS data sets replicated from the trained guide, and the tail shares p_ge = 
 sets are reduced as they are drawn; they are never written.
 --zero-inflate SHARE (default 0: the data are unchanged) sets that share of the training counts to 0 before fitting, so that --ppc has
 something to find: the Poisson family cannot reproduce the excess zeros (p_ge of `zeros` and of `dispersion` go to 0).
+--discrepancy [N_DRAWS] (off by default; d3p_amd.discrepancy) adds, after training, the realized-discrepancy check of Gelman, Meng &
+Stern (1996): per draw from the trained guide the Pearson chi-square of the observed counts and of that draw's own replicate, the share
+p_ge of draws whose replicate is at least as far from the mean as the data, the dispersion chi2_obs / rows (1 for a Poisson sample),
+and the Bayesian R^2 (both kinds), RMSE and bias per draw.  With --zero-inflate p_ge goes to 0 and the dispersion well above 1.
 """
 import argparse
 import os
@@ -198,6 +202,15 @@ def ppc_report(model, svi, state, X, y, num_draws, seed=7, statistics=("mean", "
     return [head] + res.lines()
 
 
+def discrepancy_report(model, svi, state, X, y, num_draws, seed=8):
+    """The lines of --discrepancy (d3p_amd.discrepancy): the paired p-values of the chi-square discrepancy, then mean and central 90 %
+    range over num_draws draws from the trained guide of chi2_obs, chi2_rep, dispersion, both R^2 kinds, RMSE and bias."""
+    from d3p_amd import discrepancy
+    import d3p_amd.random.debug as jax_random
+    res = discrepancy.discrepancy_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), svi.guide, svi.get_params(state))
+    return ["realized discrepancy check ({} rows, {} draws):".format(res.n_rows, res.n_draws)] + res.lines()
+
+
 def zero_inflate(y, share, seed=99):
     """y with `share` of its entries set to 0, chosen by a generator of its own (--zero-inflate)."""
     g = torch.Generator(device="cuda").manual_seed(seed)
@@ -274,6 +287,8 @@ def main(args):
         print("\n".join(compare_models_report(fits, X, y, args.compare_models)))
     if getattr(args, "ppc", None) is not None:
         print("\n".join(ppc_report(model, svi, state, X, y, args.ppc)))
+    if getattr(args, "discrepancy", None) is not None:
+        print("\n".join(discrepancy_report(model, svi, state, X, y, args.discrepancy)))
     return first, last, err0, err
 
 
@@ -314,4 +329,7 @@ if __name__ == "__main__":
                              'statistic the observed value, the replicated mean and 90 %% range, p_ge and p_le')
     parser.add_argument('--zero-inflate', default=0.0, type=float, metavar='SHARE',
                         help='set this share of the training counts to 0 before fitting (default 0: unchanged), for --ppc to find')
+    parser.add_argument('--discrepancy', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, print the chi-square realized-discrepancy check of N_DRAWS (default 100) draws: p_ge, p_le, '
+                             'the dispersion, the Bayesian R^2, RMSE and bias per draw')
     main(parser.parse_args())

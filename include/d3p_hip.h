@@ -1336,6 +1336,36 @@ int d3p_predict_stats(void* stream, const d3p_logreg_model* model, const float* 
                       int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n, const uint32_t* obs_keys_dev, double shift,
                       double* out_dev, void* workspace_dev, size_t workspace_bytes);
 
+/* Realized-discrepancy sums of a fitted regression model over its ROWS (d3p_amd/discrepancy.py: the chi-square check of Gelman, Meng &
+ * Stern 1996 and the Bayesian R^2; d3p_discrepancy.hip); added symbols, ABI 9 and d3p_logreg_model unchanged.  The one
+ * reduction over the rows that needs the observed y, the conditional mean and the replicated outcome together.
+ * For draw s and row r, with t the product tile's value (+ the intercept) as in every entry above:
+ *   mu = the float32 mean d3p_predict_mean_rows stores for the same arguments (logistic: its two-branch sigmoid; linear: t; Poisson: expf(t))
+ *   v  = the outcome d3p_predict_glm / d3p_predict_logreg store for the same arguments, obs keys included (as in d3p_predict_stats)
+ * and in float64, every operation rounded once (no fused multiply-add), with the host-given float64 `shift` and sigma = lik_sigma:
+ *   M = fl64(mu)     V = fl64(sigma) fl64(sigma) (D3P_FAMILY_LINREG) | M (D3P_FAMILY_POISSON) | M (1.0 - M) (D3P_FAMILY_LOGREG)
+ *   q(x) = (e == 0.0) ? 0.0 : (e e) / V,  e = fl64(x) - M          m = M - shift          ey = fl64(y_r) - M
+ * out_dev of 6 n float64:
+ *   out_dev[0 n + s] = sum_r q(y_r)        the realized discrepancy D(y, theta_s)
+ *   out_dev[1 n + s] = sum_r q(v[s, r])    the replicated discrepancy D(y_rep_s, theta_s)
+ *   out_dev[2 n + s] = sum_r m             out_dev[3 n + s] = sum_r fl64(m m)
+ *   out_dev[4 n + s] = sum_r ey            out_dev[5 n + s] = sum_r fl64(ey ey)
+ * ONE convention: a row that is matched exactly (e == 0) contributes nothing, even at V == 0.  Otherwise nothing is clamped: e != 0 at
+ * V == 0 gives +inf, a NaN mu gives NaN, and the Poisson family's markers (-1, 2147483647) are values like any other.
+ * Summation order of all six: d3p_rep_stats' exactly (tiles, per and strips as above; four quarter accumulators of 32 consecutive rows per
+ * tile, tiles and rows ascending from 0.0; strip partial = ((q0 + q1) + q2) + q3; strips merged ascending by a second small launch; no
+ * floating-point atomics).  The bits are a function of the arguments alone: a draw's result does not depend on the other draws, on
+ * latent_ld or on n.
+ * Workspace (the contract of "Workspaces"): d3p_predict_discrepancy_workspace(rows, n) = strips x 6 x n float64 (0 for rows == 0 or
+ * rows >= 2^32); its prior content is never read and nothing is written past it.
+ * Before any launch, d3p_predict_stats' refusals with y_dev among the pointers (null or non-device: D3P_E_INVALID_ARG), y_dev aligned
+ * to 4 bytes, rows == 0, an out not aligned to 8 bytes, a non-finite shift and a short, null, misaligned or non-device workspace:
+ * D3P_E_INVALID_ARG; D3P_FAMILY_GAUSS_MEAN and D3P_GUIDE_EXP_SITES: D3P_E_UNSUPPORTED. */
+size_t d3p_predict_discrepancy_workspace(uint64_t rows, uint32_t n);
+int d3p_predict_discrepancy(void* stream, const d3p_logreg_model* model, const float* X_dev, const float* y_dev, uint64_t rows, int32_t d,
+                            const float* latent_dev, int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n,
+                            const uint32_t* obs_keys_dev, double shift, double* out_dev, void* workspace_dev, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

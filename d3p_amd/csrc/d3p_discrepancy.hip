@@ -2,8 +2,8 @@
 // Stern 1996 and the Bayesian R^2 of Gelman, Goodrich, Gabry & Vehtari 2019).  The one reduction over the rows that
 // needs the observed y, the conditional mean mu and the replicated outcome v together.  For draw s and row r, t = the product tile's
 // value (+ the intercept), as for every user of the tile:
-//   mu = the float32 mean d3p_predict_mean_rows stores (k_mean_rows' link, restated below: disc_mean)
-//   v  = the outcome d3p_predict_glm / d3p_predict_logreg store: the same rule (d3p_outcome.h, normal_site_value), obs keys, rows and r
+//   mu = the float32 mean d3p_predict_mean_rows stores: k_mean_rows' link, glm_mean<FAMILY> (d3p_glm_tile.h)
+//   v  = the outcome d3p_predict_glm / d3p_predict_logreg store: the same rule (glm_outcome, d3p_outcome.h), obs keys, rows and r
 // and in float64, every operation rounded once (the file is compiled with fp contract off):
 //   M = fl64(mu)     V = fl64(sigma) fl64(sigma) (linear) | M (Poisson) | M (1.0 - M) (logistic)
 //   q(x) = (e == 0.0) ? 0.0 : (e e) / V,  e = fl64(x) - M          m = M - shift          ey = fl64(y_r) - M
@@ -12,10 +12,11 @@
 // ONE convention: a row that is matched exactly contributes nothing, even at V == 0; otherwise nothing is clamped (e != 0 at V == 0:
 // +inf; a NaN mu: NaN; Poisson's markers -1 and 2147483647 are values like any other).
 //
-// Summation order of all six: d3p_rep_stats' (d3p_rep_stats.hip), which is d3p_loglik_draw_sums' (DESIGN.md section 4j):
+// Summation order of all six: d3p_rep_stats' (d3p_rep_stats.hip), which is d3p_loglik_draw_sums' (DESIGN.md section 4j), by the same
+// definitions (d3p_row_sums.h: row_strips, strip_tiles, quarter_sum, k_strip_merge):
 //   tiles = ceil(rows / 128);  per = ceil(tiles / 512);  strips = ceil(tiles / per)
 // four quarter accumulators of 32 consecutive rows per tile, tiles and rows ascending from 0.0; strip partial = ((q0 + q1) + q2) + q3
-// into the workspace as float64 [strip][6][n]; k_discrepancy_merge adds the strips ascending from strip 0's.  No floating-point atomics.
+// into the workspace as float64 [strip][6][n]; k_strip_merge<6, -1, -1> adds them ascending from strip 0's.  No floating-point atomics.
 //
 // k_predict_discrepancy<FAMILY> has k_predict_stats' shape: grid (row strips, tiles of 128 draws), tile_product per row tile,
 // tile_scatter per draw half under `unroll 1`, lane = draw l % 32 and row half l / 32 walking 32 rows on 32 distinct LDS banks, the
@@ -27,36 +28,13 @@
 #include "d3p_glm_tile.h"
 #include "d3p_host.h"
 #include "d3p_outcome.h"
+#include "d3p_row_sums.h"
 
 #pragma clang fp contract(off)
 
 namespace d3p {
 
-#define D3P_DISC_MAX_STRIPS 512   // d3p_loglik_draw_sums' strip function
 #define D3P_DISC_SUMS 6
-
-static inline void disc_strips(uint64_t rows, uint32_t* tiles, uint32_t* per, uint32_t* strips)
-{
-    *tiles = cdiv(rows, D3P_TILE_N);
-    *per = *tiles ? cdiv(*tiles, D3P_DISC_MAX_STRIPS) : 0;
-    *strips = *tiles ? cdiv(*tiles, *per) : 0;
-}
-
-// k_mean_rows' link (d3p_quantiles.hip), text for text: mu = sigmoid(t) | t | exp(t)
-template <int FAMILY>
-__device__ __forceinline__ float disc_mean(float t)
-{
-    float mu;
-    if (FAMILY == D3P_FAMILY_LOGREG) {   // k_moments' p = sigmoid(t): one e = exp(-|t|), the larger value 1 / (1 + e), the smaller e / (1 + e)
-        const float e = expf(-fabsf(t));
-        const float den = 1.0f + e;
-        const float big = 1.0f / den, small = e / den;
-        mu = t >= 0.0f ? big : small;    // (a NaN t: both NaN)
-    } else {
-        mu = FAMILY == D3P_FAMILY_POISSON ? expf(t) : t;
-    }
-    return mu;
-}
 
 // q(x) = (e == 0.0) ? 0.0 : (e e) / V: an exactly matched row contributes nothing, even at V == 0; nothing else is clamped
 __device__ __forceinline__ double disc_q(double e, double V) { return e == 0.0 ? 0.0 : (e * e) / V; }
@@ -77,30 +55,6 @@ __device__ __forceinline__ void disc_put(double* red, int q, int dl, const DiscA
     red[(3 * 4 + q) * D3P_TILE_M + dl] = a.m2;
     red[(4 * 4 + q) * D3P_TILE_M + dl] = a.e1;
     red[(5 * 4 + q) * D3P_TILE_M + dl] = a.e2;
-}
-
-// out[k n + s] = the strips' partials of draw s in ascending strip order, starting from strip 0's
-__global__ void __launch_bounds__(256) k_discrepancy_merge(const double* part, uint32_t strips, uint32_t n, double* out)
-{
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s >= n) return;
-    const double* p = part + s;
-    double a0 = p[0], a1 = p[n], a2 = p[2 * (size_t)n], a3 = p[3 * (size_t)n], a4 = p[4 * (size_t)n], a5 = p[5 * (size_t)n];
-    for (uint32_t k = 1; k < strips; ++k) {
-        p += (size_t)D3P_DISC_SUMS * n;
-        a0 = a0 + p[0];
-        a1 = a1 + p[n];
-        a2 = a2 + p[2 * (size_t)n];
-        a3 = a3 + p[3 * (size_t)n];
-        a4 = a4 + p[4 * (size_t)n];
-        a5 = a5 + p[5 * (size_t)n];
-    }
-    out[s] = a0;
-    out[(size_t)n + s] = a1;
-    out[2 * (size_t)n + s] = a2;
-    out[3 * (size_t)n + s] = a3;
-    out[4 * (size_t)n + s] = a4;
-    out[5 * (size_t)n + s] = a5;
 }
 
 struct DiscrepancyArgs {
@@ -133,18 +87,9 @@ __global__ void __launch_bounds__(256, 1) k_predict_discrepancy(DiscrepancyArgs 
     const int i = lane & 31, h = lane >> 5;            // the lane's draw within a half of the wave's draws; its half of the wave's rows
     const int col = wn * 64 + h * 32;                  // first of the lane's 32 rows within a tile: quarter q = 2 wn + h
     const uint32_t s0 = blockIdx.y * D3P_TILE_M;
-    const uint32_t t_lo = blockIdx.x * g.per;
-    const uint32_t t_hi = t_lo + g.per < g.tiles ? t_lo + g.per : g.tiles;
-    if (tid < D3P_TILE_M) {   // (read after the barriers of the first product, which runs at least once: d >= 1, a strip has a tile)
-        const uint32_t s = s0 + tid;
-        uint32_t o0 = 0u, o1 = 0u, f0 = 0u, f1 = 0u;
-        if (s < g.n) {
-            o0 = g.obs_keys[2 * (size_t)s];
-            o1 = g.obs_keys[2 * (size_t)s + 1];
-            if (FAMILY == D3P_FAMILY_POISSON) threefry2x32(o0, o1, 0u, 0u, f0, f1);   // jax.random.fold_in(obs_key, 0)
-        }
-        keys[tid][0] = o0; keys[tid][1] = o1; keys[tid][2] = f0; keys[tid][3] = f1;
-    }
+    uint32_t t_lo, t_hi;
+    strip_tiles(g.per, g.tiles, t_lo, t_hi);
+    stage_obs_keys<FAMILY>(keys, g.obs_keys, s0, g.n);
     DiscAcc a0, a1;
     disc_init(a0);
     disc_init(a1);
@@ -157,8 +102,7 @@ __global__ void __launch_bounds__(256, 1) k_predict_discrepancy(DiscrepancyArgs 
         tile_f16v acc[2][2];
         tile_product(smem, g, r0, s0, acc);
         float* L = tile_block(smem);
-        const uint64_t left = g.rows - r0;   // >= 1
-        const int jn = left <= (uint64_t)col ? 0 : (left - col >= 32 ? 32 : (int)(left - col));   // the lane's live rows in this tile
+        const int jn = quarter_live_rows(g.rows, r0, col);
 #pragma unroll 1
         for (int mb = 0; mb < 2; ++mb) {
             tile_scatter(L, mb == 0 ? acc[0][0] : acc[1][0], mb == 0 ? acc[0][1] : acc[1][1]);   // (selected by hand: the loop is not unrolled)
@@ -175,7 +119,7 @@ __global__ void __launch_bounds__(256, 1) k_predict_discrepancy(DiscrepancyArgs 
                 for (int j = 0; j < jn; ++j) {
                     float tv = p[j];
                     if (g.b_col >= 0) tv = tv + b;
-                    const double M = (double)disc_mean<FAMILY>(tv);
+                    const double M = (double)glm_mean<FAMILY>(tv);
                     const double V = FAMILY == D3P_FAMILY_LINREG ? g.var : (FAMILY == D3P_FAMILY_POISSON ? M : M * (1.0 - M));
                     const double m = M - g.shift;
                     const double ey = (double)ys[col + j] - M;
@@ -184,14 +128,7 @@ __global__ void __launch_bounds__(256, 1) k_predict_discrepancy(DiscrepancyArgs 
                     a.m2 = a.m2 + m * m;
                     a.e1 = a.e1 + ey;
                     a.e2 = a.e2 + ey * ey;
-                    const uint64_t r = rb + j;
-                    double v;
-                    if (FAMILY == D3P_FAMILY_LINREG)
-                        v = (double)normal_site_value(tv, bits_to_normal(tf_iota_word(o0, o1, g.rows, r)), g.sigma);
-                    else if (FAMILY == D3P_FAMILY_POISSON)
-                        v = (double)poisson_draw(tv, o0, o1, keys[sl][2], keys[sl][3], (uint32_t)g.rows, (uint32_t)r);
-                    else
-                        v = (double)bernoulli_draw(tf_iota_word(o0, o1, g.rows, r), sigmoid_probs(tv));
+                    const double v = (double)glm_outcome<FAMILY>(tv, o0, o1, keys[sl][2], keys[sl][3], g.rows, rb + j, g.sigma);
                     a.d_rep = a.d_rep + disc_q(v - M, V);
                 }
                 if (mb == 0) a0 = a; else a1 = a;
@@ -206,10 +143,7 @@ __global__ void __launch_bounds__(256, 1) k_predict_discrepancy(DiscrepancyArgs 
     if (tid < D3P_TILE_M && s0 + tid < g.n) {   // the four quarters of draw tid in the order q = 0, 1, 2, 3 -> part[strip][sum][n]
         double* p = g.part + (size_t)blockIdx.x * D3P_DISC_SUMS * g.n + s0 + tid;
 #pragma unroll
-        for (int k = 0; k < D3P_DISC_SUMS; ++k) {
-            const double* r = red + k * 4 * D3P_TILE_M + tid;
-            p[k * (size_t)g.n] = ((r[0] + r[D3P_TILE_M]) + r[2 * D3P_TILE_M]) + r[3 * D3P_TILE_M];
-        }
+        for (int k = 0; k < D3P_DISC_SUMS; ++k) p[k * (size_t)g.n] = quarter_sum(red + k * 4 * D3P_TILE_M + tid, D3P_TILE_M);
     }
 }
 
@@ -223,7 +157,7 @@ size_t d3p_predict_discrepancy_workspace(uint64_t rows, uint32_t n)
 {
     if (rows > 0xFFFFFFFFull) return 0;
     uint32_t tiles, per, strips;
-    disc_strips(rows, &tiles, &per, &strips);
+    row_strips(rows, D3P_TILE_N, D3P_ROW_SUMS_MAX_STRIPS, &tiles, &per, &strips);
     return (size_t)strips * D3P_DISC_SUMS * n * sizeof(double);
 }
 
@@ -247,13 +181,8 @@ int d3p_predict_discrepancy(void* stream, const d3p_logreg_model* model, const f
     if (!std::isfinite(shift)) return fail(D3P_E_INVALID_ARG, "%s: the shift must be finite", what);
     DiscrepancyArgs g;
     uint32_t strips;
-    disc_strips(rows, &g.tiles, &g.per, &strips);
-    const size_t need = (size_t)strips * D3P_DISC_SUMS * n * sizeof(double);
-    if (!workspace_dev || (uintptr_t)workspace_dev % sizeof(double))
-        return fail(D3P_E_INVALID_ARG, "%s: the workspace must be aligned to 8 bytes and not null", what);
-    if (workspace_bytes < need)
-        return fail(D3P_E_INVALID_ARG, "%s: workspace of %zu bytes, %zu needed (d3p_predict_discrepancy_workspace)", what, workspace_bytes, need);
-    if (!is_device_ptr(workspace_dev)) return fail(D3P_E_INVALID_ARG, "%s: the workspace must be device memory", what);
+    row_strips(rows, D3P_TILE_N, D3P_ROW_SUMS_MAX_STRIPS, &g.tiles, &g.per, &strips);
+    if (int rc = row_workspace_check(what, "d3p_predict_discrepancy_workspace", workspace_dev, workspace_bytes, strips, D3P_DISC_SUMS, n)) return rc;
     g.X = X_dev; g.y = y_dev; g.rows = rows; g.d = d; g.w_off = w_off; g.b_col = b_col; g.lat = latent_dev; g.ld = latent_ld; g.n = n;
     g.sigma = m->family == D3P_FAMILY_LINREG ? m->lik_sigma : 0.f;
     g.var = (double)g.sigma * (double)g.sigma;
@@ -264,8 +193,7 @@ int d3p_predict_discrepancy(void* stream, const d3p_logreg_model* model, const f
     else if (m->family == D3P_FAMILY_POISSON) hipLaunchKernelGGL((k_predict_discrepancy<D3P_FAMILY_POISSON>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((k_predict_discrepancy<D3P_FAMILY_LOGREG>), grid, dim3(256), 0, s, g);
     if (int rc = check_launch(what)) return rc;
-    hipLaunchKernelGGL(k_discrepancy_merge, dim3(cdiv(n, 256)), dim3(256), 0, s, g.part, strips, n, out_dev);
-    return check_launch(what);
+    return strip_merge<D3P_DISC_SUMS, -1, -1>(what, s, g.part, strips, n, out_dev);
 }
 
 }  // extern "C"

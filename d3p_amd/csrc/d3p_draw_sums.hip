@@ -5,7 +5,8 @@
 // intercept add, the same label constant and the same loglik_value<FAMILY> (d3p_glm_tile.h).  Every other reduction over the tile
 // (lppd, the moments, WAIC) runs over the draws, once per row; this one runs over the rows, once per draw.
 //
-// Grid: x = row strips, y = tiles of 128 draws.  The table's row tiles (128 rows) are cut into strips of `per` consecutive tiles,
+// Grid: x = row strips, y = tiles of 128 draws.  The table's row tiles (128 rows) are cut into strips of `per` consecutive tiles by
+// row_strips (d3p_row_sums.h, the definitions every per-draw reduction over rows shares),
 //   tiles = ceil(rows / 128);  per = ceil(tiles / 512);  strips = ceil(tiles / per)  (<= 512)
 // a function of rows alone -- not of the device, its CU count or n -- so the summation order below is a function of the arguments
 // only.  A workgroup walks the row tiles of its strip in ascending order; X is read once per draw tile, as in the rows form.
@@ -21,16 +22,15 @@
 //
 // Summation order of out[s], fixed:  a tile's 128 rows fall into four quarters q = 0..3 of 32 consecutive rows.  Quarter sum (strip,
 // q) = the rows of quarter q of every tile of the strip, tiles ascending, rows ascending within a tile, added one by one from 0.0.
-// Strip partial = ((q0 + q1) + q2) + q3, written to the workspace as float64 [strip][n].  A second launch (k_draw_sums_merge, one
+// Strip partial = ((q0 + q1) + q2) + q3, written to the workspace as float64 [strip][n].  A second launch (k_strip_merge<1, -1, -1>, one
 // thread per draw) adds the strips' partials in ascending strip order, starting from strip 0's.  No floating-point atomics, no
 // arrival-order dependence: the output bits are a function of the arguments only.
 #include "d3p_device.h"
 #include "d3p_glm_tile.h"
 #include "d3p_host.h"
+#include "d3p_row_sums.h"
 
 namespace d3p {
-
-#define D3P_DRAW_SUMS_MAX_STRIPS 512
 
 struct DrawSumsArgs {
     const float* X;
@@ -45,14 +45,6 @@ struct DrawSumsArgs {
     double* part;           // [strips][n]
 };
 
-// the strip function (file comment): rows alone decide
-static inline void draw_sums_strips(uint64_t rows, uint32_t* tiles, uint32_t* per, uint32_t* strips)
-{
-    *tiles = cdiv(rows, D3P_TILE_N);
-    *per = *tiles ? cdiv(*tiles, D3P_DRAW_SUMS_MAX_STRIPS) : 0;
-    *strips = *tiles ? cdiv(*tiles, *per) : 0;
-}
-
 // Registers: the X addresses of the staging loads live across the row-tile loop beside the 64 accumulators, as in k_loglik's lppd
 // form, which spills at two waves per SIMD: one wave per SIMD, no scratch (docs/experiments_guide_diag.md).
 template <int FAMILY>
@@ -66,8 +58,8 @@ __global__ void __launch_bounds__(256, 1) k_draw_sums(DrawSumsArgs g)
     const int i = lane & 31, h = lane >> 5;            // the lane's draw within a half of the wave's draws; its half of the wave's rows
     const int col = wn * 64 + h * 32;                  // first of the lane's 32 rows within a tile: quarter q = 2 wn + h
     const uint32_t s0 = blockIdx.y * D3P_TILE_M;
-    const uint32_t t_lo = blockIdx.x * g.per;
-    const uint32_t t_hi = t_lo + g.per < g.tiles ? t_lo + g.per : g.tiles;
+    uint32_t t_lo, t_hi;
+    strip_tiles(g.per, g.tiles, t_lo, t_hi);
     uint32_t s[2];
     float b[2];
     double sum[2] = {0.0, 0.0};
@@ -87,8 +79,7 @@ __global__ void __launch_bounds__(256, 1) k_draw_sums(DrawSumsArgs g)
         tile_f16v acc[2][2];
         tile_product(smem, g, r0, s0, acc);
         float* L = tile_block(smem);
-        const uint64_t left = g.rows - r0;   // >= 1
-        const int jn = left <= (uint64_t)col ? 0 : (left - col >= 32 ? 32 : (int)(left - col));   // the lane's live rows in this tile
+        const int jn = quarter_live_rows(g.rows, r0, col);
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
             tile_scatter(L, acc[mb][0], acc[mb][1]);
@@ -109,19 +100,7 @@ __global__ void __launch_bounds__(256, 1) k_draw_sums(DrawSumsArgs g)
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) red[(wn * 2 + h) * D3P_TILE_M + wm * 64 + mb * 32 + i] = sum[mb];
     __syncthreads();
-    if (tid < D3P_TILE_M && s0 + tid < g.n)
-        g.part[(size_t)blockIdx.x * g.n + s0 + tid] =
-            ((red[tid] + red[D3P_TILE_M + tid]) + red[2 * D3P_TILE_M + tid]) + red[3 * D3P_TILE_M + tid];
-}
-
-// out[s] = the strips' partials of draw s in ascending strip order
-__global__ void __launch_bounds__(256) k_draw_sums_merge(const double* part, uint32_t strips, uint32_t n, double* out)
-{
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s >= n) return;
-    double a = part[s];
-    for (uint32_t k = 1; k < strips; ++k) a += part[(size_t)k * n + s];
-    out[s] = a;
+    if (tid < D3P_TILE_M && s0 + tid < g.n) g.part[(size_t)blockIdx.x * g.n + s0 + tid] = quarter_sum(red + tid, D3P_TILE_M);
 }
 
 }  // namespace d3p
@@ -133,7 +112,7 @@ extern "C" {
 size_t d3p_loglik_draw_sums_workspace(uint64_t rows, uint32_t n)
 {
     uint32_t tiles, per, strips;
-    draw_sums_strips(rows, &tiles, &per, &strips);
+    row_strips(rows, D3P_TILE_N, D3P_ROW_SUMS_MAX_STRIPS, &tiles, &per, &strips);
     return (size_t)strips * n * sizeof(double);
 }
 
@@ -157,12 +136,8 @@ int d3p_loglik_draw_sums(void* stream, const d3p_logreg_model* model, const floa
     }
     DrawSumsArgs g;
     uint32_t strips;
-    draw_sums_strips(rows, &g.tiles, &g.per, &strips);
-    const size_t need = (size_t)strips * n * sizeof(double);
-    if (!workspace_dev || (uintptr_t)workspace_dev % sizeof(double) || !is_device_ptr(workspace_dev))
-        return fail(D3P_E_INVALID_ARG, "%s: the workspace must be device memory aligned to 8 bytes", what);
-    if (workspace_bytes < need)
-        return fail(D3P_E_INVALID_ARG, "%s: workspace of %zu bytes, %zu needed (d3p_loglik_draw_sums_workspace)", what, workspace_bytes, need);
+    row_strips(rows, D3P_TILE_N, D3P_ROW_SUMS_MAX_STRIPS, &g.tiles, &g.per, &strips);
+    if (int rc = row_workspace_check(what, "d3p_loglik_draw_sums_workspace", workspace_dev, workspace_bytes, strips, 1, n)) return rc;
     g.X = X_dev; g.y = y_dev; g.rows = rows; g.d = m->d; g.w_off = w_off; g.b_col = b_col; g.lat = latent_dev; g.ld = latent_ld; g.n = n;
     g.part = static_cast<double*>(workspace_dev);
     // as the rows form's arguments (d3p_loglik.hip)
@@ -174,8 +149,7 @@ int d3p_loglik_draw_sums(void* stream, const d3p_logreg_model* model, const floa
     else if (m->family == D3P_FAMILY_POISSON) hipLaunchKernelGGL((k_draw_sums<D3P_FAMILY_POISSON>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((k_draw_sums<D3P_FAMILY_LOGREG>), grid, dim3(256), 0, s, g);
     if (int rc = check_launch(what)) return rc;
-    hipLaunchKernelGGL(k_draw_sums_merge, dim3(cdiv(n, 256)), dim3(256), 0, s, g.part, strips, n, out_draws_dev);
-    return check_launch(what);
+    return strip_merge<1, -1, -1>(what, s, g.part, strips, n, out_draws_dev);
 }
 
 }  // extern "C"

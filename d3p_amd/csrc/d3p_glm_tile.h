@@ -128,6 +128,31 @@ __device__ __forceinline__ float loglik_value(float t, float y, float nh, float 
     return -(lin + log1pf(expf(-fabsf(t))));
 }
 
+// ---- the conditional mean E[y | t] of the forms that take it: k_moments (d3p_moments.hip), k_mean_rows (d3p_quantiles.hip) and
+// k_predict_discrepancy (d3p_discrepancy.hip), whose float32 mu are bit for bit the same (tests/test_gpu_glm_tile.py) ----------------
+// p = sigmoid(t) and q = sigmoid(-t) from ONE e = exp(-|t|): the larger is 1 / (1 + e), the smaller e / (1 + e); neither is 1 - the
+// other.  A NaN t gives both NaN.  (No a * b + c shape: the including file's fp contract setting cannot change a bit.)
+__device__ __forceinline__ void sigmoid_pair(float t, float& p, float& q)
+{
+    const float e = expf(-fabsf(t));
+    const float den = 1.0f + e;
+    const float big = 1.0f / den, small = e / den;
+    p = t >= 0.0f ? big : small;
+    q = t >= 0.0f ? small : big;
+}
+
+// mu = sigmoid(t) | t | exp(t)   (logistic | linear | Poisson); no clamps: exp(t) = inf stays inf
+template <int FAMILY>
+__device__ __forceinline__ float glm_mean(float t)
+{
+    if (FAMILY == D3P_FAMILY_LOGREG) {
+        float p, q;
+        sigmoid_pair(t, p, q);
+        return p;
+    }
+    return FAMILY == D3P_FAMILY_POISSON ? expf(t) : t;
+}
+
 // ---- host: the argument checks of the C entries that take a model and a latent buffer (d3p_loglik_rows / _lppd, d3p_predict_moments,
 // d3p_predict_glm), in the order those entries have always made them.  ptrs: X, the latent buffer and the entry's other buffers;
 // null_names / dev_names: how the entry's two messages list them.  *launch = false with D3P_OK: rows == 0, nothing to do. -------------

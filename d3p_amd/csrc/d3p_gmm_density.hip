@@ -45,18 +45,20 @@
 // the float32 value the rows form writes: the same instantiated text up to the line that stores it.  Grid: the table's row tiles are
 // cut into strips of `per` consecutive tiles,
 //   tiles = ceil(rows / 64);  per = ceil(tiles / 2048);  strips = ceil(tiles / per)  (<= 2048)
-// a function of rows alone, as d3p_draw_sums.hip's.  A workgroup walks the tiles of its strip in ascending order and, per tile, all n
-// draws exactly as the other forms do (the same W, the same staging).  Summation order of out[s], fixed:
+// a function of rows alone: d3p_draw_sums.hip's row_strips (d3p_row_sums.h) at this file's tile and cap.  A workgroup walks the tiles
+// of its strip in ascending order and, per tile, all n draws exactly as the other forms do (the same W, the same staging).
+// Summation order of out[s], fixed:
 //   tile sum   = the 64 lanes' (double)ll in the xor butterfly v = v + v[lane ^ off], off = 1, 2, 4, 8, 16, 32, i.e. the balanced binary
 //                tree over the rows of the tile in index order; a row past the end is exactly 0.0 (its value, of a staged zero row, is
 //                computed and dropped);
 //   strip sum  = the tile sums of the strip added one by one in ascending tile order, from 0.0, kept at ws[strip][s] by the lane
 //                that owns (strip, s) -- lane 0 of wave s % W of workgroup `strip`, always the same -- with a plain load, add and store;
-//   out[s]     = the strip sums added in ascending strip order, starting from strip 0's (k_gmm_draw_sums_merge, a second launch).
+//   out[s]     = the strip sums added in ascending strip order, starting from strip 0's (k_strip_merge<1, -1, -1>, a second launch).
 // No floating-point atomics, no arrival order; a draw's sum does not depend on the other draws of the launch.  Nothing is clamped:
 // a draw with ll = -inf in some row sums to -inf, a NaN row of obs makes every draw NaN, a NaN in a draw's latents that draw only.
 #include "d3p_colreduce.h"
 #include "d3p_device.h"
+#include "d3p_row_sums.h"
 #include "d3p_shifted_sums.h"
 
 namespace d3p {
@@ -100,8 +102,8 @@ __global__ void __launch_bounds__(256) k_gmm_density(GmmDensityArgs g)
     float* cj = mine + 2 * kd;                      // [j] = C_j
     // REDUCE == 3 walks the row tiles of its strip in ascending order; every other form owns the one tile of its workgroup (the loop's
     // condition is false at compile time and its body, left at its indentation, is the text those forms always had)
-    const uint32_t tile_lo = REDUCE == 3 ? blockIdx.x * g.per : blockIdx.x;
-    const uint32_t tile_hi = REDUCE == 3 ? (tile_lo + g.per < g.tiles ? tile_lo + g.per : g.tiles) : tile_lo + 1;
+    uint32_t tile_lo = blockIdx.x, tile_hi = tile_lo + 1;
+    if (REDUCE == 3) strip_tiles(g.per, g.tiles, tile_lo, tile_hi);
     uint32_t tile = tile_lo;
     bool live;
     float run_m = -INFINITY;
@@ -346,24 +348,6 @@ static int gd_entry(const char* what, void* stream, const float* obs, uint64_t r
     return gd_launch<32, REDUCE>(what, s, g, W, lds, grid);
 }
 
-// the strip function of the draw-sums form (file comment): rows alone decide
-static inline void gd_strips(uint64_t rows, uint32_t* tiles, uint32_t* per, uint32_t* strips)
-{
-    *tiles = cdiv(rows, D3P_GD_ROW_TILE);
-    *per = *tiles ? cdiv(*tiles, D3P_GD_MAX_STRIPS) : 0;
-    *strips = *tiles ? cdiv(*tiles, *per) : 0;
-}
-
-// out[s] = the strips' sums of draw s in ascending strip order
-__global__ void __launch_bounds__(256) k_gmm_draw_sums_merge(const double* part, uint32_t strips, uint32_t n, double* out)
-{
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s >= n) return;
-    double a = part[s];
-    for (uint32_t t = 1; t < strips; ++t) a += part[(size_t)t * n + s];
-    out[s] = a;
-}
-
 }  // namespace d3p
 
 using namespace d3p;
@@ -393,7 +377,7 @@ size_t d3p_gmm_loglik_draw_sums_workspace(uint64_t rows, int32_t d, int32_t k, u
 {
     (void)d; (void)k;   // (the strips are a function of rows alone)
     uint32_t tiles, per, strips;
-    gd_strips(rows, &tiles, &per, &strips);
+    row_strips(rows, D3P_GD_ROW_TILE, D3P_GD_MAX_STRIPS, &tiles, &per, &strips);
     return (size_t)strips * n * sizeof(double);
 }
 
@@ -423,12 +407,8 @@ int d3p_gmm_loglik_draw_sums(void* stream, const float* obs_dev, uint64_t rows, 
         return fail(D3P_E_INVALID_ARG, "%s: every pointer must be device memory", what);
     GmmDensityArgs g = {};
     uint32_t strips;
-    gd_strips(rows, &g.tiles, &g.per, &strips);
-    const size_t need = (size_t)strips * n * sizeof(double);
-    if (!workspace_dev || (uintptr_t)workspace_dev % sizeof(double) || !is_device_ptr(workspace_dev))
-        return fail(D3P_E_INVALID_ARG, "%s: the workspace must be device memory aligned to 8 bytes", what);
-    if (workspace_bytes < need)
-        return fail(D3P_E_INVALID_ARG, "%s: workspace of %zu bytes, %zu needed (d3p_gmm_loglik_draw_sums_workspace)", what, workspace_bytes, need);
+    row_strips(rows, D3P_GD_ROW_TILE, D3P_GD_MAX_STRIPS, &g.tiles, &g.per, &strips);
+    if (int rc = row_workspace_check(what, "d3p_gmm_loglik_draw_sums_workspace", workspace_dev, workspace_bytes, strips, 1, n)) return rc;
     g.obs = obs_dev; g.lat = latent_dev; g.ld = latent_ld; g.rows = (uint32_t)rows; g.n = n; g.k = k; g.d = d;
     g.part = static_cast<double*>(workspace_dev);
     int W;
@@ -437,8 +417,7 @@ int d3p_gmm_loglik_draw_sums(void* stream, const float* obs_dev, uint64_t rows, 
     if (int rc = k <= 4 ? gd_launch<4, 3>(what, s, g, W, lds, strips) : k <= 16 ? gd_launch<16, 3>(what, s, g, W, lds, strips)
                                                                                 : gd_launch<32, 3>(what, s, g, W, lds, strips))
         return rc;
-    hipLaunchKernelGGL(k_gmm_draw_sums_merge, dim3(cdiv(n, 256)), dim3(256), 0, s, g.part, strips, n, out_dev);
-    return check_launch(what);
+    return strip_merge<1, -1, -1>(what, s, g.part, strips, n, out_dev);
 }
 
 }  // extern "C"

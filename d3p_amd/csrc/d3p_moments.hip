@@ -70,13 +70,12 @@ __global__ void __launch_bounds__(256, 1) k_moments(MomentsArgs g)
                     float t = L[i * 65 + lane];
                     if (g.b_col >= 0) t = t + g.lat[(size_t)s * g.ld + g.b_col];
                     if (FAMILY == D3P_FAMILY_LOGREG) {
-                        const float e = expf(-fabsf(t));
-                        const float den = 1.0f + e;
-                        const float big = 1.0f / den, small = e / den;
-                        a0 += (double)(t >= 0.0f ? big : small);   // p = sigmoid(t)   (a NaN t: both NaN)
-                        a1 += (double)(t >= 0.0f ? small : big);   // q = sigmoid(-t)
+                        float p, q;
+                        sigmoid_pair(t, p, q);   // p = sigmoid(t), q = sigmoid(-t)   (a NaN t: both NaN)
+                        a0 += (double)p;
+                        a1 += (double)q;
                     } else {
-                        const float mu = FAMILY == D3P_FAMILY_POISSON ? expf(t) : t;
+                        const float mu = glm_mean<FAMILY>(t);
                         if (fabsf(mu) == INFINITY) {
                             inf_seen |= mu > 0.0f ? 1u : 2u;
                         } else {

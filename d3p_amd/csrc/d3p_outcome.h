@@ -4,8 +4,10 @@
 //   k_predict_stats (d3p_rep_stats.hip)   k_predict_discrepancy (d3p_discrepancy.hip)
 // The linear family's rule, normal_site_value, lives beside the tile (d3p_glm_tile.h).  Which numpyro / jax function each restates:
 // the file comments of d3p_predict.hip and d3p_predict_glm.hip, DESIGN.md section 4b.
+// glm_outcome<FAMILY> is the choice among the three rules per element, stage_obs_keys<FAMILY> the per-draw keys they take.
 #pragma once
 #include "d3p_device.h"
+#include "d3p_glm_tile.h"
 
 namespace d3p {
 
@@ -67,6 +69,35 @@ __device__ __forceinline__ int32_t poisson_draw(float t, uint32_t o0, uint32_t o
         }
     }
     return k > 2147483647.0 ? 2147483647 : (int32_t)k;
+}
+
+// keys[draw of the tile] = the draw's obs key and, for Poisson, fold_in(obs key, 0) (zeros past n), once per workgroup.  Called by
+// every thread before the first tile_product, which runs at least once (d >= 1, a strip has a tile): the product's barriers come
+// between this and the readers.
+template <int FAMILY>
+__device__ __forceinline__ void stage_obs_keys(uint32_t (*keys)[4], const uint32_t* obs_keys, uint32_t s0, uint32_t n)
+{
+    const int tid = threadIdx.x;
+    if (tid < D3P_TILE_M) {
+        const uint32_t s = s0 + tid;
+        uint32_t o0 = 0u, o1 = 0u, f0 = 0u, f1 = 0u;
+        if (s < n) {
+            o0 = obs_keys[2 * (size_t)s];
+            o1 = obs_keys[2 * (size_t)s + 1];
+            if (FAMILY == D3P_FAMILY_POISSON) threefry2x32(o0, o1, 0u, 0u, f0, f1);   // jax.random.fold_in(obs_key, 0)
+        }
+        keys[tid][0] = o0; keys[tid][1] = o1; keys[tid][2] = f0; keys[tid][3] = f1;
+    }
+}
+
+// The outcome of row r of `rows` at the predictor t under the draw's staged key words (o0, o1, f0, f1): float32 for the linear
+// family (sigma: the observation's standard deviation), int32 for Poisson and logistic -- what k_predict_glm / k_predict_logreg store
+template <int FAMILY>
+__device__ __forceinline__ auto glm_outcome(float t, uint32_t o0, uint32_t o1, uint32_t f0, uint32_t f1, uint64_t rows, uint64_t r, float sigma)
+{
+    if constexpr (FAMILY == D3P_FAMILY_LINREG) return normal_site_value(t, bits_to_normal(tf_iota_word(o0, o1, rows, r)), sigma);
+    else if constexpr (FAMILY == D3P_FAMILY_POISSON) return poisson_draw(t, o0, o1, f0, f1, (uint32_t)rows, (uint32_t)r);
+    else return bernoulli_draw(tf_iota_word(o0, o1, rows, r), sigmoid_probs(t));
 }
 
 }  // namespace d3p

@@ -53,16 +53,7 @@ __global__ void __launch_bounds__(256) k_predict_glm(GlmPredictArgs g)
     const int wm = wave >> 1, wn = wave & 1;
     const uint64_t r0 = (uint64_t)blockIdx.x * D3P_TILE_N;
     const uint32_t s0 = blockIdx.y * D3P_TILE_M;
-    if (tid < D3P_TILE_M) {   // (read after the barriers of the product loop, which runs at least once: d >= 1)
-        const uint32_t s = s0 + tid;
-        uint32_t o0 = 0u, o1 = 0u, f0 = 0u, f1 = 0u;
-        if (s < g.n) {
-            o0 = g.obs_keys[2 * (size_t)s];
-            o1 = g.obs_keys[2 * (size_t)s + 1];
-            if (FAMILY == D3P_FAMILY_POISSON) threefry2x32(o0, o1, 0u, 0u, f0, f1);   // jax.random.fold_in(obs_key, 0)
-        }
-        keys[tid][0] = o0; keys[tid][1] = o1; keys[tid][2] = f0; keys[tid][3] = f1;
-    }
+    stage_obs_keys<FAMILY>(keys, g.obs_keys, s0, g.n);
     tile_f16v acc[2][2];
     tile_product(smem, g, r0, s0, acc);
     // Epilogue, per half of the wave's 64 draws: the accumulators go to LDS ([draw 0..31][row 0..63], rows padded to 65 floats), then

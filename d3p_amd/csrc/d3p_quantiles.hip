@@ -23,7 +23,7 @@
 // draws of 0 and writes nothing.
 //
 // k_mean_rows is the sixth user of the draws x rows product tile (d3p_glm_tile.h) with k_loglik's rows-form grid (row tiles x draw
-// tiles) and store (64 consecutive floats per wave), and k_moments' link, text for text: mu = sigmoid(t) | t | exp(t).
+// tiles) and store (64 consecutive floats per wave), and the link k_moments has: mu = glm_mean<FAMILY>(t) (d3p_glm_tile.h).
 #include "d3p_colreduce.h"
 #include "d3p_device.h"
 #include "d3p_glm_tile.h"
@@ -189,16 +189,7 @@ __global__ void __launch_bounds__(256, 2) k_mean_rows(MeanRowsArgs g)
                 if (s >= g.n) break;
                 float t = L[i * 65 + lane];
                 if (g.b_col >= 0) t = t + g.lat[(size_t)s * g.ld + g.b_col];
-                float mu;
-                if (FAMILY == D3P_FAMILY_LOGREG) {   // k_moments' p = sigmoid(t): one e = exp(-|t|), the larger value 1 / (1 + e), the smaller e / (1 + e)
-                    const float e = expf(-fabsf(t));
-                    const float den = 1.0f + e;
-                    const float big = 1.0f / den, small = e / den;
-                    mu = t >= 0.0f ? big : small;    // (a NaN t: both NaN)
-                } else {
-                    mu = FAMILY == D3P_FAMILY_POISSON ? expf(t) : t;
-                }
-                g.out[(size_t)s * (size_t)g.out_ld + r] = mu;
+                g.out[(size_t)s * (size_t)g.out_ld + r] = glm_mean<FAMILY>(t);
             }
         }
         __syncthreads();

@@ -2,13 +2,14 @@
 // For draw s over the values v[s, r], r < rows (float32 or int32, taken to float64 exactly) and a host-given float64 shift c:
 //   out[0 n + s] = sum_r e,  e = fl64(v - c)          out[1 n + s] = sum_r fl64(e e)   (product and addition: two roundings)
 //   out[2 n + s] = min_r v   out[3 n + s] = max_r v   out[4 n + s] = #{r : v == 0}     (-0.0 counts, NaN does not)
-// Two forms with ONE accumulation (rep_add), one quarter merge (rep_strip_partial) and one strip merge (k_rep_stats_merge):
+// Two forms with ONE accumulation (rep_add), one quarter merge (rep_strip_partial) and one strip merge (k_strip_merge<5, 2, 3>):
 //   k_rep_stats<T>           v is a matrix in memory, m[s ld + r]                          (d3p_rep_stats)
 //   k_predict_stats<FAMILY>  v is the outcome the predictive kernels WOULD store, bit for bit: the shared product tile, the same
 //                            intercept add, the same outcome rule (d3p_outcome.h, normal_site_value) with the same obs keys, rows
 //                            and r as k_predict_glm / k_predict_logreg -- the n x rows matrix is never written  (d3p_predict_stats)
 //
-// Summation order of outputs 0 and 1: d3p_loglik_draw_sums' (d3p_draw_sums.hip), a function of the arguments alone.
+// Summation order of outputs 0 and 1: d3p_loglik_draw_sums' (d3p_draw_sums.hip), a function of the arguments alone -- the same
+// row_strips, strip_tiles, quarter_sum and k_strip_merge (d3p_row_sums.h).
 //   tiles = ceil(rows / 128);  per = ceil(tiles / 512);  strips = ceil(tiles / per)
 // A tile's 128 rows fall into four quarters of 32 consecutive rows.  One accumulator per (draw, strip, quarter) runs over the
 // strip's tiles ascending and rows ascending from 0.0; strip partial = ((q0 + q1) + q2) + q3, written to the workspace as float64
@@ -21,26 +22,20 @@
 // 0..63][row 0..127] with rows padded to 129 words.  Then wave q = quarter, lane = draw: lane l walks 32 rows at L[l 129 + 32 q + j],
 // 64 lanes on 64 distinct banks ((l + j) mod 64).
 // k_predict_stats: k_draw_sums' grid and epilogue (lane = draw l % 32 and row half l / 32 of the wave's 64 rows, walking 32 rows on 32
-// distinct banks), the per-draw keys in LDS once per workgroup as in k_predict_glm.  The draw halves are NOT unrolled (the outcome
-// rule, Poisson's above all, is instantiated once); the lane's two accumulators are picked by hand, so nothing is indexed in scratch.
+// distinct banks), the per-draw keys in LDS once per workgroup (stage_obs_keys, d3p_outcome.h).  The draw halves are NOT unrolled (the
+// outcome rule, glm_outcome, Poisson's above all, is instantiated once); the lane's two accumulators are picked by hand, so nothing is
+// indexed in scratch.
 #include "d3p_device.h"
 #include "d3p_glm_tile.h"
 #include "d3p_host.h"
 #include "d3p_outcome.h"
+#include "d3p_row_sums.h"
 
 namespace d3p {
 
-#define D3P_REP_MAX_STRIPS 512   // d3p_loglik_draw_sums' strip function
 #define D3P_REP_STATS 5
 #define D3P_REP_LD 129           // padded row count of a staged draw (k_rep_stats)
 #define D3P_REP_HALF 64          // draws staged at a time (k_rep_stats)
-
-static inline void rep_strips(uint64_t rows, uint32_t* tiles, uint32_t* per, uint32_t* strips)
-{
-    *tiles = cdiv(rows, D3P_TILE_N);
-    *per = *tiles ? cdiv(*tiles, D3P_REP_MAX_STRIPS) : 0;
-    *strips = *tiles ? cdiv(*tiles, *per) : 0;
-}
 
 // one (draw, strip, quarter) accumulator; T = float or int32_t
 template <class T>
@@ -90,48 +85,20 @@ __device__ __forceinline__ void rep_put(double* red, int q, int dl, const RepAcc
     red[(4 * 4 + q) * D3P_TILE_M + dl] = (double)a.zeros;
 }
 
-// min / max by value with NaN carried: x NaN or m NaN gives NaN
-__device__ __forceinline__ double rep_min(double m, double x) { return (m != m || x != x) ? m + x : (x < m ? x : m); }
-__device__ __forceinline__ double rep_max(double m, double x) { return (m != m || x != x) ? m + x : (x > m ? x : m); }
-
 // the four quarters of draw dl in the order q = 0, 1, 2, 3 -> part[strip][stat][n]; called by the threads dl < 128 after a barrier
+// (min and max by rep_min / rep_max, d3p_row_sums.h: a NaN is carried)
 __device__ __forceinline__ void rep_strip_partial(const double* red, int dl, uint32_t s, uint32_t n, uint32_t strip, double* part)
 {
-#pragma clang fp contract(off)
+    const int M = D3P_TILE_M;
     const double* r = red + dl;
     double* p = part + (size_t)strip * D3P_REP_STATS * n + s;
-    p[0] = ((r[0] + r[D3P_TILE_M]) + r[2 * D3P_TILE_M]) + r[3 * D3P_TILE_M];
-    r += 4 * D3P_TILE_M;
-    p[n] = ((r[0] + r[D3P_TILE_M]) + r[2 * D3P_TILE_M]) + r[3 * D3P_TILE_M];
-    r += 4 * D3P_TILE_M;
-    p[2 * (size_t)n] = rep_min(rep_min(rep_min(r[0], r[D3P_TILE_M]), r[2 * D3P_TILE_M]), r[3 * D3P_TILE_M]);
-    r += 4 * D3P_TILE_M;
-    p[3 * (size_t)n] = rep_max(rep_max(rep_max(r[0], r[D3P_TILE_M]), r[2 * D3P_TILE_M]), r[3 * D3P_TILE_M]);
-    r += 4 * D3P_TILE_M;
-    p[4 * (size_t)n] = ((r[0] + r[D3P_TILE_M]) + r[2 * D3P_TILE_M]) + r[3 * D3P_TILE_M];   // (counts: exact)
-}
-
-// out[k n + s] = the strips' partials of draw s in ascending strip order, starting from strip 0's
-__global__ void __launch_bounds__(256) k_rep_stats_merge(const double* part, uint32_t strips, uint32_t n, double* out)
-{
-#pragma clang fp contract(off)
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s >= n) return;
-    const double* p = part + s;
-    double a0 = p[0], a1 = p[n], a2 = p[2 * (size_t)n], a3 = p[3 * (size_t)n], a4 = p[4 * (size_t)n];
-    for (uint32_t k = 1; k < strips; ++k) {
-        p += (size_t)D3P_REP_STATS * n;
-        a0 = a0 + p[0];
-        a1 = a1 + p[n];
-        a2 = rep_min(a2, p[2 * (size_t)n]);
-        a3 = rep_max(a3, p[3 * (size_t)n]);
-        a4 = a4 + p[4 * (size_t)n];
-    }
-    out[s] = a0;
-    out[(size_t)n + s] = a1;
-    out[2 * (size_t)n + s] = a2;
-    out[3 * (size_t)n + s] = a3;
-    out[4 * (size_t)n + s] = a4;
+    p[0] = quarter_sum(r, M);
+    p[n] = quarter_sum(r + 4 * M, M);
+    r += 8 * M;
+    p[2 * (size_t)n] = rep_min(rep_min(rep_min(r[0], r[M]), r[2 * M]), r[3 * M]);
+    r += 4 * M;
+    p[3 * (size_t)n] = rep_max(rep_max(rep_max(r[0], r[M]), r[2 * M]), r[3 * M]);
+    p[4 * (size_t)n] = quarter_sum(r + 4 * M, M);   // (counts: exact)
 }
 
 // ---- the model-free form ---------------------------------------------------------------------------------------------------------
@@ -154,16 +121,16 @@ __global__ void __launch_bounds__(256) k_rep_stats(RepStatsArgs g)
     const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;   // q: the wave, and the quarter it walks
     const T* m = static_cast<const T*>(g.m);
     const uint32_t s0 = blockIdx.y * D3P_TILE_M;
-    const uint32_t t_lo = blockIdx.x * g.per;
-    const uint32_t t_hi = t_lo + g.per < g.tiles ? t_lo + g.per : g.tiles;
+    uint32_t t_lo, t_hi;
+    strip_tiles(g.per, g.tiles, t_lo, t_hi);
     const int col = q * 32;
     RepAcc<T> acc[2];
     rep_init(acc[0]);
     rep_init(acc[1]);
     for (uint32_t t = t_lo; t < t_hi; ++t) {
         const uint64_t r0 = (uint64_t)t * D3P_TILE_N;
-        const uint64_t left = g.rows - r0;   // >= 1
-        const int jn = left <= (uint64_t)col ? 0 : (left - col >= 32 ? 32 : (int)(left - col));   // the lane's live rows in this tile
+        const uint64_t left = g.rows - r0;   // >= 1: the tile's live rows, for the staging
+        const int jn = quarter_live_rows(g.rows, r0, col);
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
 #pragma unroll
@@ -224,18 +191,9 @@ __global__ void __launch_bounds__(256, 1) k_predict_stats(PredictStatsArgs g)
     const int i = lane & 31, h = lane >> 5;            // the lane's draw within a half of the wave's draws; its half of the wave's rows
     const int col = wn * 64 + h * 32;                  // first of the lane's 32 rows within a tile: quarter q = 2 wn + h
     const uint32_t s0 = blockIdx.y * D3P_TILE_M;
-    const uint32_t t_lo = blockIdx.x * g.per;
-    const uint32_t t_hi = t_lo + g.per < g.tiles ? t_lo + g.per : g.tiles;
-    if (tid < D3P_TILE_M) {   // (read after the barriers of the first product, which runs at least once: d >= 1, a strip has a tile)
-        const uint32_t s = s0 + tid;
-        uint32_t o0 = 0u, o1 = 0u, f0 = 0u, f1 = 0u;
-        if (s < g.n) {
-            o0 = g.obs_keys[2 * (size_t)s];
-            o1 = g.obs_keys[2 * (size_t)s + 1];
-            if (FAMILY == D3P_FAMILY_POISSON) threefry2x32(o0, o1, 0u, 0u, f0, f1);   // jax.random.fold_in(obs_key, 0)
-        }
-        keys[tid][0] = o0; keys[tid][1] = o1; keys[tid][2] = f0; keys[tid][3] = f1;
-    }
+    uint32_t t_lo, t_hi;
+    strip_tiles(g.per, g.tiles, t_lo, t_hi);
+    stage_obs_keys<FAMILY>(keys, g.obs_keys, s0, g.n);
     RepAcc<T> a0, a1;
     rep_init(a0);
     rep_init(a1);
@@ -244,8 +202,7 @@ __global__ void __launch_bounds__(256, 1) k_predict_stats(PredictStatsArgs g)
         tile_f16v acc[2][2];
         tile_product(smem, g, r0, s0, acc);
         float* L = tile_block(smem);
-        const uint64_t left = g.rows - r0;   // >= 1
-        const int jn = left <= (uint64_t)col ? 0 : (left - col >= 32 ? 32 : (int)(left - col));   // the lane's live rows in this tile
+        const int jn = quarter_live_rows(g.rows, r0, col);
 #pragma unroll 1
         for (int mb = 0; mb < 2; ++mb) {
             tile_scatter(L, mb == 0 ? acc[0][0] : acc[1][0], mb == 0 ? acc[0][1] : acc[1][1]);   // (selected by hand: the loop is not unrolled)
@@ -262,14 +219,7 @@ __global__ void __launch_bounds__(256, 1) k_predict_stats(PredictStatsArgs g)
                 for (int j = 0; j < jn; ++j) {
                     float tv = p[j];
                     if (g.b_col >= 0) tv = tv + b;
-                    const uint64_t r = rb + j;
-                    T v;
-                    if (FAMILY == D3P_FAMILY_LINREG)
-                        v = (T)normal_site_value(tv, bits_to_normal(tf_iota_word(o0, o1, g.rows, r)), g.sigma);
-                    else if (FAMILY == D3P_FAMILY_POISSON)
-                        v = (T)poisson_draw(tv, o0, o1, keys[sl][2], keys[sl][3], (uint32_t)g.rows, (uint32_t)r);
-                    else
-                        v = (T)bernoulli_draw(tf_iota_word(o0, o1, g.rows, r), sigmoid_probs(tv));
+                    const T v = glm_outcome<FAMILY>(tv, o0, o1, keys[sl][2], keys[sl][3], g.rows, rb + j, g.sigma);
                     rep_add(a, v, g.shift);
                 }
                 if (mb == 0) a0 = a; else a1 = a;
@@ -284,15 +234,6 @@ __global__ void __launch_bounds__(256, 1) k_predict_stats(PredictStatsArgs g)
     if (tid < D3P_TILE_M && s0 + tid < g.n) rep_strip_partial(red, tid, s0 + tid, g.n, blockIdx.x, g.part);
 }
 
-static int rep_workspace_check(const char* what, void* ws, size_t ws_bytes, uint32_t strips, uint32_t n)
-{
-    const size_t need = (size_t)strips * D3P_REP_STATS * n * sizeof(double);
-    if (!ws || (uintptr_t)ws % sizeof(double)) return fail(D3P_E_INVALID_ARG, "%s: the workspace must be aligned to 8 bytes and not null", what);
-    if (ws_bytes < need) return fail(D3P_E_INVALID_ARG, "%s: workspace of %zu bytes, %zu needed (d3p_rep_stats_workspace)", what, ws_bytes, need);
-    if (!is_device_ptr(ws)) return fail(D3P_E_INVALID_ARG, "%s: the workspace must be device memory", what);
-    return D3P_OK;
-}
-
 }  // namespace d3p
 
 using namespace d3p;
@@ -303,7 +244,7 @@ size_t d3p_rep_stats_workspace(uint64_t rows, uint32_t n)
 {
     if (rows > 0xFFFFFFFFull) return 0;
     uint32_t tiles, per, strips;
-    rep_strips(rows, &tiles, &per, &strips);
+    row_strips(rows, D3P_TILE_N, D3P_ROW_SUMS_MAX_STRIPS, &tiles, &per, &strips);
     return (size_t)strips * D3P_REP_STATS * n * sizeof(double);
 }
 
@@ -322,8 +263,8 @@ int d3p_rep_stats(void* stream, const void* m_dev, int32_t dtype, int64_t ld, ui
     if (!std::isfinite(shift)) return fail(D3P_E_INVALID_ARG, "%s: the shift must be finite", what);
     RepStatsArgs g;
     uint32_t strips;
-    rep_strips(rows, &g.tiles, &g.per, &strips);
-    if (int rc = rep_workspace_check(what, workspace_dev, workspace_bytes, strips, n)) return rc;
+    row_strips(rows, D3P_TILE_N, D3P_ROW_SUMS_MAX_STRIPS, &g.tiles, &g.per, &strips);
+    if (int rc = row_workspace_check(what, "d3p_rep_stats_workspace", workspace_dev, workspace_bytes, strips, D3P_REP_STATS, n)) return rc;
     if (!is_device_ptr(m_dev) || !is_device_ptr(out_dev)) return fail(D3P_E_INVALID_ARG, "%s: the matrix and out must be device memory", what);
     g.m = m_dev; g.ld = ld; g.n = n; g.rows = rows; g.shift = shift; g.part = static_cast<double*>(workspace_dev);
     hipStream_t s = (hipStream_t)stream;
@@ -331,8 +272,7 @@ int d3p_rep_stats(void* stream, const void* m_dev, int32_t dtype, int64_t ld, ui
     if (dtype == 0) hipLaunchKernelGGL((k_rep_stats<float>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((k_rep_stats<int32_t>), grid, dim3(256), 0, s, g);
     if (int rc = check_launch(what)) return rc;
-    hipLaunchKernelGGL(k_rep_stats_merge, dim3(cdiv(n, 256)), dim3(256), 0, s, g.part, strips, n, out_dev);
-    return check_launch(what);
+    return strip_merge<D3P_REP_STATS, 2, 3>(what, s, g.part, strips, n, out_dev);
 }
 
 int d3p_predict_stats(void* stream, const d3p_logreg_model* model, const float* X_dev, uint64_t rows, int32_t d, const float* latent_dev,
@@ -355,8 +295,8 @@ int d3p_predict_stats(void* stream, const d3p_logreg_model* model, const float* 
     if (!std::isfinite(shift)) return fail(D3P_E_INVALID_ARG, "%s: the shift must be finite", what);
     PredictStatsArgs g;
     uint32_t strips;
-    rep_strips(rows, &g.tiles, &g.per, &strips);
-    if (int rc = rep_workspace_check(what, workspace_dev, workspace_bytes, strips, n)) return rc;
+    row_strips(rows, D3P_TILE_N, D3P_ROW_SUMS_MAX_STRIPS, &g.tiles, &g.per, &strips);
+    if (int rc = row_workspace_check(what, "d3p_rep_stats_workspace", workspace_dev, workspace_bytes, strips, D3P_REP_STATS, n)) return rc;
     g.X = X_dev; g.rows = rows; g.d = d; g.w_off = w_off; g.b_col = b_col; g.lat = latent_dev; g.ld = latent_ld; g.n = n;
     g.sigma = m->family == D3P_FAMILY_LINREG ? m->lik_sigma : 0.f;
     g.obs_keys = obs_keys_dev; g.shift = shift; g.part = static_cast<double*>(workspace_dev);
@@ -366,8 +306,7 @@ int d3p_predict_stats(void* stream, const d3p_logreg_model* model, const float* 
     else if (m->family == D3P_FAMILY_POISSON) hipLaunchKernelGGL((k_predict_stats<D3P_FAMILY_POISSON>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((k_predict_stats<D3P_FAMILY_LOGREG>), grid, dim3(256), 0, s, g);
     if (int rc = check_launch(what)) return rc;
-    hipLaunchKernelGGL(k_rep_stats_merge, dim3(cdiv(n, 256)), dim3(256), 0, s, g.part, strips, n, out_dev);
-    return check_launch(what);
+    return strip_merge<D3P_REP_STATS, 2, 3>(what, s, g.part, strips, n, out_dev);
 }
 
 }  // extern "C"

@@ -244,8 +244,11 @@ def test_module_surface_and_lazy_import():
 def test_the_kernel_calls_the_shared_outcome_rules_and_has_no_atomics():
     with open(os.path.join(ROOT, "d3p_amd", "csrc", "d3p_discrepancy.hip")) as f:
         text = f.read()
+    with open(os.path.join(ROOT, "d3p_amd", "csrc", "d3p_outcome.h")) as f:
+        outcome = f.read()
+    choice = outcome[outcome.index("auto glm_outcome("):]   # the one choice among the rules, built on the one definition of each
     for call in ("poisson_draw(", "bernoulli_draw(", "sigmoid_probs(", "normal_site_value(", "tile_product(", "tile_scatter("):
-        assert call in text, call
+        assert call in text or ("glm_outcome<FAMILY>(" in text and call in choice), call
     for definition in (r"int32_t poisson_draw\(", r"int32_t bernoulli_draw\(", r"float sigmoid_probs\(", r"float normal_site_value\("):
         assert not re.search(definition, text), definition
     assert "atomic" not in text.lower().replace("no floating-point atomics", "")

@@ -86,3 +86,35 @@ def test_moments_of_identical_draws_are_the_single_draws(gpu, family, intercept)
                 assert torch.equal(_bits(mean), _bits(mean1)), (d, rows, n)
                 if family == "linear":
                     assert np.all(var.cpu().numpy() == sig2), (d, rows, n)
+
+
+@pytest.mark.parametrize("intercept", [False, True])
+@pytest.mark.parametrize("family", list(FAMILIES))
+def test_the_three_users_of_the_link_agree_bit_for_bit(gpu, family, intercept):
+    """glm_mean (d3p_glm_tile.h) is ONE link: for one draw in a padded latent row, d3p_predict_moments' mean (its float64 sums of one
+    value round back to the float32 mu) is row 0 of d3p_predict_mean_rows' matrix, and d3p_predict_discrepancy's out[2] at shift 0 is
+    the float64 sum of that row in the stated order (tests/discrepancy_ref.py)."""
+    from . import discrepancy_ref as R
+    lib = L.load()
+    d, rows, n = 33, 129, 1
+    X, y, w = _problem(family, d, rows, intercept, seed=4242 + int(intercept))
+    ld, w_off, b_col = d + 3, 2, (0 if intercept else -1)
+    lat = torch.full((n, ld), 7.0, device="cuda")           # (the padding is never read: 7 would show)
+    lat[:, w_off:w_off + d] = w[:, :d]
+    if intercept:
+        lat[:, b_col] = w[:, d]
+    ms = _struct(family, d, intercept)
+    mu = torch.empty((n, rows), device="cuda")
+    L.check(lib.d3p_predict_mean_rows(L.stream_ptr(), C.byref(ms), L.ptr(X), rows, L.ptr(lat), ld, w_off, b_col, n, L.ptr(mu), rows))
+    mean, var = torch.empty(rows, device="cuda"), torch.empty(rows, device="cuda")
+    L.check(lib.d3p_predict_moments(L.stream_ptr(), C.byref(ms), L.ptr(X), rows, L.ptr(lat), ld, w_off, b_col, n, L.ptr(mean), L.ptr(var)))
+    assert bool(torch.isfinite(mu).all())
+    assert torch.equal(_bits(mean), _bits(mu[0]))
+    keys = torch.tensor([[0x9E3779B9 - 2 ** 32, 0x243F6A88]], dtype=torch.int32, device="cuda")
+    out = torch.empty((6, n), dtype=torch.float64, device="cuda")
+    nbytes = lib.d3p_predict_discrepancy_workspace(rows, n)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
+    L.check(lib.d3p_predict_discrepancy(L.stream_ptr(), C.byref(ms), L.ptr(X), L.ptr(y), rows, d, L.ptr(lat), ld, w_off, b_col, n, L.ptr(keys), 0.0,
+                                        L.ptr(out), L.ptr(ws), nbytes))
+    want = R.ordered_sum(mu.cpu().numpy().astype(np.float64))
+    assert np.array_equal(out[2].cpu().numpy().view(np.int64), want.view(np.int64)), (out[2], want)

@@ -108,8 +108,11 @@ def test_each_outcome_rule_is_defined_once():
     assert all(c == 1 for c in counts.values()), counts
     with open(os.path.join(csrc, "d3p_rep_stats.hip")) as f:
         text = f.read()
+    with open(os.path.join(csrc, "d3p_outcome.h")) as f:
+        outcome = f.read()
+    choice = outcome[outcome.index("auto glm_outcome("):]   # the one choice among the rules, built on the one definition of each
     for call in ("poisson_draw(", "bernoulli_draw(", "sigmoid_probs(", "normal_site_value(", "tile_product(", "tile_scatter("):
-        assert call in text, call                      # the fused kernel applies the shared rules, not copies
+        assert call in text or ("glm_outcome<FAMILY>(" in text and call in choice), call   # the fused kernel applies the shared rules, not copies
     assert "atomic" not in text.lower().replace("no floating-point atomics", "")
 
 

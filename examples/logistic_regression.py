@@ -20,6 +20,11 @@ reduced as they are drawn; they are never written.
 Stern (1996) on the training table: per draw from the trained guide the Pearson chi-square of the observed outcomes and of that draw's
 own replicate, the share p_ge of draws whose replicate is at least as far from the mean as the data, the dispersion chi2_obs / rows
 (near 1 for labels the model explains), and the Bayesian R^2 (both kinds), RMSE and bias per draw.
+--classification-report [N_DRAWS] (off by default; d3p_amd.classification; --guide auto) adds, after training, the classifier's own
+numbers on the TEST table: the sampled accuracy of N_DRAWS posterior draws -- the number --predictive-accuracy prints, here with its sd
+and 90 % interval over the draws and without the N_DRAWS x rows label matrix -- then accuracy, TPR, FPR and F1 of the predicted
+probability at the threshold 0.5, and of the posterior mean probability the AUC with its certificate [auc_lo, auc_hi], the KS statistic
+and the expected calibration error.  estimate_accuracy below stays as the stored-matrix comparator.
 """
 import argparse
 import os
@@ -82,6 +87,15 @@ def discrepancy_report(model, guide, params, X, y, num_draws, seed=8):
     import d3p_amd.random.debug as jax_random
     res = discrepancy.discrepancy_check(jax_random.PRNGKey(seed), num_draws, model, (X, y), guide, params)
     return ["realized discrepancy check ({} rows, {} draws):".format(res.n_rows, res.n_draws)] + res.lines()
+
+
+def classification_lines(model, guide, params, X, y, num_draws, seed=9, bins=10):
+    """The lines of --classification-report (d3p_amd.classification): sampled accuracy +- sd with its 90 % interval over num_draws draws
+    from the trained guide; accuracy, TPR, FPR and F1 at the threshold 0.5; auc [auc_lo, auc_hi], KS and ECE of the mean probability."""
+    from d3p_amd import classification
+    import d3p_amd.random.debug as jax_random
+    return classification.classification_report(jax_random.PRNGKey(seed), num_draws, model, (X, y), guide, params, thresholds=(0.5,),
+                                                bins=bins).lines()
 
 
 def main(args):
@@ -149,6 +163,11 @@ def main(args):
         print("\n".join(ppc_report(model, guide, svi.get_params(svi_state), *train, args.ppc)))
     if getattr(args, "discrepancy", None) is not None:   # both guides
         print("\n".join(discrepancy_report(model, guide, svi.get_params(svi_state), *train, args.discrepancy)))
+    if getattr(args, "classification_report", None) is not None:
+        if isinstance(guide, MeanFieldGuide):
+            print("classification report: --guide auto only (d3p_amd.classification runs AutoDiagonalNormal and DiagonalNormalGuide)")
+        else:
+            print("\n".join(classification_lines(model, guide, svi.get_params(svi_state), *test, args.classification_report)))
     return accs, train_losses
 
 
@@ -174,4 +193,7 @@ if __name__ == "__main__":
     parser.add_argument('--discrepancy', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, print the chi-square realized-discrepancy check of N_DRAWS (default 100) draws: p_ge, p_le, '
                              'the dispersion, the Bayesian R^2, RMSE and bias per draw')
+    parser.add_argument('--classification-report', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, print on the test table the sampled accuracy of N_DRAWS (default 100) posterior draws with '
+                             'its sd, accuracy / TPR / FPR / F1 at 0.5, and the AUC with its certificate, KS and ECE of the mean probability')
     main(parser.parse_args())

@@ -1366,6 +1366,57 @@ int d3p_predict_discrepancy(void* stream, const d3p_logreg_model* model, const f
                             const float* latent_dev, int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n,
                             const uint32_t* obs_keys_dev, double shift, double* out_dev, void* workspace_dev, size_t workspace_bytes);
 
+/* Classification metrics of a fitted logistic regression (d3p_amd/classification.py; d3p_classify.hip); added symbols,
+ * ABI 9 and d3p_logreg_model unchanged.  Everything below is an INTEGER (counts, pair counts, fixed-point sums): no summation order is
+ * promised because none matters, and every output is a function of the arguments alone.
+ *
+ * d3p_predict_confusion (D3P_FAMILY_LOGREG only; every other family: D3P_E_UNSUPPORTED): for draw s and row r, with t the product
+ * tile's value (+ the intercept) as in every entry above,
+ *   mu = the float32 mean d3p_predict_mean_rows stores for the same arguments (the two-branch sigmoid)
+ *   v  = the 0 / 1 label d3p_predict_logreg stores for the same arguments, obs keys included
+ * out_dev of D3P_CONF_COUNTS n uint64, D3P_CONF_COUNTS = 2 + 2 D3P_CONF_THRESHOLDS = 10:
+ *   out_dev[0 n + s]           = #{r : (float)v[s, r] == y_r}             (the reference's estimate_accuracy, per draw)
+ *   out_dev[1 n + s]           = #{r : mu[s, r] is NaN}
+ *   out_dev[(2 + 2 j) n + s]   = #{r : mu[s, r] >= tau[j] and y_r == 1}   true positives at threshold j < T
+ *   out_dev[(3 + 2 j) n + s]   = #{r : mu[s, r] >= tau[j] and y_r == 0}   false positives at threshold j < T
+ * The comparison is float32 >=: a NaN mu is in neither set, and a NaN threshold counts nothing.  The slots of j >= T are 0.  y_dev: float32
+ * labels on the device; a label that is neither 0 nor 1 is in no tp / fp set.  tau_host: T float32 thresholds in HOST memory (read
+ * before the entry returns; may be null at T == 0).  The entry zeroes out_dev on the stream and the kernel adds each strip's counts onto
+ * it with 64-bit integer atomic adds: no workspace.  d3p_predict_confusion_set_strips(max_strips) (a test aid; 0: the default, 512)
+ * changes the grid, never a result.
+ * Before any launch, d3p_predict_discrepancy's refusals (model, d, pointers null or not device memory, n, the latent layout, rows == 0,
+ * y_dev aligned to 4 bytes, out_dev to 8) and T outside 0..4 or a null tau_host at T > 0: D3P_E_INVALID_ARG; D3P_GUIDE_EXP_SITES and
+ * D3P_FAMILY_GAUSS_MEAN / LINREG / POISSON: D3P_E_UNSUPPORTED.
+ *
+ * d3p_binary_curve: the ROC histogram and the reliability table of one score vector p_dev (float32[rows], probabilities in [0, 1])
+ * against labels y_dev (int32[rows] in {0, 1}); model-free.
+ *   hist_dev[class][bin] uint32, 2 x D3P_CURVE_BINS, D3P_CURVE_BINS = 0x7E001: with c(x) = float_as_uint(x) >> 12,
+ *       bin(p) = c(p) for p < 0.5f,   2 * 0x3F000 - c(1.0f - p) otherwise   (1.0f - p is exact there; -0.0f counts as 0)
+ *     a strictly order-preserving map that keeps 11 mantissa bits of min(p, 1 - p) at both ends
+ *   calib_dev[3][B] uint64 over B <= 64 equal-width bins, b = min(B - 1, (int)(p * (float)B)) in float32:
+ *     calib_dev[0 B + b] = #{r in bin b}   calib_dev[1 B + b] = #{r in bin b, y_r == 1}   calib_dev[2 B + b] = sum_r (uint64)((double)p_r * 2^36)
+ *   summary_dev[D3P_CURVE_SUMMARY = 6] uint64: [0] = the rows left out of every table (p NaN, < 0 or > 1, or y outside {0, 1})
+ *     [1] = P = the positives   [2] = N = the negatives
+ *     [3] = pairs_concordant = sum_b pos_b #{negatives in the bins below b}   [4] = pairs_same_bin = sum_b pos_b neg_b
+ *     [5] = max_k |b_k P - a_k N|, a_k / b_k the positives / negatives of the bins 0..k: over P N, the Kolmogorov-Smirnov statistic
+ *           max |tpr - fpr| over the bin edges
+ * so that (conc + same / 2) / (P N) is the AUC up to the pairs one bin cannot order, and conc / (P N) <= AUC <= (conc + same) / (P N).
+ * The entry zeroes the three tables on the stream; equal bins of a wavefront are added once.  rows <= 2^27 (the fixed-point sums stay
+ * below 2^63).  Workspace: d3p_binary_curve_workspace() bytes (the per-chunk totals of hist); its prior content is never read.
+ * Before any launch: a null, misaligned (p, y, hist: 4 bytes; calib, summary, workspace: 8) or non-device pointer, rows == 0 or
+ * > 2^27, B outside 1..64, a short workspace: D3P_E_INVALID_ARG. */
+#define D3P_CONF_THRESHOLDS 4
+#define D3P_CONF_COUNTS (2 + 2 * D3P_CONF_THRESHOLDS)
+#define D3P_CURVE_BINS 0x7E001
+#define D3P_CURVE_SUMMARY 6
+int d3p_predict_confusion_set_strips(int32_t max_strips);
+int d3p_predict_confusion(void* stream, const d3p_logreg_model* model, const float* X_dev, const float* y_dev, uint64_t rows, int32_t d,
+                          const float* latent_dev, int64_t latent_ld, int32_t w_off, int32_t b_col, uint32_t n,
+                          const uint32_t* obs_keys_dev, const float* tau_host, int32_t T, uint64_t* out_dev);
+size_t d3p_binary_curve_workspace(void);
+int d3p_binary_curve(void* stream, const float* p_dev, const int32_t* y_dev, uint64_t rows, uint32_t B, uint32_t* hist_dev, uint64_t* calib_dev,
+                     uint64_t* summary_dev, void* workspace_dev, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

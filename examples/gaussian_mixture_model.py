@@ -27,6 +27,11 @@ whose Pareto shape lies above the threshold, on the same split and draws.
 --guide-diagnostic [N_DRAWS] (off by default; d3p_amd.mixture_diagnostics) adds one line: the full-data ELBO +- its standard error, the
 importance-sampling estimate of the log evidence, the Pareto k of the guide's importance ratios against its threshold and their
 effective sample size, on the training split (Yao et al. 2018: is the trained guide a usable approximation of the posterior?).
+
+--energy-score [N_DRAWS] (off by default; d3p_amd.energy) adds one line beside --held-out-density: the energy score (the multivariate
+CRPS, Gneiting & Raftery 2007) of N_DRAWS posterior predictive draws per point of the test split +- its standard error, with its two
+parts, the mean distance of a draw to the point and the spread of the draws.  It scores the draws a user would ship as synthetic data,
+in the data's own units; smaller is better.
 """
 import argparse
 import itertools
@@ -102,6 +107,15 @@ def held_out_density(X_test, z_test, params, k, num_draws, seed=4321):
             mapped[c] = j
         best = max(best, float((mapped[soft] == z_test).float().mean()))
     return float(out["log_predictive_density"].mean()), best
+
+
+def energy_score_report(X_test, params, k, num_draws, seed=4324):
+    """The EnergyScoreResult of num_draws posterior predictive draws per held-out point against X_test (d3p_amd.energy): the
+    multivariate CRPS, in the data's own units."""
+    from d3p_amd import energy
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    return energy.posterior_predictive_energy_score(threefry.PRNGKey(seed), num_draws, model, (k, X_test), GaussianMixtureGuide(model), params)
 
 
 def waic_report(X, params, k, num_draws, seed=4322):
@@ -197,6 +211,10 @@ def main(args):
         print("held-out log predictive density (mean over {} points, {} posterior draws): {:.4f}".format(
             X_test.shape[0], args.posterior_draws, lppd))
         print("assignment accuracy (argmax of posterior responsibilities): {:.4f}".format(soft_acc))
+    if getattr(args, "energy_score", None) is not None:
+        res = energy_score_report(X_test, params, k, args.energy_score)
+        print("held-out energy score (mean over {} points, {} predictive draws): {:.4f} +- {:.4f} (mean distance {:.4f}, spread {:.4f})".format(
+            res.n_rows, res.n_draws, float(res.es), float(res.se), float(res.mae), float(res.spread)))
     if getattr(args, "waic", False):
         res = waic_report(X_train, params, k, args.posterior_draws)
         print("WAIC ({} points, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
@@ -233,6 +251,9 @@ def parse_args(argv=None):
     parser.add_argument('--guide-diagnostic', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, report the ELBO, the importance-sampling evidence, the Pareto k and the effective sample '
                              'size of N_DRAWS (default 100) draws from the guide on the training table')
+    parser.add_argument('--energy-score', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
+                        help='after training, report the energy score (the multivariate CRPS) of N_DRAWS (default 100) posterior '
+                             'predictive draws per point of the test split')
     return parser.parse_args(argv)
 
 

@@ -1417,6 +1417,43 @@ size_t d3p_binary_curve_workspace(void);
 int d3p_binary_curve(void* stream, const float* p_dev, const int32_t* y_dev, uint64_t rows, uint32_t B, uint32_t* hist_dev, uint64_t* calib_dev,
                      uint64_t* summary_dev, void* workspace_dev, size_t workspace_bytes);
 
+/* The energy score of multivariate predictive draws against the observed outcomes (model-free; d3p_amd/energy.py; d3p_energy.hip;
+ * DESIGN.md 4v); added symbols, ABI 9 unchanged.  ES = E|X - y| - 1/2 E|X - X'| (Gneiting & Raftery 2007), the multivariate CRPS.
+ * draws_dev[s * ld_draw + r * ld_row + c] is draw s < n of row r < rows in column c < d (column stride 1), float32 (dtype 0) or int32
+ * (dtype 1: converted to float32 when staged, which is exact for |v| <= 2^24; the Python layer refuses larger magnitudes);
+ * y_dev[r * y_ld + c] the observation, of the same dtype.  For row r the items are z_0 .. z_{n-1} (the draws) and z_n = y_r; per pair
+ *   t_c = fl32(a_c - b_c),  q = the float32 fmaf chain over c ascending from 0,  dist = sqrtf(q) correctly rounded, widened to float64
+ * and with S1 = sum_i dist(z_i, y), S2 = sum_{i != j} dist(z_i, z_j) in float64 in the fixed order d3p_energy.hip states (each
+ * unordered pair computed once, counted twice):
+ *   out_dev[0 * out_ld + r] = es      = mae - spread
+ *   out_dev[1 * out_ld + r] = es_fair = mae - S2 / (2 n (n - 1))   (NaN at n = 1: 0 / 0 is the rule)
+ *   out_dev[2 * out_ld + r] = mae     = S1 / n
+ *   out_dev[3 * out_ld + r] = spread  = S2 / (2 n^2)
+ * each rounded to float32 once.  A NaN or +-inf element among a row's draws or in its y makes that row's four outputs NaN and touches
+ * no other row; finite elements whose t_c or q overflows float32 follow IEEE from there (dist = inf).  At d = 1 es is the CRPS of
+ * d3p_col_crps up to the two rules' rounding.
+ * Two forms, which agree bit for bit: 1, rows (one wavefront per row, d3p_energy_score_rows_per_group(1) = 16 adjacent rows per
+ * workgroup) and 2, streamed (one row per workgroup, its pair tiles dealt to four wavefronts).  Both walk pair tiles of
+ * d3p_energy_score_tile_draws() = 32 items a side in column chunks of d3p_energy_score_chunk_cols() = 32 staged in LDS, so neither n nor
+ * d is bounded by LDS.  d3p_energy_score_form(n, rows, d) is the form the entry takes (0: n or d not served);
+ * d3p_energy_score_set_form(form) (a test aid; 0: the rule) forces one and changes no result.
+ * Deterministic: no floating-point atomics, no workspace, no host synchronisation; a row's output bits depend on that row's values, y,
+ * n and d alone -- not on rows, the other rows, ld_draw, ld_row, y_ld, out_ld, the row's position in a workgroup or the form.
+ * D3P_E_INVALID_ARG before any launch: a null pointer, a pointer not aligned to 4 bytes, a dtype other than 0 / 1, n < 1, d < 1,
+ * ld_row < d, ld_draw < rows * ld_row, y_ld < d, out_ld < rows, draws_dev / y_dev / out_dev not device memory.  n >
+ * d3p_energy_score_max_n() = 65535, or more than 2^31 - 1 workgroups: D3P_E_UNSUPPORTED; rows == 0: D3P_OK, no launch. */
+int d3p_energy_score(void* stream, const void* draws_dev, int32_t dtype, int64_t ld_draw, int64_t ld_row, uint32_t n, uint64_t rows, uint32_t d,
+                     const void* y_dev, int64_t y_ld,          /* rows x d words of the draws' dtype */
+                     float* out_dev, int64_t out_ld            /* 4 rows: es, es_fair, mae, spread */);
+/* host only, no device call: the largest n served; the items a side of a pair tile (T); the columns of a staged chunk (C); the rows
+ * one workgroup owns in form 1 / 2 (0: no such form); the form taken at a shape */
+uint32_t d3p_energy_score_max_n(void);
+uint32_t d3p_energy_score_tile_draws(void);
+uint32_t d3p_energy_score_chunk_cols(void);
+uint32_t d3p_energy_score_rows_per_group(int32_t form);
+uint32_t d3p_energy_score_form(uint32_t n, uint64_t rows, uint32_t d);
+int d3p_energy_score_set_form(int32_t form);
+
 #ifdef __cplusplus
 }
 #endif

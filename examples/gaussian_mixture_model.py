@@ -32,6 +32,12 @@ effective sample size, on the training split (Yao et al. 2018: is the trained gu
 CRPS, Gneiting & Raftery 2007) of N_DRAWS posterior predictive draws per point of the test split +- its standard error, with its two
 parts, the mean distance of a draw to the point and the spread of the draws.  It scores the draws a user would ship as synthetic data,
 in the data's own units; smaller is better.
+
+--synthetic-fidelity (off by default; d3p_amd.fidelity) draws ONE synthetic table of the training split's size from the posterior
+predictive and adds two lines: its energy distance (Szekely & Rizzo) to the training and to the test split, and the quantiles of the
+distance to the closest training record, the number of exact copies, the nearest-neighbour adversarial accuracy (Yale et al. 2020; 0.5:
+indistinguishable) against the training and the held-out split and their difference, the privacy loss.  The numbers are functions of
+the private table and are not covered by the accountant.
 """
 import argparse
 import itertools
@@ -116,6 +122,17 @@ def energy_score_report(X_test, params, k, num_draws, seed=4324):
     from d3p_amd.random import debug as threefry
     model = GaussianMixtureModel()
     return energy.posterior_predictive_energy_score(threefry.PRNGKey(seed), num_draws, model, (k, X_test), GaussianMixtureGuide(model), params)
+
+
+def synthetic_fidelity_report(X_train, X_test, params, k, seed=4325):
+    """The FidelityReport (d3p_amd.fidelity) of one synthetic table of X_train's size -- one posterior predictive draw per row --
+    against the training split, with the test split as the holdout."""
+    from d3p_amd import fidelity, mixture
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    return fidelity.fidelity_report(X_train, synthetic, holdout=X_test)
 
 
 def waic_report(X, params, k, num_draws, seed=4322):
@@ -215,6 +232,14 @@ def main(args):
         res = energy_score_report(X_test, params, k, args.energy_score)
         print("held-out energy score (mean over {} points, {} predictive draws): {:.4f} +- {:.4f} (mean distance {:.4f}, spread {:.4f})".format(
             res.n_rows, res.n_draws, float(res.es), float(res.se), float(res.mae), float(res.spread)))
+    if getattr(args, "synthetic_fidelity", False):
+        res = synthetic_fidelity_report(X_train, X_test, params, k)
+        print("synthetic table ({} rows, d = {}): energy distance to train {:.5f} ({} rows), to test {:.5f} ({} rows)".format(
+            res.n_synthetic, res.dim, float(res.energy_train.d2), res.n_train, float(res.energy_holdout.d2), res.n_holdout))
+        print("distance to closest training record: quantiles {} {}, exact copies {}; adversarial accuracy train {:.4f}, held-out {:.4f}, "
+              "privacy loss {:.4f}".format("/".join("{:g}%".format(100 * p) for p in res.dcr_probs),
+                                           "/".join("{:.4f}".format(v) for v in res.dcr_quantiles), res.n_exact_copies, res.aa,
+                                           res.aa_holdout, res.privacy_loss))
     if getattr(args, "waic", False):
         res = waic_report(X_train, params, k, args.posterior_draws)
         print("WAIC ({} points, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
@@ -254,6 +279,9 @@ def parse_args(argv=None):
     parser.add_argument('--energy-score', nargs='?', const=100, default=None, type=int, metavar='N_DRAWS',
                         help='after training, report the energy score (the multivariate CRPS) of N_DRAWS (default 100) posterior '
                              'predictive draws per point of the test split')
+    parser.add_argument('--synthetic-fidelity', action='store_true',
+                        help='after training, draw one synthetic table of the training split\'s size and report its energy distance to the '
+                             'train and test splits, the distance to the closest record and the nearest-neighbour adversarial accuracy')
     return parser.parse_args(argv)
 
 

@@ -1454,6 +1454,53 @@ uint32_t d3p_energy_score_rows_per_group(int32_t form);
 uint32_t d3p_energy_score_form(uint32_t n, uint64_t rows, uint32_t d);
 int d3p_energy_score_set_form(int32_t form);
 
+/* Pair statistics of two tables (model-free; d3p_amd/fidelity.py; d3p_pair_stats.hip); added symbols, ABI 9 unchanged.
+ * What the two-sample energy distance (Szekely & Rizzo), the distance to the closest record and the nearest-neighbour adversarial
+ * accuracy (Yale et al. 2020) of a synthetic table reduce: ONE O(na nb d) walk over the pairs of two tables.
+ * a_dev[i * a_ld + c] is row i < na of the first table in column c < d (column stride 1), b_dev[j * b_ld + c] row j < nb of the second,
+ * both float32 (dtype 0) or both int32 (dtype 1: converted to float32 when staged, which is exact for |v| <= 2^24; the Python layer
+ * refuses larger magnitudes).  Per pair, d3p_energy_score's distance word for word:
+ *   t_c = fl32(a_c - b_c),  q = the float32 fmaf chain over c ascending from 0,  dist = sqrtf(q) correctly rounded
+ * never a Gram matrix.  For row i over the admissible j -- all j < nb, without j == i when exclude_diagonal is 1 (na == nb required);
+ * duplicate rows are pairs like any other --
+ *   sum_dev[i]    = sum_j (double)dist(i, j)   in float64, in the fixed order d3p_pair_stats.hip states, not rounded further
+ *   min_dev[i]    = sqrtf(q_min), q_min the smallest q
+ *   argmin_dev[i] = the SMALLEST j whose q equals q_min (the tie rule is on q, not on the rounded root)
+ * min and argmin are one unsigned 64-bit minimum of (bits(q) << 32) | j: no order to promise.  No admissible j (nb == 1 with the
+ * diagonal excluded): sum = 0, min = +inf, argmin = 0xFFFFFFFF.  A NaN or +-inf element in row i of a makes that row's outputs NaN,
+ * NaN, 0xFFFFFFFF and touches no other row; one anywhere in b does the same to every row (flags taken while staging, never inf - inf);
+ * finite elements whose t_c or q overflows float32 follow IEEE from there (dist = inf, ties at inf to the smallest j).
+ * THE ORDER of a row's sum: the rows of b in tiles of d3p_pair_stats_tile_rows() = 32, the tiles in segments of
+ * d3p_pair_stats_segment_tiles() = 16, tile J of a segment in slot J mod 4; per slot a lane adds its pairs in ascending J, kj fastest,
+ * the 8 lanes of a row meet by the xor butterfly 4, 2, 1; per segment the four slot sums are added in ascending order onto 0, then the
+ * segments in ascending order onto 0.  Two forms over that one order, which agree bit for bit: 1, wide (one workgroup per tile of a
+ * walks every segment; no workspace) and 2, split (one workgroup per tile of a and segment of b writes a float64 sum, a packed minimum
+ * and a flag word per (segment, row) to ws_dev; a second launch adds them in segment order).  d3p_pair_stats_form(na, nb, d) is the form
+ * the entry takes (0: a zero argument): split where the tiles of a alone cannot fill the chip; d3p_pair_stats_set_form(form) (a test
+ * aid; 0: the rule) forces one and changes no result.  d3p_pair_stats_workspace(na, nb, d) is the size that form needs: 0 for the wide
+ * form, where a null ws_dev is fine.  Columns are staged in chunks of d3p_pair_stats_chunk_cols() = 32 in LDS: neither table's length
+ * nor d is bounded by it.
+ * Deterministic: no floating-point atomics, no host synchronisation; repeated calls give equal bits; a row's three outputs depend on that
+ * row's values, b, nb, d and the flag alone -- not on na, the other rows of a, a_ld, b_ld, the row's place in its tile, the form or the
+ * workspace's previous contents.
+ * Checked before any launch, in this order: a null a_dev / b_dev / sum_dev / min_dev / argmin_dev, a pointer not aligned to 4 bytes
+ * (sum_dev, ws_dev: 8), a dtype other than 0 / 1, na < 1, nb < 1, d < 1, a_ld < d, b_ld < d, exclude_diagonal other than 0 / 1 or set with
+ * na != nb: D3P_E_INVALID_ARG; ws_bytes below d3p_pair_stats_workspace (or a null ws_dev where it is not 0): D3P_E_WORKSPACE; more than
+ * 2^31 - 1 workgroups: D3P_E_UNSUPPORTED; last, a table, an output or a needed workspace that is not device memory:
+ * D3P_E_INVALID_ARG. */
+int d3p_pair_stats(void* stream, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld, uint32_t na, uint32_t nb,
+                   uint32_t d, int32_t exclude_diagonal,
+                   double* sum_dev, float* min_dev, uint32_t* argmin_dev,      /* na each */
+                   void* ws_dev, size_t ws_bytes);
+/* host only, no device call: the rows a side of a pair tile (T); the columns of a staged chunk (C); the tiles of b per segment (G); the
+ * form taken at a shape; the workspace that form needs */
+uint32_t d3p_pair_stats_tile_rows(void);
+uint32_t d3p_pair_stats_chunk_cols(void);
+uint32_t d3p_pair_stats_segment_tiles(void);
+uint32_t d3p_pair_stats_form(uint32_t na, uint32_t nb, uint32_t d);
+size_t d3p_pair_stats_workspace(uint32_t na, uint32_t nb, uint32_t d);
+int d3p_pair_stats_set_form(int32_t form);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,12 @@ predictive and adds two lines: its energy distance (Szekely & Rizzo) to the trai
 distance to the closest training record, the number of exact copies, the nearest-neighbour adversarial accuracy (Yale et al. 2020; 0.5:
 indistinguishable) against the training and the held-out split and their difference, the privacy loss.  The numbers are functions of
 the private table and are not covered by the accountant.
+
+--marginal-fidelity [BINS] (off by default; d3p_amd.marginals) draws the same synthetic table and adds two lines of its own: the mean
+and the worst total variation distance of the binned one-way marginals (BINS quantile bins of the training split, default 16) and of
+the two-way marginals with the worst pair of columns, and the mean and largest difference of the pairwise associations (Cramer's V),
+followed by the floor -- what the test split, a fresh sample of the same distribution, scores against the training split.  These too
+are functions of the private table and are not covered by the accountant.
 """
 import argparse
 import itertools
@@ -133,6 +139,17 @@ def synthetic_fidelity_report(X_train, X_test, params, k, seed=4325):
     synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
                                                      params)["obs"][0]
     return fidelity.fidelity_report(X_train, synthetic, holdout=X_test)
+
+
+def marginal_fidelity_report(X_train, X_test, params, k, bins, seed=4325):
+    """The MarginalFidelity (d3p_amd.marginals) of the synthetic table of synthetic_fidelity_report against the training split, cut at
+    the training split's quantiles into `bins` bins, with the test split as the holdout (the noise floor)."""
+    from d3p_amd import marginals, mixture
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    return marginals.marginal_fidelity(X_train, synthetic, bins=bins, holdout=X_test)
 
 
 def waic_report(X, params, k, num_draws, seed=4322):
@@ -240,6 +257,17 @@ def main(args):
               "privacy loss {:.4f}".format("/".join("{:g}%".format(100 * p) for p in res.dcr_probs),
                                            "/".join("{:.4f}".format(v) for v in res.dcr_quantiles), res.n_exact_copies, res.aa,
                                            res.aa_holdout, res.privacy_loss))
+    if getattr(args, "marginal_fidelity", None) is not None:
+        res = marginal_fidelity_report(X_train, X_test, params, k, args.marginal_fidelity)
+        pair = lambda r: "columns {} and {} ({:.4f})".format(r.worst_pairs[0][0][0], r.worst_pairs[0][0][1], r.worst_pairs[0][1]) \
+            if r.worst_pairs else "none"  # noqa: E731
+        print("binned marginals ({} bins, {} columns, {} synthetic rows): 1-way TVD mean {:.4f}, worst column {} ({:.4f}); 2-way TVD mean "
+              "{:.4f}, worst {}".format(args.marginal_fidelity, len(res.columns), res.n_synthetic, res.tvd_one_way_mean, res.worst_columns[0][0],
+                                        res.worst_columns[0][1], res.tvd_two_way_mean, pair(res)))
+        print("association (Cramer's V) difference mean {:.4f}, max {:.4f}; held-out floor ({} rows): 1-way TVD mean {:.4f}, 2-way TVD mean "
+              "{:.4f}, association difference mean {:.4f}".format(res.assoc_diff_mean, res.assoc_diff_max, res.floor.n_synthetic,
+                                                                  res.floor.tvd_one_way_mean, res.floor.tvd_two_way_mean,
+                                                                  res.floor.assoc_diff_mean))
     if getattr(args, "waic", False):
         res = waic_report(X_train, params, k, args.posterior_draws)
         print("WAIC ({} points, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
@@ -282,6 +310,10 @@ def parse_args(argv=None):
     parser.add_argument('--synthetic-fidelity', action='store_true',
                         help='after training, draw one synthetic table of the training split\'s size and report its energy distance to the '
                              'train and test splits, the distance to the closest record and the nearest-neighbour adversarial accuracy')
+    parser.add_argument('--marginal-fidelity', nargs='?', const=16, default=None, type=int, metavar='BINS',
+                        help='after training, draw one synthetic table of the training split\'s size and report the total variation '
+                             'distance of its binned one- and two-way marginals (BINS quantile bins of the training split, default 16) and '
+                             'the difference of the pairwise associations, with the test split\'s scores as the noise floor')
     return parser.parse_args(argv)
 
 

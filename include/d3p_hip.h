@@ -1501,6 +1501,50 @@ uint32_t d3p_pair_stats_form(uint32_t na, uint32_t nb, uint32_t d);
 size_t d3p_pair_stats_workspace(uint32_t na, uint32_t nb, uint32_t d);
 int d3p_pair_stats_set_form(int32_t form);
 
+/* Binned one- and two-way marginal counts of a table (model-free; d3p_amd/marginals.py; d3p_marginals.hip); added symbols,
+ * ABI 9 unchanged.  What the total variation distance of the 1- and 2-way marginals and the pairwise association (Cramer's V) of a
+ * synthetic table against the real one reduce: per column the histogram of its discretised values, per pair of columns i < j their
+ * contingency table, in n d(d - 1)/2 integer increments -- never a one-hot matrix, never a launch per pair.
+ * x_dev[r * ld + c] is row r < n in column c < d (column stride 1), float32 (dtype 0) or int32 (dtype 1: converted to float32 when
+ * staged, which is exact for |v| <= 2^24; the Python layer refuses larger magnitudes).  Column c has nb_c = nbins_dev[c] bins, 1 <= nb_c
+ * <= B, cut by m = nb_c - 1 finite, non-decreasing float32 edges e_k = edges_dev[c * (B - 1) + k], k < m (a d x (B - 1) array; at B = 1
+ * it is never read, but the pointer must still be device memory); B <= d3p_marginals_max_bins() = 32.
+ * THE CODE of a value v in column c: B, the MISSING cell, if v is NaN; otherwise #{k < m : e_k < v}, numpy's searchsorted(e, v,
+ * side="left"): the bins are right-closed, bin 0 holds everything <= e_0 (-inf included), the last bin everything above e_{m-1} (+inf
+ * included), and -0.0 and 0.0 are equal.  THE CELL STRIDE is K = B + 1.  Both outputs are uint32 (n <= 2^32 - 1 fits):
+ *   one_way_dev[c * K + u]           = the number of rows whose code in column c is u
+ *   two_way_dev[(p * K + u) * K + v] = the number of rows with code u in column i and code v in column j, for every pair i < j at the
+ *                                      lexicographic index p = i (2 d - i - 1) / 2 + (j - i - 1)
+ * The entry zeroes both outputs itself; d = 1 has no pairs (two_way_dev may then be null).  The outputs are integers: a function of the
+ * arguments alone, whatever the grid or the order of the atomic adds, and not of ld or of what the workspace held.
+ * SAFETY: nbins_dev and edges_dev are device memory the entry cannot read, so the kernel clamps nb_c into [1, B] and searches at most
+ * B - 1 entries of column c's own slots: every code lies in [0, B] by construction, whatever those arrays hold (unsorted edges give an
+ * unspecified but in-range code).
+ * Two launches: the first writes the uint8 code of every element to ws_dev (column-major, n * d bytes = d3p_marginals_workspace(n, d, B);
+ * every byte read is written in the same call) and adds the one-way counts, a workgroup owning d3p_marginals_code_rows() = 4096 rows of
+ * up to 64 columns; the second gives a workgroup d3p_marginals_pair_tile() = 4 consecutive pairs and a strip of
+ * d3p_marginals_strip_rows() = 32768 rows, counts into replicated uint32 LDS histograms (a lane chooses its replica, which spreads the
+ * lanes that meet on one cell of a skewed column) and adds the strip's non-zero cells to two_way_dev with integer atomicAdd.  No
+ * floating-point atomics, no scratch, no dynamic LDS, no host synchronisation.
+ * Checked before any launch, in this order: a null x_dev / nbins_dev / edges_dev / one_way_dev (and two_way_dev where d > 1), a
+ * pointer not aligned to 4 bytes, a dtype other than 0 / 1, n < 1, d < 1, ld < d, n * ld beyond 63 bits, B outside [1,
+ * d3p_marginals_max_bins()]: D3P_E_INVALID_ARG; ws_bytes below n * d or a null ws_dev: D3P_E_WORKSPACE; a d whose pair tiles times
+ * strips exceed 2^31 - 1 workgroups (which also keeps the pair tables within size_t): D3P_E_UNSUPPORTED; last, a pointer that is not device memory:
+ * D3P_E_INVALID_ARG. */
+int d3p_marginals(void* stream, const void* x_dev, int32_t dtype, int64_t ld, uint32_t n, uint32_t d, uint32_t B,
+                  const uint32_t* nbins_dev,                  /* d */
+                  const float* edges_dev,                     /* d x (B - 1) */
+                  uint32_t* one_way_dev,                      /* d x K */
+                  uint32_t* two_way_dev,                      /* d (d - 1) / 2 x K x K */
+                  void* ws_dev, size_t ws_bytes);
+/* host only, no device call: the largest B; the rows of a strip of the pair walk; the pairs a workgroup holds at once; the rows a
+ * workgroup of the code kernel owns; the workspace in bytes (0: an argument out of range) */
+uint32_t d3p_marginals_max_bins(void);
+uint32_t d3p_marginals_strip_rows(void);
+uint32_t d3p_marginals_pair_tile(void);
+uint32_t d3p_marginals_code_rows(void);
+size_t d3p_marginals_workspace(uint32_t n, uint32_t d, uint32_t B);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libd3p_hip.so")
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip")]
-_DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_outcome.h", "d3p_row_sums.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
+_DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_outcome.h", "d3p_row_sums.h", "d3p_pair_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
 D3P_BATCH_EXPLICIT, D3P_BATCH_FEISTEL, D3P_BATCH_POISSON = 0, 1, 2

@@ -6,7 +6,8 @@
 // converted to float32 when staged, exact for |v| <= 2^24, which is what the Python layer admits); y[r * y_ld + c] the observation.
 // For row r the ITEMS are z_0 .. z_{n-1} (the draws) and z_n = y_r.  For a pair of items (a, b):
 //     t_c = fl32(a_c - b_c)      q = the float32 fmaf chain q <- fmaf(t_c, t_c, q) over c = 0 .. d-1 ascending, from q = 0
-//     dist = sqrtf(q), correctly rounded, widened to float64
+//     dist = the NATIVE root of q (1 ulp, exact on perfect squares; the bound of tests/energy_ref.bound carries it; DESIGN.md 4w's
+//            kernel takes the IEEE root), widened to float64
 // (the chain is symmetric in a and b: t_c only changes its sign).  With U = sum_{i<j<n} dist(z_i, z_j) in float64:
 //     S1 = sum_{i<n} dist(z_i, y)      S2 = 2 U        (each unordered pair is computed once and counted twice)
 //     mae = S1 / n      spread = S2 / (2 n^2)      es = mae - spread      es_fair = mae - S2 / (2 n (n - 1))   (n = 1: 0 / 0 = NaN is the rule)
@@ -24,9 +25,10 @@
 //     the four slots are added in ascending order onto 0.
 // The rows form (1) gives one wavefront a whole row: it walks the four slots one after the other; a workgroup of 4 wavefronts owns
 // R = 16 adjacent rows (at step k its wavefronts hold rows 4 k .. 4 k + 3), so that at d = 2 the workgroup uses every byte of the 128-byte
-// lines it fetches.  The streamed form (2) gives a workgroup one row and wavefront w slot w.  Either form stages the two sides of a pair tile
-// in chunks of C = 32 columns in its wavefront's own LDS (2 x 32 x 36 floats; the row stride 36 keeps the 16-byte reads of the 8 distinct
-// rows of a quarter wave on distinct banks), so neither n nor d is bounded by LDS; the pair accumulators q stay in registers across the
+// lines it fetches.  The streamed form (2) gives a workgroup one row and wavefront w slot w.  Either form walks the tile of
+// d3p_pair_tile.h: the two sides of a pair tile staged in chunks of C = 32 columns in its wavefront's own LDS (2 x 32 x 36 floats; the
+// row stride 36 keeps the 16-byte reads of the 8 distinct rows of a quarter wave on distinct banks), so neither n nor d is bounded by
+// LDS; the pair accumulators q stay in registers across the
 // chunks, which keeps the chain's order.  A chunk is padded with zeros to a multiple of 4 columns: fmaf(0, 0, q) = q for every q >= 0,
 // NaN or inf.  Static LDS: 36944 bytes at most.  No floating-point atomics, no workspace, no host synchronisation, no dynamic LDS.
 //
@@ -37,11 +39,8 @@
 // cancellation loses every digit of the distance (out of scope).
 #include "d3p_device.h"
 #include "d3p_host.h"
+#include "d3p_pair_tile.h"
 
-#define D3P_ES_T 32          // items per side of a pair tile
-#define D3P_ES_C 32          // columns per staged chunk
-#define D3P_ES_LD 36         // LDS row stride in floats (a multiple of 4: the reads are 16 bytes wide)
-#define D3P_ES_WAVES 4       // wavefronts per workgroup = slots
 #define D3P_ES_ROWS 16       // rows per workgroup of the rows form
 #define D3P_ES_MAX_N 65535u
 #define D3P_ES_FORM_ROWS 1
@@ -57,110 +56,65 @@ struct EsArgs {
     float* out; int64_t out_ld;
 };
 
-__device__ __forceinline__ void es_wave_sync()
-{
-    // the wavefront's own LDS: its ds operations complete in issue order; this keeps the compiler from moving them across the point
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ double es_wave_sum(double v)
 {
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
 
-// the 32 items of tile `tile` in columns c0 .. c0 + cw - 1 of row `rowoff`, as raw words: lane -> (item il0 + p * (64 >> lw), column
-// lane & (2^lw - 1)), 2^lw >= cw; an item beyond n and a column beyond cw read nothing and are 0
-__device__ __forceinline__ void es_load(const EsArgs& a, int64_t rowoff, const uint32_t* yrow, uint32_t tile, uint32_t c0, uint32_t cw, int lw,
-                                        int lane, uint32_t (&w)[16])
-{
-    const uint32_t c = (uint32_t)lane & ((1u << lw) - 1u), il0 = (uint32_t)lane >> lw, ipp = 64u >> lw, passes = D3P_ES_T / ipp;
-#pragma unroll
-    for (uint32_t p = 0; p < 16; ++p) {
-        w[p] = 0u;
-        if (p < passes) {
-            const uint32_t item = tile * D3P_ES_T + il0 + p * ipp;
-            if (item <= a.n && c < cw) {
-                const uint32_t* src = item < a.n ? a.z + (int64_t)item * a.ld_draw + rowoff : yrow;
-                w[p] = src[c0 + c];
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void es_store(const EsArgs& a, float* buf, int lw, int lane, const uint32_t (&w)[16], bool& bad)
-{
-    const uint32_t c = (uint32_t)lane & ((1u << lw) - 1u), il0 = (uint32_t)lane >> lw, ipp = 64u >> lw, passes = D3P_ES_T / ipp;
-#pragma unroll
-    for (uint32_t p = 0; p < 16; ++p) {
-        if (p < passes) {
-            const float v = a.dtype ? (float)(int32_t)w[p] : __uint_as_float(w[p]);
-            bad |= !(fabsf(v) <= 3.402823466e38f);   // NaN or +-inf
-            buf[(il0 + p * ipp) * D3P_ES_LD + c] = v;
-        }
-    }
-}
+// the items of row `row`: the n draws, then y as item n
+struct EsItems {
+    typedef uint32_t index;
+    const uint32_t* z; const uint32_t* yrow; int64_t ld_draw; uint32_t n;
+    __device__ __forceinline__ bool live(uint32_t item) const { return item <= n; }
+    __device__ __forceinline__ uint32_t word(uint32_t item, uint32_t col) const { return (item < n ? z + (int64_t)item * ld_draw : yrow)[col]; }
+};
 
 // the tiles of one slot of one row: adds onto the lane's s1 (pairs with y) and u (pairs of draws), ors `bad`
 __device__ __forceinline__ void es_row_slot(const EsArgs& a, uint64_t row, uint32_t slot, float* A, float* Bbuf, int lane, double& s1, double& u,
                                             bool& bad)
 {
-    const int64_t rowoff = (int64_t)row * a.ld_row;
-    const uint32_t* yrow = a.y + (int64_t)row * a.y_ld;
-    const uint32_t nt = (a.n + 1u + D3P_ES_T - 1u) / D3P_ES_T;
+    const EsItems items = {a.z + (int64_t)row * a.ld_row, a.y + (int64_t)row * a.y_ld, a.ld_draw, a.n};
+    const uint32_t nt = (a.n + 1u + D3P_PAIR_T - 1u) / D3P_PAIR_T;
     const uint32_t ti = (uint32_t)lane >> 3, tj = (uint32_t)lane & 7u;
     uint32_t t = 0;
     for (uint32_t I = 0; I < nt; ++I) {
         for (uint32_t J = I; J < nt; ++J, ++t) {
-            if ((t & (D3P_ES_WAVES - 1u)) != slot) continue;
+            if ((t & (D3P_PAIR_WAVES - 1u)) != slot) continue;
             const float* B = I == J ? A : Bbuf;
             float q[4][4];
-#pragma unroll
-            for (int ki = 0; ki < 4; ++ki)
-#pragma unroll
-                for (int kj = 0; kj < 4; ++kj) q[ki][kj] = 0.0f;
-            for (uint32_t c0 = 0; c0 < a.d; c0 += D3P_ES_C) {
-                const uint32_t cw = a.d - c0 < D3P_ES_C ? a.d - c0 : D3P_ES_C;
-                const int lw = cw > 16 ? 5 : cw > 8 ? 4 : cw > 4 ? 3 : 2;
+            pair_zero(q);
+            for (uint32_t c0 = 0; c0 < a.d; c0 += D3P_PAIR_C) {
+                const uint32_t cw = a.d - c0 < D3P_PAIR_C ? a.d - c0 : D3P_PAIR_C;
+                const int lw = pair_lanes_log2(cw);
                 {
                     uint32_t wa[16], wb[16];
-                    es_load(a, rowoff, yrow, I, c0, cw, lw, lane, wa);
-                    if (I != J) es_load(a, rowoff, yrow, J, c0, cw, lw, lane, wb);
-                    es_wave_sync();   // the reads of the chunk before are done
-                    es_store(a, A, lw, lane, wa, bad);
-                    if (I != J) es_store(a, Bbuf, lw, lane, wb, bad);
-                    es_wave_sync();
+                    pair_load(items, I, c0, cw, lw, lane, wa);
+                    if (I != J) pair_load(items, J, c0, cw, lw, lane, wb);
+                    pair_wave_sync();   // the reads of the chunk before are done
+                    pair_store(a.dtype, A, nullptr, lw, lane, wa, bad);
+                    if (I != J) pair_store(a.dtype, Bbuf, nullptr, lw, lane, wb, bad);
+                    pair_wave_sync();
                 }
                 const uint32_t cw4 = (cw + 3u) & ~3u;   // <= 2^lw: every column read below was written above
                 for (uint32_t c = 0; c < cw4; c += 4) {
                     float4 va[4], vb[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        va[k] = *reinterpret_cast<const float4*>(A + (ti + 8u * k) * D3P_ES_LD + c);
-                        vb[k] = *reinterpret_cast<const float4*>(B + (tj + 8u * k) * D3P_ES_LD + c);
+                        va[k] = *reinterpret_cast<const float4*>(A + (ti + 8u * k) * D3P_PAIR_LD + c);
+                        vb[k] = *reinterpret_cast<const float4*>(B + (tj + 8u * k) * D3P_PAIR_LD + c);
                     }
 #pragma unroll
                     for (int ki = 0; ki < 4; ++ki)
 #pragma unroll
-                        for (int kj = 0; kj < 4; ++kj) {
-                            float tt = va[ki].x - vb[kj].x;
-                            float qq = __fmaf_rn(tt, tt, q[ki][kj]);
-                            tt = va[ki].y - vb[kj].y;
-                            qq = __fmaf_rn(tt, tt, qq);
-                            tt = va[ki].z - vb[kj].z;
-                            qq = __fmaf_rn(tt, tt, qq);
-                            tt = va[ki].w - vb[kj].w;
-                            q[ki][kj] = __fmaf_rn(tt, tt, qq);
-                        }
+                        for (int kj = 0; kj < 4; ++kj) q[ki][kj] = pair_chain(va[ki], vb[kj], q[ki][kj]);
                 }
             }
 #pragma unroll
             for (int ki = 0; ki < 4; ++ki)
 #pragma unroll
                 for (int kj = 0; kj < 4; ++kj) {
-                    const uint32_t i = I * D3P_ES_T + ti + 8u * ki, j = J * D3P_ES_T + tj + 8u * kj;
+                    const uint32_t i = I * D3P_PAIR_T + ti + 8u * ki, j = J * D3P_PAIR_T + tj + 8u * kj;
                     const double dist = (double)__fsqrt_rn(q[ki][kj]);
                     const bool pair = i < j && j <= a.n;
                     s1 += pair && j == a.n ? dist : 0.0;
@@ -182,21 +136,21 @@ __device__ __forceinline__ void es_finish(const EsArgs& a, uint64_t row, double 
 }
 
 template <int FORM>
-__global__ __launch_bounds__(64 * D3P_ES_WAVES) void k_energy_score(EsArgs a)
+__global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_energy_score(EsArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[D3P_ES_WAVES][2][D3P_ES_T * D3P_ES_LD];
-    __shared__ double red[D3P_ES_WAVES][2];
-    __shared__ uint32_t red_bad[D3P_ES_WAVES];
+    __shared__ __attribute__((aligned(16))) float lds[D3P_PAIR_WAVES][2][D3P_PAIR_T * D3P_PAIR_LD];
+    __shared__ double red[D3P_PAIR_WAVES][2];
+    __shared__ uint32_t red_bad[D3P_PAIR_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* A = lds[wave][0];
     float* B = lds[wave][1];
     if (FORM == D3P_ES_FORM_ROWS) {
-        for (uint32_t k = 0; k < D3P_ES_ROWS / D3P_ES_WAVES; ++k) {
-            const uint64_t row = (uint64_t)blockIdx.x * D3P_ES_ROWS + k * D3P_ES_WAVES + (uint32_t)wave;
+        for (uint32_t k = 0; k < D3P_ES_ROWS / D3P_PAIR_WAVES; ++k) {
+            const uint64_t row = (uint64_t)blockIdx.x * D3P_ES_ROWS + k * D3P_PAIR_WAVES + (uint32_t)wave;
             if (row >= a.rows) break;   // (wave-uniform; nothing below synchronises the workgroup)
             double S1 = 0.0, U = 0.0;
             bool bad = false;
-            for (uint32_t slot = 0; slot < D3P_ES_WAVES; ++slot) {
+            for (uint32_t slot = 0; slot < D3P_PAIR_WAVES; ++slot) {
                 double s1 = 0.0, u = 0.0;
                 es_row_slot(a, row, slot, A, B, lane, s1, u, bad);
                 S1 += es_wave_sum(s1);
@@ -218,7 +172,7 @@ __global__ __launch_bounds__(64 * D3P_ES_WAVES) void k_energy_score(EsArgs a)
         if (threadIdx.x == 0) {
             double S1 = 0.0, U = 0.0;
             uint32_t any = 0u;
-            for (int w = 0; w < D3P_ES_WAVES; ++w) { S1 += red[w][0]; U += red[w][1]; any |= red_bad[w]; }
+            for (int w = 0; w < D3P_PAIR_WAVES; ++w) { S1 += red[w][0]; U += red[w][1]; any |= red_bad[w]; }
             es_finish(a, row, S1, U, any != 0u);
         }
     }
@@ -241,9 +195,9 @@ extern "C" {
 
 uint32_t d3p_energy_score_max_n(void) { return D3P_ES_MAX_N; }
 
-uint32_t d3p_energy_score_tile_draws(void) { return D3P_ES_T; }
+uint32_t d3p_energy_score_tile_draws(void) { return D3P_PAIR_T; }
 
-uint32_t d3p_energy_score_chunk_cols(void) { return D3P_ES_C; }
+uint32_t d3p_energy_score_chunk_cols(void) { return D3P_PAIR_C; }
 
 uint32_t d3p_energy_score_rows_per_group(int32_t form)
 {
@@ -290,9 +244,9 @@ int d3p_energy_score(void* stream, const void* draws_dev, int32_t dtype, int64_t
     a.z = static_cast<const uint32_t*>(draws_dev); a.y = static_cast<const uint32_t*>(y_dev); a.dtype = dtype; a.ld_draw = ld_draw;
     a.ld_row = ld_row; a.y_ld = y_ld; a.n = n; a.rows = rows; a.d = d; a.out = out_dev; a.out_ld = out_ld;
     if (form == D3P_ES_FORM_ROWS)
-        hipLaunchKernelGGL(k_energy_score<D3P_ES_FORM_ROWS>, dim3((unsigned)groups), dim3(64 * D3P_ES_WAVES), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(k_energy_score<D3P_ES_FORM_ROWS>, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(k_energy_score<D3P_ES_FORM_STREAM>, dim3((unsigned)groups), dim3(64 * D3P_ES_WAVES), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(k_energy_score<D3P_ES_FORM_STREAM>, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
     return check_launch(what);
 }
 

@@ -9,7 +9,7 @@
 // For a pair of rows (i, j):
 //     t_c = fl32(a_c - b_c)      q = the float32 fmaf chain q <- fmaf(t_c, t_c, q) over c = 0 .. d-1 ascending, from q = 0
 //     dist = sqrtf(q), correctly rounded (the IEEE root: ps_sqrt below, not the native instruction's 1 ulp)
-// which is the distance of d3p_energy.hip word for word.  The ADMISSIBLE j of row i are all j < nb, without j == i when
+// which is the chain of d3p_energy.hip: both walk the tile of d3p_pair_tile.h.  The ADMISSIBLE j of row i are all j < nb, without j == i when
 // exclude_diagonal is set (which requires na == nb); duplicate rows are pairs like any other.  Over the admissible j:
 //     sum[i]    = sum_j (double)dist(i, j)     in float64, in the order below, not rounded further
 //     min[i]    = sqrtf(q_min),  q_min the smallest q
@@ -47,11 +47,8 @@
 // cancellation loses every digit of the distance, and the nearest record is exactly where that happens.
 #include "d3p_device.h"
 #include "d3p_host.h"
+#include "d3p_pair_tile.h"
 
-#define D3P_PS_T 32          // rows per side of a pair tile
-#define D3P_PS_C 32          // columns per staged chunk
-#define D3P_PS_LD 36         // LDS row stride in floats (a multiple of 4: the reads are 16 bytes wide)
-#define D3P_PS_WAVES 4       // wavefronts per workgroup = slots
 #define D3P_PS_G 16          // tiles of b per segment (a multiple of the slots)
 #define D3P_PS_FORM_WIDE 1
 #define D3P_PS_FORM_SPLIT 2
@@ -69,109 +66,64 @@ struct PsArgs {
     double* ws_sum; unsigned long long* ws_min; uint32_t* ws_flag;
 };
 
-__device__ __forceinline__ void ps_wave_sync()
-{
-    // the wavefront's own LDS: its ds operations complete in issue order; this keeps the compiler from moving them across the point
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the 32 rows of tile `tile` of a table in columns c0 .. c0 + cw - 1, as raw words: lane -> (row il0 + p * (64 >> lw), column
-// lane & (2^lw - 1)), 2^lw >= cw; a row beyond n and a column beyond cw read nothing and are 0
-__device__ __forceinline__ void ps_load(const uint32_t* base, int64_t ld, uint32_t n, uint32_t tile, uint32_t c0, uint32_t cw, int lw, int lane,
-                                        uint32_t (&w)[16])
-{
-    const uint32_t c = (uint32_t)lane & ((1u << lw) - 1u), il0 = (uint32_t)lane >> lw, ipp = 64u >> lw, passes = D3P_PS_T / ipp;
-#pragma unroll
-    for (uint32_t p = 0; p < 16; ++p) {
-        w[p] = 0u;
-        if (p < passes) {
-            const uint64_t row = (uint64_t)tile * D3P_PS_T + il0 + p * ipp;
-            if (row < n && c < cw) w[p] = base[(int64_t)row * ld + c0 + c];
-        }
-    }
-}
-
-// stores the chunk and takes the flags: `bad` for the whole chunk, and with rowflag a word per row (every lane that sets one stores 1)
-__device__ __forceinline__ void ps_store(int32_t dtype, float* buf, uint32_t* rowflag, int lw, int lane, const uint32_t (&w)[16], bool& bad)
-{
-    const uint32_t c = (uint32_t)lane & ((1u << lw) - 1u), il0 = (uint32_t)lane >> lw, ipp = 64u >> lw, passes = D3P_PS_T / ipp;
-#pragma unroll
-    for (uint32_t p = 0; p < 16; ++p) {
-        if (p < passes) {
-            const float v = dtype ? (float)(int32_t)w[p] : __uint_as_float(w[p]);
-            const bool nf = !(fabsf(v) <= 3.402823466e38f);   // NaN or +-inf
-            bad |= nf;
-            if (rowflag && nf) rowflag[il0 + p * ipp] = 1u;
-            buf[(il0 + p * ipp) * D3P_PS_LD + c] = v;
-        }
-    }
-}
+// the items of one table: its n rows
+struct PsItems {
+    typedef uint64_t index;
+    const uint32_t* base; int64_t ld; uint32_t n;
+    __device__ __forceinline__ bool live(uint64_t row) const { return row < n; }
+    __device__ __forceinline__ uint32_t word(uint64_t row, uint32_t col) const { return base[(int64_t)row * ld + col]; }
+};
 
 // the IEEE root.  sqrtf is correctly rounded under the compiler's default -fhip-fp32-correctly-rounded-divide-sqrt; the rounded-root
 // intrinsic of this toolchain's headers is the NATIVE instruction (1 ulp) unless OCML_BASIC_ROUNDED_OPERATIONS is defined, which the
 // by-value tests of non-square q tell apart
 __device__ __forceinline__ float ps_sqrt(float q) { return __builtin_sqrtf(q); }
 
-__device__ __forceinline__ int ps_lanes_log2(uint32_t cw) { return cw > 16 ? 5 : cw > 8 ? 4 : cw > 4 ? 3 : 2; }
-
 // the tiles of one slot of one segment against tile I of a: adds onto the lane's four sums, lowers its four packed minima, ors bad_b.
 // With a_resident (d <= C) tile I of a already lies in A.
 __device__ __forceinline__ void ps_segment_slot(const PsArgs& a, uint32_t I, uint32_t seg, uint32_t slot, float* A, float* B, uint32_t* aflag,
                                                 bool a_resident, int lane, double (&ls)[4], unsigned long long (&pm)[4], bool& bad_b)
 {
-    const uint32_t ntb = (uint32_t)(((uint64_t)a.nb + D3P_PS_T - 1u) / D3P_PS_T);
+    const uint32_t ntb = (uint32_t)(((uint64_t)a.nb + D3P_PAIR_T - 1u) / D3P_PAIR_T);
     const uint32_t j_lo = seg * D3P_PS_G, j_hi = ntb - j_lo < D3P_PS_G ? ntb : j_lo + D3P_PS_G;
     const uint32_t ti = (uint32_t)lane >> 3, tj = (uint32_t)lane & 7u;
     bool bad_a = false;   // (the rows' flags go to aflag)
-    for (uint32_t J = j_lo + slot; J < j_hi; J += D3P_PS_WAVES) {
+    const PsItems rows_a = {a.a, a.a_ld, a.na}, rows_b = {a.b, a.b_ld, a.nb};
+    for (uint32_t J = j_lo + slot; J < j_hi; J += D3P_PAIR_WAVES) {
         float q[4][4];
-#pragma unroll
-        for (int ki = 0; ki < 4; ++ki)
-#pragma unroll
-            for (int kj = 0; kj < 4; ++kj) q[ki][kj] = 0.0f;
-        for (uint32_t c0 = 0; c0 < a.d; c0 += D3P_PS_C) {
-            const uint32_t cw = a.d - c0 < D3P_PS_C ? a.d - c0 : D3P_PS_C;
-            const int lw = ps_lanes_log2(cw);
+        pair_zero(q);
+        for (uint32_t c0 = 0; c0 < a.d; c0 += D3P_PAIR_C) {
+            const uint32_t cw = a.d - c0 < D3P_PAIR_C ? a.d - c0 : D3P_PAIR_C;
+            const int lw = pair_lanes_log2(cw);
             {
                 uint32_t wa[16], wb[16];
-                if (!a_resident) ps_load(a.a, a.a_ld, a.na, I, c0, cw, lw, lane, wa);
-                ps_load(a.b, a.b_ld, a.nb, J, c0, cw, lw, lane, wb);
-                ps_wave_sync();   // the reads of the chunk before are done
-                if (!a_resident) ps_store(a.dtype, A, aflag, lw, lane, wa, bad_a);
-                ps_store(a.dtype, B, nullptr, lw, lane, wb, bad_b);
-                ps_wave_sync();
+                if (!a_resident) pair_load(rows_a, I, c0, cw, lw, lane, wa);
+                pair_load(rows_b, J, c0, cw, lw, lane, wb);
+                pair_wave_sync();   // the reads of the chunk before are done
+                if (!a_resident) pair_store(a.dtype, A, aflag, lw, lane, wa, bad_a);
+                pair_store(a.dtype, B, nullptr, lw, lane, wb, bad_b);
+                pair_wave_sync();
             }
             const uint32_t cw4 = (cw + 3u) & ~3u;   // <= 2^lw: every column read below was written above
             for (uint32_t c = 0; c < cw4; c += 4) {
                 float4 va[4], vb[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    va[k] = *reinterpret_cast<const float4*>(A + (ti + 8u * k) * D3P_PS_LD + c);
-                    vb[k] = *reinterpret_cast<const float4*>(B + (tj + 8u * k) * D3P_PS_LD + c);
+                    va[k] = *reinterpret_cast<const float4*>(A + (ti + 8u * k) * D3P_PAIR_LD + c);
+                    vb[k] = *reinterpret_cast<const float4*>(B + (tj + 8u * k) * D3P_PAIR_LD + c);
                 }
 #pragma unroll
                 for (int ki = 0; ki < 4; ++ki)
 #pragma unroll
-                    for (int kj = 0; kj < 4; ++kj) {
-                        float tt = va[ki].x - vb[kj].x;
-                        float qq = __fmaf_rn(tt, tt, q[ki][kj]);
-                        tt = va[ki].y - vb[kj].y;
-                        qq = __fmaf_rn(tt, tt, qq);
-                        tt = va[ki].z - vb[kj].z;
-                        qq = __fmaf_rn(tt, tt, qq);
-                        tt = va[ki].w - vb[kj].w;
-                        q[ki][kj] = __fmaf_rn(tt, tt, qq);
-                    }
+                    for (int kj = 0; kj < 4; ++kj) q[ki][kj] = pair_chain(va[ki], vb[kj], q[ki][kj]);
             }
         }
 #pragma unroll
         for (int ki = 0; ki < 4; ++ki) {
-            const uint64_t i = (uint64_t)I * D3P_PS_T + ti + 8u * ki;
+            const uint64_t i = (uint64_t)I * D3P_PAIR_T + ti + 8u * ki;
 #pragma unroll
             for (int kj = 0; kj < 4; ++kj) {
-                const uint64_t j = (uint64_t)J * D3P_PS_T + tj + 8u * kj;
+                const uint64_t j = (uint64_t)J * D3P_PAIR_T + tj + 8u * kj;
                 const bool ok = j < a.nb && !(a.excl && j == i);
                 const float qv = q[ki][kj];
                 const double dist = (double)ps_sqrt(qv);
@@ -209,13 +161,13 @@ __device__ __forceinline__ void ps_finish(const PsArgs& a, uint64_t i, double to
 }
 
 template <int FORM>
-__global__ __launch_bounds__(64 * D3P_PS_WAVES) void k_pair_stats(PsArgs a)
+__global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_stats(PsArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[D3P_PS_WAVES][2][D3P_PS_T * D3P_PS_LD];
-    __shared__ double slot_sum[2][D3P_PS_WAVES][D3P_PS_T];
-    __shared__ unsigned long long slot_min[D3P_PS_WAVES][D3P_PS_T];
-    __shared__ uint32_t slot_aflag[D3P_PS_WAVES][D3P_PS_T];
-    __shared__ uint32_t slot_bflag[D3P_PS_WAVES];
+    __shared__ __attribute__((aligned(16))) float lds[D3P_PAIR_WAVES][2][D3P_PAIR_T * D3P_PAIR_LD];
+    __shared__ double slot_sum[2][D3P_PAIR_WAVES][D3P_PAIR_T];
+    __shared__ unsigned long long slot_min[D3P_PAIR_WAVES][D3P_PAIR_T];
+    __shared__ uint32_t slot_aflag[D3P_PAIR_WAVES][D3P_PAIR_T];
+    __shared__ uint32_t slot_bflag[D3P_PAIR_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t ti = (uint32_t)lane >> 3, tj = (uint32_t)lane & 7u;
     float* A = lds[wave][0];
@@ -224,17 +176,17 @@ __global__ __launch_bounds__(64 * D3P_PS_WAVES) void k_pair_stats(PsArgs a)
     const uint32_t I = FORM == D3P_PS_FORM_WIDE ? blockIdx.x : blockIdx.x / a.nseg;
     const uint32_t seg_lo = FORM == D3P_PS_FORM_WIDE ? 0u : blockIdx.x % a.nseg;
     const uint32_t seg_hi = FORM == D3P_PS_FORM_WIDE ? a.nseg : seg_lo + 1u;
-    if (lane < D3P_PS_T) aflag[lane] = 0u;
-    ps_wave_sync();
-    const bool a_resident = a.d <= D3P_PS_C;
+    if (lane < D3P_PAIR_T) aflag[lane] = 0u;
+    pair_wave_sync();
+    const bool a_resident = a.d <= D3P_PAIR_C;
     bool bad_b = false;
     if (a_resident) {   // one chunk: tile I of a is staged once, by every wavefront for itself
-        const int lw = ps_lanes_log2(a.d);
+        const int lw = pair_lanes_log2(a.d);
         uint32_t wa[16];
         bool bad_a = false;
-        ps_load(a.a, a.a_ld, a.na, I, 0u, a.d, lw, lane, wa);
-        ps_store(a.dtype, A, aflag, lw, lane, wa, bad_a);
-        ps_wave_sync();
+        pair_load(PsItems{a.a, a.a_ld, a.na}, I, 0u, a.d, lw, lane, wa);
+        pair_store(a.dtype, A, aflag, lw, lane, wa, bad_a);
+        pair_wave_sync();
     }
     unsigned long long pm[4] = {D3P_PS_NONE, D3P_PS_NONE, D3P_PS_NONE, D3P_PS_NONE};
     double total = 0.0;   // (threads 0 .. 31: row 32 I + threadIdx.x)
@@ -249,9 +201,9 @@ __global__ __launch_bounds__(64 * D3P_PS_WAVES) void k_pair_stats(PsArgs a)
         }
         // one barrier per segment: the sums of segment s + 2 are written after the barrier of segment s + 1, which follows the reads below
         __syncthreads();
-        if (threadIdx.x < D3P_PS_T) {
+        if (threadIdx.x < D3P_PAIR_T) {
             double s = 0.0;
-            for (int w = 0; w < D3P_PS_WAVES; ++w) s += slot_sum[par][w][threadIdx.x];
+            for (int w = 0; w < D3P_PAIR_WAVES; ++w) s += slot_sum[par][w][threadIdx.x];
             total += s;
         }
     }
@@ -263,12 +215,12 @@ __global__ __launch_bounds__(64 * D3P_PS_WAVES) void k_pair_stats(PsArgs a)
     bad_b = __builtin_amdgcn_ballot_w64(bad_b) != 0ull;
     if (lane == 0) slot_bflag[wave] = bad_b ? 1u : 0u;
     __syncthreads();
-    if (threadIdx.x < D3P_PS_T) {
-        const uint64_t i = (uint64_t)I * D3P_PS_T + threadIdx.x;
+    if (threadIdx.x < D3P_PAIR_T) {
+        const uint64_t i = (uint64_t)I * D3P_PAIR_T + threadIdx.x;
         if (i < a.na) {
             unsigned long long key = D3P_PS_NONE;
             uint32_t fa = 0u, fb = 0u;
-            for (int w = 0; w < D3P_PS_WAVES; ++w) {
+            for (int w = 0; w < D3P_PAIR_WAVES; ++w) {
                 key = slot_min[w][threadIdx.x] < key ? slot_min[w][threadIdx.x] : key;
                 fa |= slot_aflag[w][threadIdx.x];
                 fb |= slot_bflag[w];
@@ -302,7 +254,7 @@ __global__ __launch_bounds__(256) void k_pair_stats_merge(PsArgs a)
     ps_finish(a, i, total, key, flags != 0u);
 }
 
-static uint32_t ps_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + D3P_PS_T - 1u) / D3P_PS_T); }
+static uint32_t ps_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + D3P_PAIR_T - 1u) / D3P_PAIR_T); }
 
 static uint32_t ps_segments(uint32_t nb) { return (ps_tiles(nb) + D3P_PS_G - 1u) / D3P_PS_G; }
 
@@ -327,9 +279,9 @@ using namespace d3p;
 
 extern "C" {
 
-uint32_t d3p_pair_stats_tile_rows(void) { return D3P_PS_T; }
+uint32_t d3p_pair_stats_tile_rows(void) { return D3P_PAIR_T; }
 
-uint32_t d3p_pair_stats_chunk_cols(void) { return D3P_PS_C; }
+uint32_t d3p_pair_stats_chunk_cols(void) { return D3P_PAIR_C; }
 
 uint32_t d3p_pair_stats_segment_tiles(void) { return D3P_PS_G; }
 
@@ -383,10 +335,10 @@ int d3p_pair_stats(void* stream, const void* a_dev, const void* b_dev, int32_t d
     a.ws_min = need ? reinterpret_cast<unsigned long long*>(static_cast<char*>(ws_dev) + 8u * cells) : nullptr;
     a.ws_flag = need ? reinterpret_cast<uint32_t*>(static_cast<char*>(ws_dev) + 16u * cells) : nullptr;
     if (form == D3P_PS_FORM_WIDE) {
-        hipLaunchKernelGGL(k_pair_stats<D3P_PS_FORM_WIDE>, dim3((unsigned)groups), dim3(64 * D3P_PS_WAVES), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(k_pair_stats<D3P_PS_FORM_WIDE>, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
         return check_launch(what);
     }
-    hipLaunchKernelGGL(k_pair_stats<D3P_PS_FORM_SPLIT>, dim3((unsigned)groups), dim3(64 * D3P_PS_WAVES), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_pair_stats<D3P_PS_FORM_SPLIT>, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
     const int rc = check_launch(what);
     if (rc != D3P_OK) return rc;
     hipLaunchKernelGGL(k_pair_stats_merge, dim3((unsigned)(((uint64_t)na + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, a);

@@ -1422,7 +1422,8 @@ int d3p_binary_curve(void* stream, const float* p_dev, const int32_t* y_dev, uin
  * draws_dev[s * ld_draw + r * ld_row + c] is draw s < n of row r < rows in column c < d (column stride 1), float32 (dtype 0) or int32
  * (dtype 1: converted to float32 when staged, which is exact for |v| <= 2^24; the Python layer refuses larger magnitudes);
  * y_dev[r * y_ld + c] the observation, of the same dtype.  For row r the items are z_0 .. z_{n-1} (the draws) and z_n = y_r; per pair
- *   t_c = fl32(a_c - b_c),  q = the float32 fmaf chain over c ascending from 0,  dist = sqrtf(q) correctly rounded, widened to float64
+ *   t_c = fl32(a_c - b_c),  q = the float32 fmaf chain over c ascending from 0,  dist = the native root of q, widened to float64
+ * (1 ulp, exact on perfect squares; the bound of tests/energy_ref.bound carries it; d3p_pair_stats below takes the IEEE root)
  * and with S1 = sum_i dist(z_i, y), S2 = sum_{i != j} dist(z_i, z_j) in float64 in the fixed order d3p_energy.hip states (each
  * unordered pair computed once, counted twice):
  *   out_dev[0 * out_ld + r] = es      = mae - spread
@@ -1459,7 +1460,7 @@ int d3p_energy_score_set_form(int32_t form);
  * accuracy (Yale et al. 2020) of a synthetic table reduce: ONE O(na nb d) walk over the pairs of two tables.
  * a_dev[i * a_ld + c] is row i < na of the first table in column c < d (column stride 1), b_dev[j * b_ld + c] row j < nb of the second,
  * both float32 (dtype 0) or both int32 (dtype 1: converted to float32 when staged, which is exact for |v| <= 2^24; the Python layer
- * refuses larger magnitudes).  Per pair, d3p_energy_score's distance word for word:
+ * refuses larger magnitudes).  Per pair, d3p_energy_score's chain (both walk the tile of d3p_pair_tile.h) and the IEEE root:
  *   t_c = fl32(a_c - b_c),  q = the float32 fmaf chain over c ascending from 0,  dist = sqrtf(q) correctly rounded
  * never a Gram matrix.  For row i over the admissible j -- all j < nb, without j == i when exclude_diagonal is 1 (na == nb required);
  * duplicate rows are pairs like any other --

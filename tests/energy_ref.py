@@ -62,17 +62,23 @@ def _dist64(a, b):
     return np.sqrt((t * t).sum(axis=1))
 
 
-def _dist32(a, b):
-    """The kernel's rule: t_c = fl32(a_c - b_c), q <- fmaf(t_c, t_c, q) over c ascending, sqrtf.  fmaf is formed as the float64 t * t
-    (exact: 48 bits) plus q rounded to float64 and then to float32; the double rounding can differ from a true fmaf by one float32 ulp in
-    rare ties, which is inside the bound and immaterial to the exact cases."""
+def _q32(a, b):
+    """The kernel's chain over the last axis of a and b (which broadcast against each other): t_c = fl32(a_c - b_c), q <- fmaf(t_c, t_c, q)
+    over c ascending; the root is taken where q is used.  fmaf is formed as the float64 t * t (exact: 48 bits) plus q rounded to float64
+    and then to float32; the double rounding can differ from a true fmaf by one float32 ulp in rare ties, which is inside the bound and
+    immaterial to the exact cases."""
     with np.errstate(all="ignore"):
         a32, b32 = a.astype(np.float32), b.astype(np.float32)
-        q = np.zeros(max(a32.shape[0], b32.shape[0]), np.float32)
-        for c in range(a32.shape[1]):
-            t = (a32[:, c] - b32[:, c]).astype(np.float32)
+        q = np.zeros(np.broadcast_shapes(a32.shape[:-1], b32.shape[:-1]), np.float32)
+        for c in range(a32.shape[-1]):
+            t = (a32[..., c] - b32[..., c]).astype(np.float32)
             q = (t.astype(np.float64) * t.astype(np.float64) + q.astype(np.float64)).astype(np.float32)
-        return np.sqrt(q).astype(np.float32).astype(np.float64)
+        return q
+
+
+def _dist32(a, b):
+    with np.errstate(all="ignore"):
+        return np.sqrt(_q32(a, b)).astype(np.float32).astype(np.float64)
 
 
 def exact(draws, y):

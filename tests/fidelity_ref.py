@@ -1,7 +1,6 @@
 """Comparator of the pair statistics and the fidelity report (d3p_amd/fidelity.py, d3p_amd/csrc/d3p_pair_stats.hip; DESIGN.md section
-4w): a numpy float64 restatement with math.fsum sums and exact minima, a float32 emulation of the kernel's distance rule formed as
-tests/energy_ref.py forms it, the derived error bound, and the report restated on given per-row statistics.  Nothing here reaches a
-device.
+4w): a numpy float64 restatement with math.fsum sums and exact minima, a float32 emulation of the kernel's distance rule by the chain of
+tests/energy_ref.py, the derived error bound, and the report restated on given per-row statistics.  Nothing here reaches a device.
 
     exact(a, b, exclude_diagonal=False)    -> {"sum": (na,) float64 (fsum), "min": (na,) float64, "argmin": (na,) int64, "dist": (na, nb)}
     emulate(a, b, exclude_diagonal=False)  -> {"sum": float64 (fsum of the float32 distances), "min": float32, "argmin": int64}: the
@@ -14,7 +13,7 @@ import math
 
 import numpy as np
 
-from tests.energy_ref import U32, U64, _fsum, _half_ulp32
+from tests.energy_ref import U32, U64, _fsum, _half_ulp32, _q32
 
 NONE = -1
 
@@ -46,19 +45,6 @@ def _q64(a, b):
     return q
 
 
-def _q32(a, b):
-    """The kernel's chain: t_c = fl32(a_c - b_c), q <- fmaf(t_c, t_c, q) over c ascending.  fmaf is formed as in energy_ref._dist32: the
-    float64 t * t (exact: 48 bits) plus q rounded to float64 and then to float32; the double rounding can differ from a true fmaf by one
-    float32 ulp in rare ties, which is inside the bound and immaterial to the exact cases."""
-    with np.errstate(all="ignore"):
-        a32, b32 = a.astype(np.float32), b.astype(np.float32)
-        q = np.zeros((a.shape[0], b.shape[0]), np.float32)
-        for c in range(a32.shape[1]):
-            t = (a32[:, c][:, None] - b32[:, c][None, :]).astype(np.float32)
-            q = (t.astype(np.float64) * t.astype(np.float64) + q.astype(np.float64)).astype(np.float32)
-        return q
-
-
 def _reduce(q, dist, ok, bad, min_dtype):
     na = q.shape[0]
     out = {"sum": np.zeros(na, np.float64), "min": np.full(na, np.inf, min_dtype), "argmin": np.full(na, NONE, np.int64)}
@@ -88,7 +74,7 @@ def exact(a, b, exclude_diagonal=False):
 def emulate(a, b, exclude_diagonal=False):
     a, b = _as2(a), _as2(b)
     with np.errstate(all="ignore"):
-        q = _q32(a, b)
+        q = _q32(a[:, None, :], b[None, :, :])
         dist = np.sqrt(q).astype(np.float32)
     return _reduce(q, dist.astype(np.float64), _admissible(a.shape[0], b.shape[0], exclude_diagonal), _bad_rows(a, b), np.float32)
 

@@ -216,18 +216,24 @@ def test_python_layer_refuses_before_the_device(no_device):
 def test_source_text_rules():
     csrc = os.path.join(ROOT, "d3p_amd", "csrc")
     text = open(os.path.join(csrc, "d3p_energy.hip")).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ["d3p_device.h", "d3p_host.h"]
+    tile = open(os.path.join(csrc, "d3p_pair_tile.h")).read()          # the 32 x 32 pair tile, shared with d3p_pair_stats.hip
+    assert re.findall(r'#include "([^"]+)"', text) == ["d3p_device.h", "d3p_host.h", "d3p_pair_tile.h"]
     code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    tile_code = "\n".join(line.split("//")[0] for line in tile.splitlines())
     for banned in ("hipFuncSetAttribute", "147456", "atomic", "hipMalloc", "hipStreamSynchronize", "hipDeviceSynchronize", "hipMemcpy",
                    "mfma", "extern __shared__", "workspace"):
-        assert banned not in code, banned
+        assert banned not in code and banned not in tile_code, banned
     header = text[:text.index("#include")]
     for said in ("THE RULE", "THE ORDER", "DETERMINISM", "fmaf chain", "2^24", "follow IEEE", "NaN or +-inf", "bit for bit", "Gram matrix"):
         assert said in header, said
-    assert "__fmaf_rn(" in code and "__fsqrt_rn(" in code and "sqrtf(" not in code.replace("__fsqrt_rn(", "")
-    lds = int(re.search(r"#define D3P_ES_T (\d+)", text).group(1)) * int(re.search(r"#define D3P_ES_LD (\d+)", text).group(1)) * 4 * 2 \
-        * int(re.search(r"#define D3P_ES_WAVES (\d+)", text).group(1))
+    # the chain is the tile's (tests/test_fidelity_host.py pins its text there); the root is this file's own
+    assert tile_code.count("__fmaf_rn(") == 4 and "__fmaf_rn(" not in code and "pair_chain(" in code
+    assert "__fsqrt_rn(" in code and "sqrtf(" not in code.replace("__fsqrt_rn(", "") and "sqrt" not in tile_code
+    assert not re.search(r"#define D3P_(ES|PS)_(T|C|LD|WAVES)\b", text)
+    num = {k: int(re.search(r"#define D3P_PAIR_" + k + r" (\d+)", tile).group(1)) for k in ("T", "C", "LD", "WAVES")}
+    lds = num["T"] * num["LD"] * 4 * 2 * num["WAVES"]
     assert lds + 1024 <= 64 * 1024                                    # static LDS stays below 64 KiB
+    assert lds + num["WAVES"] * (2 * 8 + 4) == 36944 and "Static LDS: 36944 bytes at most" in header
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design[design.index("4v."):]
     for said in ("Gram", "variogram", "rank histogram", "PSIS", "VGPR", "bit for bit"):

@@ -196,26 +196,34 @@ def test_python_layer_refuses_before_the_device(no_device):
 def test_source_text_rules():
     csrc = os.path.join(ROOT, "d3p_amd", "csrc")
     text = open(os.path.join(csrc, "d3p_pair_stats.hip")).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ["d3p_device.h", "d3p_host.h"]
+    tile = open(os.path.join(csrc, "d3p_pair_tile.h")).read()          # the 32 x 32 pair tile, shared with d3p_energy.hip
+    assert re.findall(r'#include "([^"]+)"', text) == ["d3p_device.h", "d3p_host.h", "d3p_pair_tile.h"]
     code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    tile_code = "\n".join(line.split("//")[0] for line in tile.splitlines())
     for banned in ("hipFuncSetAttribute", "147456", "atomic", "hipMalloc", "hipStreamSynchronize", "hipDeviceSynchronize", "hipMemcpy", "mfma",
                    "extern __shared__", "d3p_row_sums.h", "d3p_colreduce.h"):
-        assert banned not in code, banned
+        assert banned not in code and banned not in tile_code, banned
     header = text[:text.index("#include")]
     for said in ("THE RULE", "THE ORDER", "DETERMINISM", "fmaf chain", "2^24", "follow IEEE", "NaN or +-inf", "bit for bit", "Gram matrix",
                  "SMALLEST j", "(bits(q) << 32) | j", "0xFFFFFFFF", "J mod 4", "butterfly 4, 2, 1", "ascending segment order", "exclude_diagonal",
                  "not on na", "the form"):
         assert said in header, said
     # the IEEE root: this toolchain's __fsqrt_rn is the native instruction (1 ulp) unless OCML_BASIC_ROUNDED_OPERATIONS is defined
-    assert "__fmaf_rn(" in code and code.count("sqrtf(") == 1 and "__builtin_sqrtf(q)" in code and "__fsqrt_rn" not in code
-    assert "native" not in code and "fast" not in code
-    num = {k: int(re.search(r"#define D3P_PS_" + k + r" (\d+)", text).group(1)) for k in ("T", "C", "LD", "WAVES", "G")}
+    assert code.count("sqrtf(") == 1 and "__builtin_sqrtf(q)" in code and "__fsqrt_rn" not in code and "sqrt" not in tile_code
+    assert "native" not in code and "fast" not in code and "native" not in tile_code and "fast" not in tile_code
+    num = {k: int(re.search(r"#define D3P_PAIR_" + k + r" (\d+)", tile).group(1)) for k in ("T", "C", "LD", "WAVES")}
+    num["G"] = int(re.search(r"#define D3P_PS_G (\d+)", text).group(1))
     lds = num["T"] * num["LD"] * 4 * 2 * num["WAVES"] + num["T"] * num["WAVES"] * (2 * 8 + 8 + 4) + 4 * num["WAVES"]
     assert f"Static LDS: {lds} bytes" in header and lds < 64 * 1024          # static LDS stays below 64 KiB
     assert num["G"] % num["WAVES"] == 0 and num["LD"] % 4 == 0 and num["LD"] >= num["C"]
+    # the distance of d3p_energy.hip: ONE chain, the tile's, columns x, y, z, w ascending; neither file restates it or the constants
     energy = open(os.path.join(csrc, "d3p_energy.hip")).read()
-    chain = re.search(r"float tt = va\[ki\]\.x - vb\[kj\]\.x;.*?q\[ki\]\[kj\] = __fmaf_rn\(tt, tt, qq\);", energy, flags=re.S).group(0)
-    assert re.sub(r"\s+", " ", chain) in re.sub(r"\s+", " ", text)              # the distance of d3p_energy.hip, word for word
+    chain = r"float tt = va\.x - vb\.x; q = __fmaf_rn\(tt, tt, q\); tt = va\.y - vb\.y; q = __fmaf_rn\(tt, tt, q\); " \
+            r"tt = va\.z - vb\.z; q = __fmaf_rn\(tt, tt, q\); tt = va\.w - vb\.w; return __fmaf_rn\(tt, tt, q\);"
+    assert len(re.findall(chain, re.sub(r"\s+", " ", tile_code))) == 1 and tile_code.count("__fmaf_rn(") == 4
+    for name, src in (("d3p_pair_stats.hip", text), ("d3p_energy.hip", energy)):
+        assert "__fmaf_rn(" not in src and "pair_chain(va[ki], vb[kj], q[ki][kj])" in src, name
+        assert not re.search(r"#define D3P_(ES|PS)_(T|C|LD|WAVES)\b", src), name
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design[design.index("4w."):]
     for said in ("Gram", "permutation", "half-walk", "MMD", "categorical", "VGPR", "bit for bit", "d3p_energy.hip", "accountant"):

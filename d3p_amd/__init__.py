@@ -9,7 +9,7 @@ from .version import __version__  # noqa: F401
 
 __all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "loo", "posterior_loo", "LOOResult",
            "diagnostics", "log_likelihood_total", "log_joint", "guide_diagnostic", "GuideDiagnostic", "mixture_diagnostics", "intervals", "clipping",
-           "scoring", "model_weights", "ppc", "discrepancy", "classification", "marginals", "fidelity", "energy"]
+           "scoring", "model_weights", "ppc", "discrepancy", "classification", "permutation", "marginals", "fidelity", "energy"]
 
 
 def __getattr__(name):
@@ -24,9 +24,10 @@ def __getattr__(name):
     # replicated data sets over their rows) and d3p_amd.discrepancy (realized-discrepancy chi-square checks and the Bayesian R^2) and
     # d3p_amd.classification (confusion counts per draw, ROC histogram, AUC and calibration of a logistic regression) and d3p_amd.energy
     # (the energy score of multivariate predictive draws) and d3p_amd.fidelity (energy distance and nearest-record checks of a synthetic
-    # table) and d3p_amd.marginals (binned one- and two-way marginal fidelity of a synthetic table) without making `import d3p_amd` import torch
+    # table) and d3p_amd.marginals (binned one- and two-way marginal fidelity of a synthetic table) and d3p_amd.permutation (the permutation test of
+    # the energy distance) without making `import d3p_amd` import torch
     if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "diagnostics", "mixture_diagnostics",
-                "intervals", "clipping", "scoring", "model_weights", "ppc", "discrepancy", "classification", "energy", "fidelity", "marginals"):
+                "intervals", "clipping", "scoring", "model_weights", "ppc", "discrepancy", "classification", "energy", "fidelity", "marginals", "permutation"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("loo", "posterior_loo", "LOOResult"):   # PSIS-LOO (d3p_amd.criteria), under the same lazy rule

@@ -10,7 +10,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libd3p_hip.so")
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip", "d3p_label_sums.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_outcome.h", "d3p_row_sums.h", "d3p_pair_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
@@ -390,6 +390,13 @@ SIGNATURES = {
     "d3p_marginals_pair_tile": (C.c_uint32, []),
     "d3p_marginals_code_rows": (C.c_uint32, []),
     "d3p_marginals_workspace": (_SZ, [_U32, _U32, _U32]),
+    # label sums of the pooled pair distances for the energy distance's permutation test (d3p_amd/permutation.py): added symbols, ABI 9
+    # unchanged
+    "d3p_pair_label_sums": (C.c_int, [_V, _V, _I32, C.c_int64, _U32, _U32, _U32, _V, _V, _V, _V, _V, _V, _SZ]),
+    "d3p_pair_label_sums_tile_rows": (C.c_uint32, []),
+    "d3p_pair_label_sums_block_labellings": (C.c_uint32, []),
+    "d3p_pair_label_sums_max_labellings": (C.c_uint32, []),
+    "d3p_pair_label_sums_workspace": (_SZ, [_U32, _U32, _U32]),
 }
 
 _lib = None

@@ -44,6 +44,11 @@ and the worst total variation distance of the binned one-way marginals (BINS qua
 the two-way marginals with the worst pair of columns, and the mean and largest difference of the pairwise associations (Cramer's V),
 followed by the floor -- what the test split, a fresh sample of the same distribution, scores against the training split.  These too
 are functions of the private table and are not covered by the accountant.
+
+--energy-test [N_PERM] (off by default; d3p_amd.permutation) draws the same synthetic table and adds one line: the permutation test of
+its energy distance (Szekely & Rizzo; N_PERM relabellings of the pooled rows, default 199) against the training and against the test
+split -- the statistic, its p-value and the 95 % quantile of the relabelled statistics.  A function of the private table too, not
+covered by the accountant; with many rows it rejects at differences too small to matter, so read it beside --synthetic-fidelity's d2.
 """
 import argparse
 import itertools
@@ -150,6 +155,17 @@ def marginal_fidelity_report(X_train, X_test, params, k, bins, seed=4325):
     synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
                                                      params)["obs"][0]
     return marginals.marginal_fidelity(X_train, synthetic, bins=bins, holdout=X_test)
+
+
+def energy_test_report(X_train, X_test, params, k, n_perm, seed=4325):
+    """The EnergyTests (d3p_amd.permutation) of the synthetic table of synthetic_fidelity_report against the training and against the
+    test split, n_perm relabellings each."""
+    from d3p_amd import mixture, permutation
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    return permutation.energy_test(synthetic, X_train, n_perm=n_perm), permutation.energy_test(synthetic, X_test, n_perm=n_perm)
 
 
 def waic_report(X, params, k, num_draws, seed=4322):
@@ -268,6 +284,11 @@ def main(args):
               "{:.4f}, association difference mean {:.4f}".format(res.assoc_diff_mean, res.assoc_diff_max, res.floor.n_synthetic,
                                                                   res.floor.tvd_one_way_mean, res.floor.tvd_two_way_mean,
                                                                   res.floor.assoc_diff_mean))
+    if getattr(args, "energy_test", None) is not None:
+        tr, te = energy_test_report(X_train, X_test, params, k, args.energy_test)
+        print("energy distance permutation test ({} relabellings): to train statistic {:.4f}, p {:.4f} (null 95% {:.4f}); to test statistic "
+              "{:.4f}, p {:.4f} (null 95% {:.4f})".format(tr.n_perm, float(tr.statistic), tr.p_value, tr.null_quantiles[1],
+                                                          float(te.statistic), te.p_value, te.null_quantiles[1]))
     if getattr(args, "waic", False):
         res = waic_report(X_train, params, k, args.posterior_draws)
         print("WAIC ({} points, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
@@ -314,6 +335,10 @@ def parse_args(argv=None):
                         help='after training, draw one synthetic table of the training split\'s size and report the total variation '
                              'distance of its binned one- and two-way marginals (BINS quantile bins of the training split, default 16) and '
                              'the difference of the pairwise associations, with the test split\'s scores as the noise floor')
+    parser.add_argument('--energy-test', nargs='?', const=199, default=None, type=int, metavar='N_PERM',
+                        help='after training, draw one synthetic table of the training split\'s size and report the permutation test of its '
+                             'energy distance to the train and test splits (N_PERM relabellings, default 199): statistic, p-value and the '
+                             'null 95 %% quantile')
     return parser.parse_args(argv)
 
 

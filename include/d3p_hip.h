@@ -1546,6 +1546,49 @@ uint32_t d3p_marginals_pair_tile(void);
 uint32_t d3p_marginals_code_rows(void);
 size_t d3p_marginals_workspace(uint32_t n, uint32_t d, uint32_t B);
 
+/* Label sums of the pooled pair distances (model-free; d3p_amd/permutation.py; d3p_label_sums.hip); added symbols, ABI 9
+ * unchanged.  What a permutation test of the two-sample energy distance (Szekely & Rizzo; R's energy::eqdist.etest) needs of the pairs:
+ * for R labellings g_r in {0, 1}^m of the m pooled rows the quadratic form of the distance matrix, in ONE O(m^2 (d + R)) walk that
+ * computes every distance once -- never the m x m matrix, never a walk per labelling.
+ * z_dev[i * ld + c] is pooled row i < m in column c < d (column stride 1), float32 (dtype 0) or int32 (dtype 1: converted to float32 when
+ * staged, which is exact for |v| <= 2^24; the Python layer refuses larger magnitudes).  D_ij is d3p_pair_stats' distance, bit for bit
+ * (both walk the tile of d3p_pair_tile.h):
+ *   t_c = fl32(z_ic - z_jc),  q = the float32 fmaf chain over c ascending from 0,  D_ij = sqrtf(q) correctly rounded
+ * so D_ii is exactly +0.0.  labels_dev is uint32, tile-major [ceil(m / 32)][R]: bit p of word (tile, r) says that row 32 tile + p carries
+ * label 1 in labelling r.  Bits of rows >= m in the last tile's words are ignored, whatever they hold; the words are only ever read as
+ * bits, so no content can move an address.  With g_i the live bit of row i:
+ *   s11_dev[r] = sum_{i,j} g_i g_j (double)D_ij   in float64, in the fixed order d3p_label_sums.hip states, not rounded further
+ *   s1t_dev[r] = sum_i g_i row_sum_dev[i]         over i ascending onto 0; a row that is not selected adds nothing
+ *   n1_dev[r]  = the population count of the live bits
+ * row_sum_dev is the caller's (d3p_pair_stats of z against itself); s1t propagates what it holds on the selected rows.  A NaN or +-inf
+ * element anywhere in z makes every s11_dev[r] NaN (the flag taken while staging, never inf - inf); finite elements whose t_c or q
+ * overflows float32 follow IEEE from there.
+ * THE ORDER of s11[r]: rows in tiles of d3p_pair_label_sums_tile_rows() = 32, tile J in slot J mod 4; per (tile pair (I, J), r) and row ii
+ * of tile I the row sum adds its 32 distances in ascending column onto 0 (a clear column bit adds +0.0); per (I, slot, r) the slot sum
+ * adds the row sums of set row bits (a clear one adds +0.0) in ascending ii, then ascending J, onto 0; the four slot sums are added in
+ * ascending order onto 0: the cell (I, r), a float64 of ws_dev; a second launch adds the cells in ascending I onto 0 and computes s1t and
+ * n1.  One form.  A workgroup owns a tile I and a block of d3p_pair_label_sums_block_labellings() = 512 labellings, whose sums stay in
+ * registers; R <= d3p_pair_label_sums_max_labellings() = 65536; d3p_pair_label_sums_workspace(m, d, R) = 8 R ceil(m / 32) bytes (0: an
+ * argument out of range), every byte read is written in the same call.
+ * Deterministic: no floating-point atomics, no host synchronisation; repeated calls give equal bits; s11[r] depends on z, m, d and
+ * labelling r alone -- not on R, the other labellings, r's place in its group of 64 or its block, ld or the workspace's previous contents.
+ * Checked before any launch, in this order: a null pointer (ws_dev may be null only where the workspace is 0, that is, where a later check
+ * refuses the shape), a pointer not aligned to 4 bytes (row_sum_dev, s11_dev, s1t_dev, ws_dev: 8), a dtype other than 0 / 1, m < 1,
+ * d < 1, ld < d, m * ld beyond 63 bits, R outside [1, d3p_pair_label_sums_max_labellings()]: D3P_E_INVALID_ARG; more than 2^31 - 1
+ * workgroups (tiles x blocks; the message names them): D3P_E_UNSUPPORTED; ws_bytes below d3p_pair_label_sums_workspace: D3P_E_WORKSPACE,
+ * with nothing touched; last, a pointer that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_pair_label_sums(void* stream, const void* z_dev, int32_t dtype, int64_t ld, uint32_t m, uint32_t d, uint32_t R,
+                        const uint32_t* labels_dev,                 /* ceil(m / 32) x R */
+                        const double* row_sum_dev,                  /* m */
+                        double* s11_dev, double* s1t_dev, uint32_t* n1_dev,      /* R each */
+                        void* ws_dev, size_t ws_bytes);
+/* host only, no device call: the rows of a tile (32 = the bits of a label word); the labellings a workgroup owns; the largest R; the
+ * workspace in bytes */
+uint32_t d3p_pair_label_sums_tile_rows(void);
+uint32_t d3p_pair_label_sums_block_labellings(void);
+uint32_t d3p_pair_label_sums_max_labellings(void);
+size_t d3p_pair_label_sums_workspace(uint32_t m, uint32_t d, uint32_t R);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libd3p_hip.so")
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip", "d3p_label_sums.hip")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip", "d3p_label_sums.hip", "d3p_column_moments.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_outcome.h", "d3p_row_sums.h", "d3p_pair_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
@@ -91,12 +91,15 @@ class BatchSource(C.Structure):
 
 
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+# per source, on top of _FLAGS: a guard that keeps the compiler from pairing the float32 operations of d3p_column_moments.hip into packed
+# float32 instructions (it emits none there today; the other sources keep the flags their recorded results were built with)
+_EXTRA_FLAGS = {"d3p_column_moments.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _digest(paths):
     """sha256 over the compile flags and the CONTENTS of `paths` (in order)."""
     import hashlib
-    h = hashlib.sha256(" ".join(_FLAGS).encode())
+    h = hashlib.sha256(" ".join(_FLAGS + [f for p in paths for f in _EXTRA_FLAGS.get(os.path.basename(p), [])]).encode())
     for p in paths:
         h.update(os.path.basename(p).encode() + b"\0")
         with open(p, "rb") as f:
@@ -130,7 +133,7 @@ def build(force=False, verbose=False):
         objs.append(obj)
         obj_want = _digest([src] + headers)
         if force or not os.path.exists(obj) or _read(obj + ".srchash") != obj_want:
-            cmd = ["hipcc"] + _FLAGS + ["-c", src, "-o", obj]
+            cmd = ["hipcc"] + _FLAGS + _EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             jobs.append((cmd, subprocess.Popen(cmd), obj, obj_want))
@@ -397,6 +400,12 @@ SIGNATURES = {
     "d3p_pair_label_sums_block_labellings": (C.c_uint32, []),
     "d3p_pair_label_sums_max_labellings": (C.c_uint32, []),
     "d3p_pair_label_sums_workspace": (_SZ, [_U32, _U32, _U32]),
+    # column means and the centred cross-product matrix of a table on the matrix cores (d3p_amd/covariance.py): added symbols, ABI 9 unchanged
+    "d3p_column_moments": (C.c_int, [_V, _V, _I32, C.c_int64, _U64, _U32, _V, _V, C.c_int64, _V, _SZ]),
+    "d3p_column_moments_workspace": (_SZ, [_U64, _U32]),
+    "d3p_column_moments_block_cols": (C.c_uint32, []),
+    "d3p_column_moments_strip_rows": (C.c_uint32, []),
+    "d3p_column_moments_segment_rows": (C.c_uint32, [_U64, _U32]),
 }
 
 _lib = None

@@ -45,6 +45,11 @@ the two-way marginals with the worst pair of columns, and the mean and largest d
 followed by the floor -- what the test split, a fresh sample of the same distribution, scores against the training split.  These too
 are functions of the private table and are not covered by the accountant.
 
+--correlation-fidelity (off by default; d3p_amd.covariance) draws the same synthetic table and adds one line: the largest standardised
+mean difference over the columns, the mean and largest absolute difference of the pairwise Pearson correlations and the Gaussian
+Frechet distance to the training split, followed by the floor -- what the test split scores against the training split.  Functions of
+the private table too, not covered by the accountant.
+
 --energy-test [N_PERM] (off by default; d3p_amd.permutation) draws the same synthetic table and adds one line: the permutation test of
 its energy distance (Szekely & Rizzo; N_PERM relabellings of the pooled rows, default 199) against the training and against the test
 split -- the statistic, its p-value and the 95 % quantile of the relabelled statistics.  A function of the private table too, not
@@ -155,6 +160,17 @@ def marginal_fidelity_report(X_train, X_test, params, k, bins, seed=4325):
     synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
                                                      params)["obs"][0]
     return marginals.marginal_fidelity(X_train, synthetic, bins=bins, holdout=X_test)
+
+
+def correlation_fidelity_report(X_train, X_test, params, k, seed=4325):
+    """The CorrelationFidelity (d3p_amd.covariance) of the synthetic table of synthetic_fidelity_report against the training split, with
+    the test split as the holdout (the noise floor)."""
+    from d3p_amd import covariance, mixture
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    return covariance.correlation_fidelity(X_train, synthetic, holdout=X_test)
 
 
 def energy_test_report(X_train, X_test, params, k, n_perm, seed=4325):
@@ -284,6 +300,12 @@ def main(args):
               "{:.4f}, association difference mean {:.4f}".format(res.assoc_diff_mean, res.assoc_diff_max, res.floor.n_synthetic,
                                                                   res.floor.tvd_one_way_mean, res.floor.tvd_two_way_mean,
                                                                   res.floor.assoc_diff_mean))
+    if getattr(args, "correlation_fidelity", False):
+        res = correlation_fidelity_report(X_train, X_test, params, k)
+        print("correlation fidelity ({} columns, {} synthetic rows): largest standardised mean difference {:.4f}, correlation difference "
+              "mean {:.4f}, max {:.4f}, Frechet distance {:.4f}; held-out floor ({} rows): {:.4f}, {:.4f}, {:.4f}, {:.4f}".format(
+                  res.dim, res.n_synthetic, float(res.smd.max()), res.corr_diff_mean, res.corr_diff_max, res.frechet, res.floor.n_synthetic,
+                  float(res.floor.smd.max()), res.floor.corr_diff_mean, res.floor.corr_diff_max, res.floor.frechet))
     if getattr(args, "energy_test", None) is not None:
         tr, te = energy_test_report(X_train, X_test, params, k, args.energy_test)
         print("energy distance permutation test ({} relabellings): to train statistic {:.4f}, p {:.4f} (null 95% {:.4f}); to test statistic "
@@ -335,6 +357,10 @@ def parse_args(argv=None):
                         help='after training, draw one synthetic table of the training split\'s size and report the total variation '
                              'distance of its binned one- and two-way marginals (BINS quantile bins of the training split, default 16) and '
                              'the difference of the pairwise associations, with the test split\'s scores as the noise floor')
+    parser.add_argument('--correlation-fidelity', action='store_true',
+                        help='after training, draw one synthetic table of the training split\'s size and report the differences of its column '
+                             'means and pairwise correlations and its Gaussian Frechet distance to the training split, with the test '
+                             'split\'s scores as the noise floor')
     parser.add_argument('--energy-test', nargs='?', const=199, default=None, type=int, metavar='N_PERM',
                         help='after training, draw one synthetic table of the training split\'s size and report the permutation test of its '
                              'energy distance to the train and test splits (N_PERM relabellings, default 199): statistic, p-value and the '

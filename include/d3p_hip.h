@@ -1589,6 +1589,54 @@ uint32_t d3p_pair_label_sums_block_labellings(void);
 uint32_t d3p_pair_label_sums_max_labellings(void);
 size_t d3p_pair_label_sums_workspace(uint32_t m, uint32_t d, uint32_t R);
 
+/* Column means and the centred cross-product matrix of a table (model-free; d3p_amd/covariance.py; d3p_column_moments.hip; DESIGN.md
+ * 4z); added symbols, ABI 9 unchanged.  What the covariance, the Pearson correlation and the Gaussian Frechet distance of a synthetic
+ * table against the real one are made of, as one contraction over the ROWS on the matrix cores -- never a float32 Gram product of the
+ * raw values, never a float64 copy of the table.
+ * x_dev[i * ld + c] is row i < n in column c < d (column stride 1), float32 (dtype 0) or int32 (dtype 1: converted to float32 when
+ * loaded, which is exact for |v| <= 2^24; the Python layer refuses larger magnitudes); 1 <= n <= 2^32 - 2, d >= 1.
+ * THE RULE is the shifted-data algorithm:
+ *   S_c  = sum_i (double)x_ic, in the order below       c_c = (float)(S_c / n), the shift       flag_c = "S_c is not finite"
+ *   t_ic = fl32(x_ic - c_c)      G_ce = sum_i t_ic t_ie (float32 strips on v_mfma_f32_32x32x2_f32, the strips in float64)
+ *   s_c  = sum_i (double)t_ic    (float64)
+ *   mean_dev[c]             = (double)c_c + s_c / n
+ *   m2_dev[c * m2_ld + e]   = G_ce - s_c s_e / n        = sum_i (x_ic - mean_c)(x_ie - mean_e) up to the bound of DESIGN.md 4z
+ * s_c is of the order of n times the rounding of c_c: nothing cancels.  Both triangles are written, (c, e) and (e, c) from the one value
+ * computed for c <= e, so m2 is symmetric to the bit.  NON-FINITE VALUES: a column that holds a NaN, a +inf or a -inf is FLAGGED (a
+ * float64 sum of finite float32 values cannot overflow, so the flag is exactly "the sum is not finite"); it gets mean = NaN and NaN in
+ * its whole row and column of m2, from the flag and never from inf - inf, and touches no other column.  Finite values whose t or
+ * products overflow float32 follow IEEE from there.
+ * THE ORDER (one form): L = d3p_column_moments_strip_rows() = 64, B = d3p_column_moments_block_cols() = 64, R =
+ * d3p_column_moments_segment_rows(n, d), a multiple of 4 L and a function of n and d ALONE (never of the device): about 1024 workgroups
+ * over the block pairs when d is small, never below 1024 rows.  The rows are cut into segments of R, the columns into blocks of B (two
+ * tiles of 32); a workgroup of four wavefronts owns a block pair P <= Q and a segment, each wavefront one tile pair and every row pair
+ * (rows 2 j, 2 j + 1) of the segment in ascending j.  EVERY merge over segments adds them in 8 chunks of ceil(segments / 8)
+ * consecutive segments, each in ascending order onto 0, then the chunks in ascending order onto 0.  S_c (segments of
+ * d3p_column_moments_segment_rows(n, 1) rows): per segment four phases (rows mod 4), each four accumulators (a0 + a1) + (a2 + a3), the
+ * phases ascending onto 0, the segments merged.  G_ce: the wavefront adds its row pairs' products into the matrix instruction's float32
+ * accumulators and, after every L / 2 row pairs (L rows) and at the end, widens them and adds them onto float64 registers; the
+ * segments' partials merged (the last launch).  s_c: float64 per row parity in ascending j, even + odd, the segments merged.  Rows >= n
+ * and columns >= d enter as zeros (a select after the subtraction; their lanes read a word inside the table: the segment's last row,
+ * column 0).
+ * Deterministic: no atomics, no scratch, no host synchronisation or allocation; repeated calls give equal bits; m2[c][e] depends on
+ * columns c and e, n, d and the dtype alone -- not on ld, m2_ld, the other columns or the workspace's previous contents (every word
+ * read is written before in the same call).  d3p_column_moments_workspace(n, d) bytes: the shifts and flags, the segments' column sums,
+ * 128 merged s per block pair and one partial of 4224 float64 per (block pair, segment); 0: an argument out of range or a grid the entry refuses.
+ * Checked before any launch, in this order: a null pointer; x_dev not aligned to 4 bytes; mean_dev, m2_dev or ws_dev not aligned to 8; a
+ * dtype other than 0 / 1; n outside [1, 2^32 - 2]; d < 1; ld < d; n * ld beyond 63 bits; m2_ld < d: D3P_E_INVALID_ARG; more than
+ * 2^31 - 1 workgroups (block pairs x segments; the message names them): D3P_E_UNSUPPORTED; ws_bytes below
+ * d3p_column_moments_workspace: D3P_E_WORKSPACE, with nothing touched; last, a pointer that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_column_moments(void* stream, const void* x_dev, int32_t dtype, int64_t ld, uint64_t n, uint32_t d,
+                       double* mean_dev,                           /* d */
+                       double* m2_dev, int64_t m2_ld,              /* d x m2_ld */
+                       void* ws_dev, size_t ws_bytes);
+/* host only, no device call: the workspace in bytes; the columns of a block; L, the rows of a float32 strip; R, the rows of a segment
+ * (0: an argument out of range) */
+size_t d3p_column_moments_workspace(uint64_t n, uint32_t d);
+uint32_t d3p_column_moments_block_cols(void);
+uint32_t d3p_column_moments_strip_rows(void);
+uint32_t d3p_column_moments_segment_rows(uint64_t n, uint32_t d);
+
 #ifdef __cplusplus
 }
 #endif

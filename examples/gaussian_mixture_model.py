@@ -54,6 +54,12 @@ the private table too, not covered by the accountant.
 its energy distance (Szekely & Rizzo; N_PERM relabellings of the pooled rows, default 199) against the training and against the test
 split -- the statistic, its p-value and the 95 % quantile of the relabelled statistics.  A function of the private table too, not
 covered by the accountant; with many rows it rejects at differences too small to matter, so read it beside --synthetic-fidelity's d2.
+
+--prdc [K] (off by default; d3p_amd.neighbours) draws the same synthetic table and adds one line: its precision and recall
+(Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020) and authenticity (Alaa et al. 2022) against the training split
+from K-nearest-neighbour balls (default 5), followed by the floor -- what the test split scores against the training split.  Low
+precision or density says the synthetic rows leave the data's support, low recall or coverage that modes are missing.  Functions of the
+private table too, not covered by the accountant.
 """
 import argparse
 import itertools
@@ -171,6 +177,17 @@ def correlation_fidelity_report(X_train, X_test, params, k, seed=4325):
     synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
                                                      params)["obs"][0]
     return covariance.correlation_fidelity(X_train, synthetic, holdout=X_test)
+
+
+def prdc_report(X_train, X_test, params, k, n_neighbours, seed=4325):
+    """The PRDC (d3p_amd.neighbours) of the synthetic table of synthetic_fidelity_report against the training split from
+    n_neighbours-nearest-neighbour balls, with the test split as the holdout (the floor)."""
+    from d3p_amd import mixture, neighbours
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    return neighbours.prdc(X_train, synthetic, k=n_neighbours, holdout=X_test)
 
 
 def energy_test_report(X_train, X_test, params, k, n_perm, seed=4325):
@@ -311,6 +328,12 @@ def main(args):
         print("energy distance permutation test ({} relabellings): to train statistic {:.4f}, p {:.4f} (null 95% {:.4f}); to test statistic "
               "{:.4f}, p {:.4f} (null 95% {:.4f})".format(tr.n_perm, float(tr.statistic), tr.p_value, tr.null_quantiles[1],
                                                           float(te.statistic), te.p_value, te.null_quantiles[1]))
+    if getattr(args, "prdc", None) is not None:
+        res = prdc_report(X_train, X_test, params, k, args.prdc)
+        print("k-NN balls (k = {}, {} synthetic rows): precision {:.4f}, recall {:.4f}, density {:.4f}, coverage {:.4f}, authenticity {:.4f}; "
+              "held-out floor ({} rows): {:.4f}, {:.4f}, {:.4f}, {:.4f}, {:.4f}".format(
+                  res.k, res.n_synthetic, res.precision, res.recall, res.density, res.coverage, res.authenticity, res.floor.n_synthetic,
+                  res.floor.precision, res.floor.recall, res.floor.density, res.floor.coverage, res.floor.authenticity))
     if getattr(args, "waic", False):
         res = waic_report(X_train, params, k, args.posterior_draws)
         print("WAIC ({} points, {} posterior draws): elpd_waic {:.2f} +- {:.2f}, p_waic {:.2f}".format(
@@ -365,6 +388,10 @@ def parse_args(argv=None):
                         help='after training, draw one synthetic table of the training split\'s size and report the permutation test of its '
                              'energy distance to the train and test splits (N_PERM relabellings, default 199): statistic, p-value and the '
                              'null 95 %% quantile')
+    parser.add_argument('--prdc', nargs='?', const=5, default=None, type=int, metavar='K',
+                        help='after training, draw one synthetic table of the training split\'s size and report its precision, recall, '
+                             'density, coverage and authenticity against the training split from K-nearest-neighbour balls (default 5), '
+                             'with the test split\'s scores as the floor')
     return parser.parse_args(argv)
 
 

@@ -1637,6 +1637,51 @@ uint32_t d3p_column_moments_block_cols(void);
 uint32_t d3p_column_moments_strip_rows(void);
 uint32_t d3p_column_moments_segment_rows(uint64_t n, uint32_t d);
 
+/* k nearest neighbours of two tables (model-free; d3p_amd/neighbours.py; d3p_pair_knn.hip); added symbols, ABI 9 unchanged.
+ * a_dev: na rows of d columns with row stride a_ld, b_dev: nb rows with row stride b_ld, both float32 (dtype 0) or both int32 (dtype 1,
+ * converted when staged: exact for |v| <= 2^24).  q(i, j) is d3p_pair_stats' squared distance, bit for bit: t_c = fl32(a_c - b_c), the
+ * float32 fmaf chain over c ascending.  The admissible j of row i are all j < nb, without j == i when exclude_diagonal is set (na ==
+ * nb).  The key of a pair is the unsigned 64-bit integer (bits(q) << 32) | j; the keys of a row are distinct, and for t < k, ascending:
+ *   q_dev[i * k + t]     = the squared distance of the row's t-th smallest key
+ *   dist_dev[i * k + t]  = its correctly rounded (IEEE) root
+ *   index_dev[i * k + t] = its j: among equal q the smallest j first
+ * and +inf, +inf, 0xFFFFFFFF in the places that fewer than k admissible j leave.  qr_b_dev is null or nb float32 squared radii, one per
+ * row of b; with it count_dev[i] = #{admissible j : q(i, j) < qr_b_dev[j]}, strictly and by IEEE (a NaN radius contains nothing, +inf
+ * every finite q); without it count_dev is not touched and may be null.  A NaN or +-inf element in row i of a makes that row NaN, NaN,
+ * 0xFFFFFFFF with count 0xFFFFFFFF and touches no other row; one anywhere in b does so to every row.  At k = 1 dist_dev and index_dev
+ * equal d3p_pair_stats' min_dev and argmin_dev bit for bit.
+ * Everything selected or counted is an integer: the outputs of a row depend on that row, b, the radii, nb, d, k and the flag alone,
+ * not on na, the strides, the row's place, the form or the workspace's previous contents; repeated calls give equal bits.  Two forms:
+ * wide (1: a workgroup per tile of d3p_pair_knn_tile_rows() = 32 rows of a walks every tile of b; no workspace) and split (2: a
+ * workgroup per tile of a and segment of d3p_pair_knn_segment_tiles(na, nb, d, k) tiles of b writes k keys, a count and a flag word per
+ * (segment, row) to ws_dev; a second launch merges them).  d3p_pair_knn_form(na, nb, d, k) is the form the entry takes (0: an argument
+ * out of range): split where the tiles of a alone cannot fill the chip; d3p_pair_knn_set_form(form) (a test aid; 0: the rule) forces
+ * one where it exists -- a table a of more than 4096 tiles always runs wide -- and changes no result.  d3p_pair_knn_workspace(na, nb,
+ * d, k) is the size that form needs: 0 for the wide form, where a null ws_dev is fine, and at most 4096 x 32 x (8 k + 8) bytes.  The
+ * sorted list of a row lies in registers, in a capacity class d3p_pair_knn_capacity(k) = 1, 4, 8 or 16 >= k (0: k out of range);
+ * d3p_pair_knn_max_k() = 16.  Columns are staged in chunks of d3p_pair_knn_chunk_cols() = 32 in LDS: neither nb nor d is bounded by it.
+ * No atomics, no scratch, no dynamic LDS, no host synchronisation or allocation.
+ * Checked before any launch, in this order: a null pointer (count_dev only with qr_b_dev); a pointer not aligned to 4 bytes; ws_dev not
+ * aligned to 8; a dtype other than 0 / 1; na < 1 or nb < 1; d < 1; a_ld < d or b_ld < d; na * a_ld or nb * b_ld beyond 63 bits; k
+ * outside [1, d3p_pair_knn_max_k()]; exclude_diagonal other than 0 / 1, or set with na != nb: D3P_E_INVALID_ARG; ws_bytes below
+ * d3p_pair_knn_workspace (or a null ws_dev where it is not 0): D3P_E_WORKSPACE; last, a pointer that is not device memory:
+ * D3P_E_INVALID_ARG.  (No grid is refused: the tiles of a are fewer than 2^27 and the split form's workgroups are capped.) */
+int d3p_pair_knn(void* stream, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld, uint32_t na, uint32_t nb,
+                 uint32_t d, uint32_t k, int32_t exclude_diagonal,
+                 const float* qr_b_dev,                            /* nb, or null */
+                 float* q_dev, float* dist_dev, uint32_t* index_dev, /* na x k each */
+                 uint32_t* count_dev,                              /* na (with qr_b_dev) */
+                 void* ws_dev, size_t ws_bytes);
+/* host only, no device call */
+uint32_t d3p_pair_knn_max_k(void);
+uint32_t d3p_pair_knn_tile_rows(void);
+uint32_t d3p_pair_knn_chunk_cols(void);
+uint32_t d3p_pair_knn_capacity(uint32_t k);
+uint32_t d3p_pair_knn_form(uint32_t na, uint32_t nb, uint32_t d, uint32_t k);
+size_t d3p_pair_knn_workspace(uint32_t na, uint32_t nb, uint32_t d, uint32_t k);
+uint32_t d3p_pair_knn_segment_tiles(uint32_t na, uint32_t nb, uint32_t d, uint32_t k);
+int d3p_pair_knn_set_form(int32_t form);
+
 #ifdef __cplusplus
 }
 #endif

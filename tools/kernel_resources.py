@@ -3,20 +3,25 @@
 
     python tools/kernel_resources.py d3p_amd/csrc/d3p_dpvi.hip [name-filter ...]
 
-Compiles the file for gfx950 with -Rpass-analysis=kernel-resource-usage (works without a GPU) and prints one
-line per kernel whose demangled name contains any of the filters."""
+Compiles the file for gfx950 with the flags the library's build gives that source (d3p_amd._lib: the common flags and the source's
+own) and -Rpass-analysis=kernel-resource-usage (works without a GPU), and prints one line per kernel whose demangled name contains any
+of the filters."""
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from d3p_amd._lib import _EXTRA_FLAGS, _FLAGS  # noqa: E402
+
 
 def main():
     src = sys.argv[1]
     filters = sys.argv[2:] or [""]
     with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o",
+        r = subprocess.run(["hipcc"] + _FLAGS + _EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o",
                             os.path.join(tmp, "o.o"), "-Rpass-analysis=kernel-resource-usage"],
                            capture_output=True, text=True)
     if r.returncode != 0:

@@ -267,3 +267,7 @@ int d3p_predict_mean_rows(void* stream, const d3p_logreg_model* model, const flo
 }
 
 }  // extern "C"
+
+// the column sort over all rows of a table, its midranks and the KS / Wasserstein-1 distances of two sorted tables (d3p_sort_columns.hip
+// holds the entries) are compiled here: they work on the keys of d3p_colreduce.h
+#include "d3p_colsort_global_kernel.h"

@@ -50,6 +50,11 @@ mean difference over the columns, the mean and largest absolute difference of th
 Frechet distance to the training split, followed by the floor -- what the test split scores against the training split.  Functions of
 the private table too, not covered by the accountant.
 
+--univariate-fidelity (off by default; d3p_amd.univariate) draws the same synthetic table and adds one line: the largest two-sample
+Kolmogorov-Smirnov statistic over the columns with its column, the largest scaled Wasserstein-1 distance and the mean and largest
+absolute difference of the pairwise Spearman correlations, followed by the floor.  Functions of the private table too, not covered by
+the accountant.
+
 --energy-test [N_PERM] (off by default; d3p_amd.permutation) draws the same synthetic table and adds one line: the permutation test of
 its energy distance (Szekely & Rizzo; N_PERM relabellings of the pooled rows, default 199) against the training and against the test
 split -- the statistic, its p-value and the 95 % quantile of the relabelled statistics.  A function of the private table too, not
@@ -177,6 +182,17 @@ def correlation_fidelity_report(X_train, X_test, params, k, seed=4325):
     synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
                                                      params)["obs"][0]
     return covariance.correlation_fidelity(X_train, synthetic, holdout=X_test)
+
+
+def univariate_fidelity_report(X_train, X_test, params, k, seed=4325):
+    """The UnivariateFidelity (d3p_amd.univariate) of the synthetic table of synthetic_fidelity_report against the training split, with
+    the test split as the holdout (the noise floor)."""
+    from d3p_amd import mixture, univariate
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    return univariate.univariate_fidelity(X_train, synthetic, holdout=X_test)
 
 
 def prdc_report(X_train, X_test, params, k, n_neighbours, seed=4325):
@@ -323,6 +339,13 @@ def main(args):
               "mean {:.4f}, max {:.4f}, Frechet distance {:.4f}; held-out floor ({} rows): {:.4f}, {:.4f}, {:.4f}, {:.4f}".format(
                   res.dim, res.n_synthetic, float(res.smd.max()), res.corr_diff_mean, res.corr_diff_max, res.frechet, res.floor.n_synthetic,
                   float(res.floor.smd.max()), res.floor.corr_diff_mean, res.floor.corr_diff_max, res.floor.frechet))
+    if getattr(args, "univariate_fidelity", False):
+        res = univariate_fidelity_report(X_train, X_test, params, k)
+        print("univariate fidelity ({} columns, {} synthetic rows): largest KS {:.4f} (column {}), largest scaled Wasserstein-1 {:.4f}, "
+              "Spearman difference mean {:.4f}, max {:.4f}; held-out floor ({} rows): {:.4f}, {:.4f}, {:.4f}, {:.4f}".format(
+                  res.dim, res.n_synthetic, res.worst_columns[0][1], res.worst_columns[0][0], float(res.w1_scaled.max()),
+                  res.spearman_diff_mean, res.spearman_diff_max, res.floor.n_synthetic, float(res.floor.ks.max()),
+                  float(res.floor.w1_scaled.max()), res.floor.spearman_diff_mean, res.floor.spearman_diff_max))
     if getattr(args, "energy_test", None) is not None:
         tr, te = energy_test_report(X_train, X_test, params, k, args.energy_test)
         print("energy distance permutation test ({} relabellings): to train statistic {:.4f}, p {:.4f} (null 95% {:.4f}); to test statistic "
@@ -384,6 +407,10 @@ def parse_args(argv=None):
                         help='after training, draw one synthetic table of the training split\'s size and report the differences of its column '
                              'means and pairwise correlations and its Gaussian Frechet distance to the training split, with the test '
                              'split\'s scores as the noise floor')
+    parser.add_argument('--univariate-fidelity', action='store_true',
+                        help='after training, draw one synthetic table of the training split\'s size and report the per-column '
+                             'Kolmogorov-Smirnov and Wasserstein-1 distances and the differences of the pairwise Spearman correlations '
+                             'to the training split, with the test split\'s scores as the noise floor')
     parser.add_argument('--energy-test', nargs='?', const=199, default=None, type=int, metavar='N_PERM',
                         help='after training, draw one synthetic table of the training split\'s size and report the permutation test of its '
                              'energy distance to the train and test splits (N_PERM relabellings, default 199): statistic, p-value and the '

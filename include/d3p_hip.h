@@ -1682,6 +1682,69 @@ size_t d3p_pair_knn_workspace(uint32_t na, uint32_t nb, uint32_t d, uint32_t k);
 uint32_t d3p_pair_knn_segment_tiles(uint32_t na, uint32_t nb, uint32_t d, uint32_t k);
 int d3p_pair_knn_set_form(int32_t form);
 
+/* Every column of a table sorted over ALL its rows, and the doubled midranks behind the sort (model-free; d3p_amd/univariate.py;
+ * d3p_sort_columns.hip, d3p_colsort_global_kernel.h); added symbols, ABI 9 unchanged.
+ * x_dev[i * ld + c] is row i < n in column c < d (column stride 1), float32 (dtype 0) or int32 (dtype 1); 1 <= n <= 2^31 - 1, d >= 1.
+ * sorted_dev[c * ld_s + 0 .. n) receives the stored values of column c in ascending order of the column reducers' one order key: -0
+ * comes out as +0 (the key takes them as one value), negative NaNs come first and positive NaNs last, each NaN with its own bits.  The
+ * result is the sorted multiset of the column: unique, so there is no order among ties to promise.  A least-significant-digit radix
+ * sort on the keys, 8-bit digits, four passes, keys only (no index payload), segmented: every launch serves all d columns; a block is
+ * d3p_sort_columns_block_keys() = 4096 consecutive positions of a column and a workgroup.  No workgroup waits for another: per pass a
+ * count, a scan (one workgroup per column) and a stable scatter are three launches.  sorted_dev must not overlap x_dev.
+ * ranks2_dev is null or n x ld_r int32, row-major: ranks2[i * ld_r + c] = lo + hi + 1 with lo = #{rows whose key in column c is
+ * below row i's} and hi = #{.. not above ..}: TWICE the 1-based average rank, an exact integer under ties; needs n <= 2^30 - 1.  A
+ * float32 column that holds a NaN gets 0 in every row and touches no other column.  lo and hi come from a binary search over every
+ * S-th key of the sorted column staged in LDS, S = d3p_sort_columns_rank_stride(n) = ceil(n / d3p_sort_columns_staged_keys()), and one
+ * over a window of S - 1 keys in memory.
+ * Deterministic: integer operations only, no floating-point atomics, no scratch, no dynamic LDS, no host synchronisation or allocation;
+ * the outputs do not depend on ld, ld_s, ld_r or the workspace's previous contents (every word read is written before in the same
+ * call).  d3p_sort_columns_workspace(n, d, want_ranks) bytes: two key buffers of n d words (the first holds the UNSORTED column-major
+ * keys afterwards) and 256 counts per (column, block); the midranks pass through the second key buffer, so want_ranks changes only
+ * the range of n; 0: an argument out of range or a grid the entry refuses.
+ * Checked before any launch, in this order: a null pointer (ranks2_dev may be null); a pointer not aligned to 4 bytes; a dtype other
+ * than 0 / 1; n outside [1, 2^31 - 1], or above 2^30 - 1 with ranks2_dev; d < 1; ld < d; ld_s < n; ld_r < d; n * ld, d * ld_s or n *
+ * ld_r beyond 63 bits: D3P_E_INVALID_ARG; more than 2^31 - 1 workgroups (columns x blocks): D3P_E_UNSUPPORTED; ws_bytes below
+ * d3p_sort_columns_workspace: D3P_E_WORKSPACE, with nothing touched; last, a pointer that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_sort_columns(void* stream, const void* x_dev, int32_t dtype, int64_t ld, uint64_t n, uint32_t d,
+                     void* sorted_dev, int64_t ld_s,                /* d x ld_s, of x's dtype */
+                     int32_t* ranks2_dev, int64_t ld_r,             /* n x ld_r, or null */
+                     void* ws_dev, size_t ws_bytes);
+/* host only, no device call */
+size_t d3p_sort_columns_workspace(uint64_t n, uint32_t d, int32_t want_ranks);
+uint32_t d3p_sort_columns_block_keys(void);
+uint32_t d3p_sort_columns_staged_keys(void);
+uint32_t d3p_sort_columns_rank_stride(uint64_t n);
+
+/* The two-sample Kolmogorov-Smirnov statistic and the 1-Wasserstein distance per column of two SORTED tables (d3p_sort_columns'
+ * output: a_dev d x ld_a with n_a values per column, b_dev d x ld_b with n_b, one dtype); added symbols, ABI 9 unchanged.  With i =
+ * #{a <= v} and j = #{b <= v} (compared by key) over the pooled values v of column c:
+ *   ks_num_dev[c] = max_v |i n_b - j n_a|, an exact integer (KS = ks_num / (n_a n_b) is the caller's one division)
+ *   ks_at_dev[c]  = the smallest pooled value that attains it, in the tables' dtype
+ *   w1_dev[c]     = sum_v |i / n_a - j / n_b| (next(v) - v) over the distinct pooled values, next(v) the next larger one; the last
+ *                   value adds nothing
+ * ORDER of w1: a term is ((double)num / ((double)n_a (double)n_b)) ((double)next - (double)v); a block is 4096 consecutive positions of
+ * a column; thread t of 256 adds the terms of its positions block 4096 + r 256 + t in ascending r onto +0, the threads merge in the
+ * tree red[t] += red[t + w], w = 128 .. 1, and the blocks' partials are added in ascending order, a's then b's, onto +0.  No atomics:
+ * the bits are a function of the two columns alone.  BOUND: |w1 - exact| <= gamma_k sum |term|, gamma_k = k u / (1 - k u), u = 2^-53,
+ * k = d3p_column_cdf_distance_roundings(n_a, n_b) = 5 (a term: num, the denominator, the quotient, the difference, the product) + 16
+ * (a thread's chain) + 8 (the tree) + the blocks of a and of b (the merge).  For int32 and for float32 values within 29 binades the
+ * difference is exact.
+ * FLAGS, read off the ends of the sorted columns: a float32 NaN in either table gives ks_num = 2^64 - 1, ks_at = NaN and w1 = NaN; an
+ * infinity without a NaN leaves ks_num and ks_at as computed (the order is well defined) and gives w1 = NaN.  Tables that are not
+ * sorted give numbers without meaning; every access stays inside the tables.
+ * Checked before any launch, in this order: a null pointer; a_dev, b_dev or ks_at_dev not aligned to 4 bytes; ks_num_dev, w1_dev or
+ * ws_dev not aligned to 8; a dtype other than 0 / 1; n_a or n_b outside [1, 2^31 - 1] (so n_a n_b < 2^63); d < 1; ld_a < n_a or ld_b <
+ * n_b; d * ld_a or d * ld_b beyond 63 bits: D3P_E_INVALID_ARG; more than 2^31 - 1 workgroups (columns x blocks of a and b):
+ * D3P_E_UNSUPPORTED; ws_bytes below d3p_column_cdf_distance_workspace (20 bytes per (column, block)): D3P_E_WORKSPACE, with nothing
+ * touched; last, a pointer that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_column_cdf_distance(void* stream, const void* a_dev, int64_t ld_a, uint64_t n_a, const void* b_dev, int64_t ld_b, uint64_t n_b,
+                            int32_t dtype, uint32_t d,
+                            uint64_t* ks_num_dev, void* ks_at_dev, double* w1_dev,   /* d each */
+                            void* ws_dev, size_t ws_bytes);
+/* host only, no device call (0: an argument out of range) */
+size_t d3p_column_cdf_distance_workspace(uint64_t n_a, uint64_t n_b, uint32_t d);
+uint32_t d3p_column_cdf_distance_roundings(uint64_t n_a, uint64_t n_b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,8 @@
 // converted to float32 when staged, exact for |v| <= 2^24, which is what the Python layer admits); y[r * y_ld + c] the observation.
 // For row r the ITEMS are z_0 .. z_{n-1} (the draws) and z_n = y_r.  For a pair of items (a, b):
 //     t_c = fl32(a_c - b_c)      q = the float32 fmaf chain q <- fmaf(t_c, t_c, q) over c = 0 .. d-1 ascending, from q = 0
-//     dist = the NATIVE root of q (1 ulp, exact on perfect squares; the bound of tests/energy_ref.bound carries it; DESIGN.md 4w's
-//            kernel takes the IEEE root), widened to float64
+//     dist = sqrtf(q), correctly rounded (the IEEE root, pair_sqrt: the one of DESIGN.md 4w's kernel; the bound of
+//            tests/energy_ref.bound allows 1 ulp), widened to float64
 // (the chain is symmetric in a and b: t_c only changes its sign).  With U = sum_{i<j<n} dist(z_i, z_j) in float64:
 //     S1 = sum_{i<n} dist(z_i, y)      S2 = 2 U        (each unordered pair is computed once and counted twice)
 //     mae = S1 / n      spread = S2 / (2 n^2)      es = mae - spread      es_fair = mae - S2 / (2 n (n - 1))   (n = 1: 0 / 0 = NaN is the rule)
@@ -115,7 +115,7 @@ __device__ __forceinline__ void es_row_slot(const EsArgs& a, uint64_t row, uint3
 #pragma unroll
                 for (int kj = 0; kj < 4; ++kj) {
                     const uint32_t i = I * D3P_PAIR_T + ti + 8u * ki, j = J * D3P_PAIR_T + tj + 8u * kj;
-                    const double dist = (double)__fsqrt_rn(q[ki][kj]);
+                    const double dist = (double)pair_sqrt(q[ki][kj]);
                     const bool pair = i < j && j <= a.n;
                     s1 += pair && j == a.n ? dist : 0.0;
                     u += pair && j < a.n ? dist : 0.0;

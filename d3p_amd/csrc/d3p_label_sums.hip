@@ -7,7 +7,7 @@
 // THE RULE.  z[i * ld + c] is pooled row i < m in column c < d, float32 (dtype 0) or int32 (dtype 1: converted to float32 when staged,
 // exact for |v| <= 2^24, which is what the Python layer admits).  D_ij is the distance of d3p_pair_stats.hip, bit for bit:
 //     t_c = fl32(z_ic - z_jc)      q = the float32 fmaf chain q <- fmaf(t_c, t_c, q) over c = 0 .. d-1 ascending, from q = 0
-//     D_ij = sqrtf(q), correctly rounded (the IEEE root: ls_sqrt below, not the native instruction's 1 ulp)
+//     D_ij = sqrtf(q), correctly rounded (the IEEE root: pair_sqrt, not the native instruction's 1 ulp)
 // by the tile and the chain of d3p_pair_tile.h; D_ii is exactly +0.0 and D_ij == D_ji bitwise.  labels[tile * R + r] is a uint32 whose bit
 // p says that row 32 tile + p carries label 1 in labelling r (tile-major: adjacent labellings are adjacent words).  Bits of rows >= m in
 // the last tile's words are IGNORED, whatever they hold; the words are only ever read as bits, never as an index.  With g_i the live bit:
@@ -55,18 +55,6 @@ struct LsArgs {
     double* s11; double* s1t; uint32_t* n1; double* cells;
 };
 
-// the items of the pooled table: its m rows
-struct LsItems {
-    typedef uint64_t index;
-    const uint32_t* base; int64_t ld; uint32_t n;
-    __device__ __forceinline__ bool live(uint64_t row) const { return row < n; }
-    __device__ __forceinline__ uint32_t word(uint64_t row, uint32_t col) const { return base[(int64_t)row * ld + col]; }
-};
-
-// the IEEE root, as d3p_pair_stats.hip takes it (correctly rounded under the compiler's default; the rounded-root intrinsic of this
-// toolchain's headers is the 1 ulp instruction)
-__device__ __forceinline__ float ls_sqrt(float q) { return __builtin_sqrtf(q); }
-
 // the bits of the rows of `tile` that exist
 __device__ __forceinline__ uint32_t ls_live_bits(uint32_t tile, uint32_t m)
 {
@@ -90,10 +78,11 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_label_sums(LsArgs 
     const uint32_t r0 = block * D3P_LS_BLOCK;
     const uint32_t left = a.R - r0;
     const uint32_t ng = left >= D3P_LS_BLOCK ? D3P_LS_GROUPS : (left + 63u) / 64u;   // live groups of this block, >= 1
-    const LsItems rows = {a.z, a.ld, a.m};
+    const PairRows rows = {a.z, a.ld, a.m};
     const bool a_resident = a.d <= D3P_PAIR_C;
     bool bad = false;
-    if (a_resident) {   // one chunk: tile I is staged once, by every wavefront for itself
+    // pair_stage_resident's lines in place: as the helper they cost this kernel 1.7 % at d = 784 (docs/experiments_fidelity.md)
+    if (a_resident) {
         const int lw = pair_lanes_log2(a.d);
         uint32_t wa[16];
         pair_load(rows, I, 0u, a.d, lw, lane, wa);
@@ -151,7 +140,7 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_label_sums(LsArgs 
 #pragma unroll
         for (int ki = 0; ki < 4; ++ki)
 #pragma unroll
-            for (int kj = 0; kj < 4; ++kj) D[(ti + 8u * ki) * D3P_PAIR_T + tj + 8u * kj] = ls_sqrt(q[ki][kj]);
+            for (int kj = 0; kj < 4; ++kj) D[(ti + 8u * ki) * D3P_PAIR_T + tj + 8u * kj] = pair_sqrt(q[ki][kj]);
         pair_wave_sync();
         // phase 2: lanes are labellings; every lane reads the same 32 distances of row ii
         for (uint32_t ii = 0; ii < D3P_PAIR_T; ++ii) {
@@ -218,14 +207,12 @@ __global__ __launch_bounds__(256) void k_pair_label_sums_merge(LsArgs a)
     a.n1[r] = n;
 }
 
-static uint32_t ls_tiles(uint32_t m) { return (uint32_t)(((uint64_t)m + D3P_PAIR_T - 1u) / D3P_PAIR_T); }
-
 static bool ls_shape_ok(uint32_t m, uint32_t d, uint32_t R) { return m >= 1 && d >= 1 && R >= 1 && R <= D3P_LS_MAX_R; }
 
 static size_t ls_workspace(uint32_t m, uint32_t d, uint32_t R)
 {
     if (!ls_shape_ok(m, d, R)) return 0;
-    return (size_t)ls_tiles(m) * (size_t)R * sizeof(double);   // < 2^27 x 2^16 x 8: no wrap
+    return (size_t)pair_tiles(m) * (size_t)R * sizeof(double);   // < 2^27 x 2^16 x 8: no wrap
 }
 
 }  // namespace d3p
@@ -254,14 +241,10 @@ int d3p_pair_label_sums(void* stream, const void* z_dev, int32_t dtype, int64_t 
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if ((((uintptr_t)row_sum_dev | (uintptr_t)s11_dev | (uintptr_t)s1t_dev | (uintptr_t)ws_dev) & 7u) != 0)
         return fail(D3P_E_INVALID_ARG, "%s: row_sum_dev, s11_dev, s1t_dev or ws_dev is not aligned to 8 bytes", what);
-    if (dtype != 0 && dtype != 1) return fail(D3P_E_INVALID_ARG, "%s: dtype must be 0 (float32) or 1 (int32), got %d", what, dtype);
-    if (m < 1) return fail(D3P_E_INVALID_ARG, "%s: m >= 1 is required", what);
-    if (d < 1) return fail(D3P_E_INVALID_ARG, "%s: d >= 1 is required", what);
-    if (ld < 0 || (uint64_t)ld < d) return fail(D3P_E_INVALID_ARG, "%s: ld >= d is required", what);
-    if ((uint64_t)m > (uint64_t)INT64_MAX / (uint64_t)ld) return fail(D3P_E_INVALID_ARG, "%s: m * ld does not fit 63 bits", what);
+    if (const int rc = pair_check_table(what, dtype, ld, m, d, "m", "ld")) return rc;
     if (R < 1 || R > D3P_LS_MAX_R)
         return fail(D3P_E_INVALID_ARG, "%s: 1 <= R <= %u labellings are required, got %u", what, D3P_LS_MAX_R, R);
-    const uint32_t ntiles = ls_tiles(m), nblocks = (R + D3P_LS_BLOCK - 1u) / D3P_LS_BLOCK;
+    const uint32_t ntiles = pair_tiles(m), nblocks = (R + D3P_LS_BLOCK - 1u) / D3P_LS_BLOCK;
     const uint64_t groups = (uint64_t)ntiles * nblocks;
     if (groups > 0x7fffffffull)
         return fail(D3P_E_UNSUPPORTED, "%s: %u tiles of rows x %u blocks of labellings = %llu workgroups, more than 2^31 - 1", what, ntiles,
@@ -273,11 +256,7 @@ int d3p_pair_label_sums(void* stream, const void* z_dev, int32_t dtype, int64_t 
     LsArgs a;
     a.z = static_cast<const uint32_t*>(z_dev); a.dtype = dtype; a.ld = ld; a.m = m; a.d = d; a.R = R; a.ntiles = ntiles; a.nblocks = nblocks;
     a.labels = labels_dev; a.row_sum = row_sum_dev; a.s11 = s11_dev; a.s1t = s1t_dev; a.n1 = n1_dev; a.cells = static_cast<double*>(ws_dev);
-    hipLaunchKernelGGL(k_pair_label_sums, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
-    const int rc = check_launch(what);
-    if (rc != D3P_OK) return rc;
-    hipLaunchKernelGGL(k_pair_label_sums_merge, dim3((R + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, a);
-    return check_launch(what);
+    return pair_launch_merged(what, k_pair_label_sums, k_pair_label_sums_merge, (unsigned)groups, R, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

@@ -13,14 +13,15 @@
 //     (bits(q) << 32) | j
 // and the keys of one row are distinct: its k smallest keys are a SET that no order of visiting changes.  For t < k, ascending:
 //     q[i * k + t]     = the squared distance of the t-th smallest key
-//     dist[i * k + t]  = sqrtf of it, correctly rounded (the IEEE root, pk_sqrt below: not the native instruction's 1 ulp)
+//     dist[i * k + t]  = sqrtf of it, correctly rounded (the IEEE root, pair_sqrt: not the native instruction's 1 ulp)
 //     index[i * k + t] = its j           (among equal q the SMALLEST j comes first: the tie rule is on q, not on the rounded root)
 // and with fewer than k admissible j the places left hold +inf, +inf, 0xFFFFFFFF.  With qr_b (nb float32 squared radii) also
 //     count[i] = #{admissible j : q(i, j) < qr_b[j]}     strictly, by IEEE: a NaN radius contains nothing, +inf every finite q
 // A NaN or +-inf element in row i of a makes that row's outputs NaN, NaN, 0xFFFFFFFF and its count 0xFFFFFFFF and touches no other row;
 // one anywhere in b does the same to every row.  Both come from flags taken while the tables are staged, never from inf - inf.  Finite
 // elements whose t_c or q overflows float32 follow IEEE from there (q = inf, ties at inf go to the smallest j like any other tie).  At
-// k = 1 dist and index are d3p_pair_stats' min and argmin bit for bit: the chain, the tie rule and the root are the same.
+// k = 1 dist and index are d3p_pair_stats' min and argmin bit for bit: the chain, the admissible pairs, the key and the root are each
+// ONE function of d3p_pair_tile.h.
 //
 // THE SELECTION.  The walk is d3p_pair_stats': one wavefront computes a 32 x 32 pair tile (I, J), lane l = 8 ti + tj owning the 4 x 4
 // pairs (32 I + ti + 8 ki, 32 J + tj + 8 kj) in registers across chunks of C = 32 columns staged in the wavefront's own LDS (2 x 32 x
@@ -59,12 +60,8 @@
 #include "d3p_pair_tile.h"
 
 #define D3P_PK_KMAX 16               // the largest k: the largest capacity class
-#define D3P_PK_FORM_WIDE 1
-#define D3P_PK_FORM_SPLIT 2
-#define D3P_PK_WIDE_MIN_TILES 1024u  // the wide form is chosen where the tiles of a alone fill the chip: 256 CUs x 4 resident workgroups
 #define D3P_PK_MIN_G 16u             // tiles of b per segment, at least (a multiple of the slots)
 #define D3P_PK_MAX_GROUPS 4096u      // workgroups of the split form, at most: bounds the workspace
-#define D3P_PK_NONE 0xFFFFFFFFFFFFFFFFull
 
 static int32_t g_pk_form = 0;   // d3p_pair_knn_set_form: 0 = the rule below
 
@@ -78,19 +75,6 @@ struct PkArgs {
     pk_key* ws_key; uint32_t* ws_count; uint32_t* ws_flag;
 };
 
-// the items of one table: its n rows
-struct PkItems {
-    typedef uint64_t index;
-    const uint32_t* base; int64_t ld; uint32_t n;
-    __device__ __forceinline__ bool live(uint64_t row) const { return row < n; }
-    __device__ __forceinline__ uint32_t word(uint64_t row, uint32_t col) const { return base[(int64_t)row * ld + col]; }
-};
-
-// the IEEE root (d3p_pair_stats.hip's ps_sqrt: correctly rounded under the compiler's default -fhip-fp32-correctly-rounded-divide-sqrt)
-__device__ __forceinline__ float pk_sqrt(float q) { return __builtin_sqrtf(q); }
-
-__device__ __forceinline__ pk_key pk_make(float q, uint64_t j) { return ((pk_key)__float_as_uint(q) << 32) | (pk_key)j; }
-
 // the sorted list of a row in K places: the first K - k hold the key 0, which nothing sinks below, so the row's k smallest keys lie in
 // the LAST k places and the threshold is always place K - 1.  Every index is a constant after unrolling, so the list stays in registers
 // (a select of place k - 1 out of the K is turned into an indexed read by the compiler, and the list into scratch).  A pair whose key
@@ -101,7 +85,7 @@ struct PkList {
     __device__ __forceinline__ void clear(uint32_t k)
     {
 #pragma unroll
-        for (int t = 0; t < K; ++t) v[t] = (uint32_t)t < (uint32_t)K - k ? 0ull : D3P_PK_NONE;
+        for (int t = 0; t < K; ++t) v[t] = (uint32_t)t < (uint32_t)K - k ? 0ull : D3P_PAIR_NONE;
     }
     // the branch-free chain: key sinks to its place, the largest of the K + 1 falls out
     __device__ __forceinline__ void insert(pk_key key)
@@ -125,8 +109,8 @@ __device__ __forceinline__ void pk_walk(const PkArgs& a, uint32_t I, uint32_t j_
 {
     const uint32_t ti = (uint32_t)lane >> 3, tj = (uint32_t)lane & 7u;
     bool bad_a = false;   // (the rows' flags go to aflag)
-    const PkItems rows_a = {a.a, a.a_ld, a.na}, rows_b = {a.b, a.b_ld, a.nb};
-    pk_key thr[4] = {D3P_PK_NONE, D3P_PK_NONE, D3P_PK_NONE, D3P_PK_NONE};   // of rows ti + 8 ki
+    const PairRows rows_a = {a.a, a.a_ld, a.na}, rows_b = {a.b, a.b_ld, a.nb};
+    pk_key thr[4] = {D3P_PAIR_NONE, D3P_PAIR_NONE, D3P_PAIR_NONE, D3P_PAIR_NONE};   // of rows ti + 8 ki
     for (uint32_t J = j_lo + slot; J < j_hi; J += D3P_PAIR_WAVES) {
         float q[4][4];
         pair_zero(q);
@@ -172,8 +156,8 @@ __device__ __forceinline__ void pk_walk(const PkArgs& a, uint32_t I, uint32_t j_
 #pragma unroll
             for (int kj = 0; kj < 4; ++kj) {
                 const uint64_t j = (uint64_t)J * D3P_PAIR_T + tj + 8u * kj;
-                const bool ok = j < a.nb && !(a.excl && j == i);
-                cand |= ok && pk_make(q[ki][kj], j) < thr[ki];
+                const bool ok = pair_admissible(i, j, a.nb, a.excl);
+                cand |= ok && pair_key(q[ki][kj], j) < thr[ki];
                 cnt[ki] += ok && q[ki][kj] < rad[kj] ? 1u : 0u;
             }
         }
@@ -192,20 +176,14 @@ __device__ __forceinline__ void pk_walk(const PkArgs& a, uint32_t I, uint32_t j_
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const uint64_t j = (uint64_t)J * D3P_PAIR_T + c + (uint32_t)e;
-                    const pk_key key = pk_make(qs[e], j);
-                    if (j < a.nb && !(a.excl && j == i) && key < list.kth()) list.insert(key);
+                    const pk_key key = pair_key(qs[e], j);
+                    if (pair_admissible(i, j, a.nb, a.excl) && key < list.kth()) list.insert(key);
                 }
             }
         }
 #pragma unroll
         for (int ki = 0; ki < 4; ++ki) thr[ki] = __shfl(list.kth(), (int)(ti + 8u * ki), 64);   // (owner lanes: < 32)
     }
-}
-
-__device__ __forceinline__ uint32_t pk_row_count(uint32_t v)
-{
-    for (int off = 4; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // the outputs of row i from its k smallest keys, its count and its flags
@@ -218,10 +196,10 @@ __device__ __forceinline__ void pk_finish(const PkArgs& a, uint64_t i, const PkL
     for (int t = 0; t < K; ++t) {
         if ((uint32_t)t >= first) {
             const uint64_t o = i * a.k + ((uint32_t)t - first);
-            const bool none = list.v[t] == D3P_PK_NONE;
+            const bool none = list.v[t] == D3P_PAIR_NONE;
             const float qv = none ? __builtin_inff() : __uint_as_float((uint32_t)(list.v[t] >> 32));
             a.q[o] = bad ? nan : qv;
-            a.dist[o] = bad ? nan : pk_sqrt(qv);
+            a.dist[o] = bad ? nan : pair_sqrt(qv);
             a.index[o] = bad || none ? 0xFFFFFFFFu : (uint32_t)(list.v[t] & 0xFFFFFFFFull);
         }
     }
@@ -241,22 +219,18 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_knn(PkArgs a)
     float* A = lds[wave][0];
     float* B = lds[wave][1];
     uint32_t* aflag = slot_aflag[wave];
-    const uint32_t ntb = (uint32_t)(((uint64_t)a.nb + D3P_PAIR_T - 1u) / D3P_PAIR_T);
-    const uint32_t I = FORM == D3P_PK_FORM_WIDE ? blockIdx.x : blockIdx.x / a.nseg;
-    const uint32_t seg = FORM == D3P_PK_FORM_WIDE ? 0u : blockIdx.x % a.nseg;
-    const uint32_t j_lo = FORM == D3P_PK_FORM_WIDE ? 0u : seg * a.seg_tiles;                       // nseg * seg_tiles < ntb + seg_tiles: no wrap
-    const uint32_t j_hi = FORM == D3P_PK_FORM_WIDE || ntb - j_lo < a.seg_tiles ? ntb : j_lo + a.seg_tiles;
+    const uint32_t ntb = pair_tiles(a.nb);
+    const uint32_t I = FORM == D3P_PAIR_FORM_WIDE ? blockIdx.x : pair_split_tile(a.nseg);
+    const uint32_t seg = FORM == D3P_PAIR_FORM_WIDE ? 0u : pair_split_segment(a.nseg);
+    const uint32_t j_lo = FORM == D3P_PAIR_FORM_WIDE ? 0u : seg * a.seg_tiles;                       // nseg * seg_tiles < ntb + seg_tiles: no wrap
+    const uint32_t j_hi = FORM == D3P_PAIR_FORM_WIDE || ntb - j_lo < a.seg_tiles ? ntb : j_lo + a.seg_tiles;
     if (lane < D3P_PAIR_T) aflag[lane] = 0u;
     pair_wave_sync();
     const bool a_resident = a.d <= D3P_PAIR_C;
     bool bad_b = false;
-    if (a_resident) {   // one chunk: tile I of a is staged once, by every wavefront for itself
-        const int lw = pair_lanes_log2(a.d);
-        uint32_t wa[16];
+    if (a_resident) {
         bool bad_a = false;
-        pair_load(PkItems{a.a, a.a_ld, a.na}, I, 0u, a.d, lw, lane, wa);
-        pair_store(a.dtype, A, aflag, lw, lane, wa, bad_a);
-        pair_wave_sync();
+        pair_stage_resident(PairRows{a.a, a.a_ld, a.na}, I, a.d, a.dtype, A, aflag, lane, bad_a);
     }
     PkList<K> list;
     list.clear(a.k);
@@ -264,7 +238,7 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_knn(PkArgs a)
     pk_walk<K>(a, I, j_lo, j_hi, (uint32_t)wave, A, B, aflag, a_resident, lane, list, cnt, bad_b);
 #pragma unroll
     for (int ki = 0; ki < 4; ++ki) {
-        const uint32_t c = pk_row_count(cnt[ki]);
+        const uint32_t c = pair_row_reduce(cnt[ki], PairSum());
         if (tj == 0) slot_count[wave][ti + 8u * ki] = c;
     }
     bad_b = __builtin_amdgcn_ballot_w64(bad_b) != 0ull;
@@ -288,15 +262,15 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_knn(PkArgs a)
                 fa |= slot_aflag[w][threadIdx.x];
                 fb |= slot_bflag[w];
             }
-            if (FORM == D3P_PK_FORM_WIDE) {
+            if (FORM == D3P_PAIR_FORM_WIDE) {
                 pk_finish<K>(a, i, all, count, (fa | fb) != 0u);
             } else {
-                const uint64_t cell = (uint64_t)seg * a.na + i;
+                const uint64_t cell = pair_cell(seg, a.na, i);
 #pragma unroll
                 for (int t = 0; t < K; ++t)
                     if ((uint32_t)t >= (uint32_t)K - a.k) a.ws_key[cell * a.k + ((uint32_t)t - ((uint32_t)K - a.k))] = all.v[t];
                 a.ws_count[cell] = count;
-                a.ws_flag[cell] = fa | (fb << 1);
+                a.ws_flag[cell] = pair_flag_word(fa, fb);
             }
         }
     }
@@ -312,7 +286,7 @@ __global__ __launch_bounds__(256) void k_pair_knn_merge(PkArgs a)
     all.clear(a.k);
     uint32_t count = 0u, flags = 0u;
     for (uint32_t seg = 0; seg < a.nseg; ++seg) {
-        const uint64_t cell = (uint64_t)seg * a.na + i;
+        const uint64_t cell = pair_cell(seg, a.na, i);
         for (uint32_t t = 0; t < a.k; ++t) {
             const pk_key key = a.ws_key[cell * a.k + t];
             if (key < all.kth()) all.insert(key);
@@ -323,8 +297,6 @@ __global__ __launch_bounds__(256) void k_pair_knn_merge(PkArgs a)
     pk_finish<K>(a, i, all, count, flags != 0u);
 }
 
-static uint32_t pk_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + D3P_PAIR_T - 1u) / D3P_PAIR_T); }
-
 static uint32_t pk_capacity(uint32_t k) { return k <= 1u ? 1u : k <= 4u ? 4u : k <= 8u ? 8u : 16u; }
 
 static bool pk_admissible(uint32_t na, uint32_t nb, uint32_t d, uint32_t k) { return na >= 1 && nb >= 1 && d >= 1 && k >= 1 && k <= D3P_PK_KMAX; }
@@ -332,7 +304,7 @@ static bool pk_admissible(uint32_t na, uint32_t nb, uint32_t d, uint32_t k) { re
 // tiles of b per segment of the split form: at most D3P_PK_MAX_GROUPS workgroups in all, a multiple of the slots, at least D3P_PK_MIN_G
 static uint32_t pk_segment_tiles(uint32_t na, uint32_t nb)
 {
-    const uint32_t ta = pk_tiles(na), tb = pk_tiles(nb);
+    const uint32_t ta = pair_tiles(na), tb = pair_tiles(nb);
     const uint32_t most = ta >= D3P_PK_MAX_GROUPS ? 1u : D3P_PK_MAX_GROUPS / ta;   // segments, at most
     uint32_t g = (tb + most - 1u) / most;                                          // <= 2^27
     g = (g + D3P_PAIR_WAVES - 1u) / D3P_PAIR_WAVES * D3P_PAIR_WAVES;
@@ -342,37 +314,30 @@ static uint32_t pk_segment_tiles(uint32_t na, uint32_t nb)
 static uint32_t pk_segments(uint32_t na, uint32_t nb)
 {
     const uint32_t g = pk_segment_tiles(na, nb);
-    return (pk_tiles(nb) + g - 1u) / g;
+    return (pair_tiles(nb) + g - 1u) / g;
 }
 
 static uint32_t pk_form(uint32_t na, uint32_t nb, uint32_t d, uint32_t k)
 {
     if (!pk_admissible(na, nb, d, k)) return 0;
-    if (pk_tiles(na) > D3P_PK_MAX_GROUPS) return D3P_PK_FORM_WIDE;   // nothing to deal out, and the cells would not be bounded
-    if (g_pk_form) return (uint32_t)g_pk_form;
-    // the split form where the tiles of a alone cannot fill the chip and b has more than one segment to deal out; the forms agree bit
-    // for bit, so the choice may look at na
-    return pk_tiles(na) < D3P_PK_WIDE_MIN_TILES && pk_segments(na, nb) > 1u ? D3P_PK_FORM_SPLIT : D3P_PK_FORM_WIDE;
+    if (pair_tiles(na) > D3P_PK_MAX_GROUPS) return D3P_PAIR_FORM_WIDE;   // nothing to deal out, and the cells would not be bounded
+    return pair_form(g_pk_form, pair_tiles(na), pk_segments(na, nb));
 }
 
 static size_t pk_workspace(uint32_t na, uint32_t nb, uint32_t d, uint32_t k)
 {
-    if (pk_form(na, nb, d, k) != D3P_PK_FORM_SPLIT) return 0;
+    if (pk_form(na, nb, d, k) != D3P_PAIR_FORM_SPLIT) return 0;
     return (size_t)pk_segments(na, nb) * (size_t)na * (8u * (size_t)k + 8u);   // <= 4096 x 32 x 136
 }
 
 template <int K>
 static int pk_launch(const char* what, uint32_t form, unsigned groups, hipStream_t stream, const PkArgs& a)
 {
-    if (form == D3P_PK_FORM_WIDE) {
-        hipLaunchKernelGGL((k_pair_knn<D3P_PK_FORM_WIDE, K>), dim3(groups), dim3(64 * D3P_PAIR_WAVES), 0, stream, a);
+    if (form == D3P_PAIR_FORM_WIDE) {
+        hipLaunchKernelGGL((k_pair_knn<D3P_PAIR_FORM_WIDE, K>), dim3(groups), dim3(64 * D3P_PAIR_WAVES), 0, stream, a);
         return check_launch(what);
     }
-    hipLaunchKernelGGL((k_pair_knn<D3P_PK_FORM_SPLIT, K>), dim3(groups), dim3(64 * D3P_PAIR_WAVES), 0, stream, a);
-    const int rc = check_launch(what);
-    if (rc != D3P_OK) return rc;
-    hipLaunchKernelGGL((k_pair_knn_merge<K>), dim3((unsigned)(((uint64_t)a.na + 255u) / 256u)), dim3(256), 0, stream, a);
-    return check_launch(what);
+    return pair_launch_merged(what, k_pair_knn<D3P_PAIR_FORM_SPLIT, K>, k_pair_knn_merge<K>, groups, a.na, stream, a);
 }
 
 }  // namespace d3p
@@ -398,13 +363,7 @@ uint32_t d3p_pair_knn_segment_tiles(uint32_t na, uint32_t nb, uint32_t d, uint32
     return pk_admissible(na, nb, d, k) ? pk_segment_tiles(na, nb) : 0u;
 }
 
-int d3p_pair_knn_set_form(int32_t form)
-{
-    if (form != 0 && form != D3P_PK_FORM_WIDE && form != D3P_PK_FORM_SPLIT)
-        return fail(D3P_E_INVALID_ARG, "d3p_pair_knn_set_form: form must be 0 (the rule), 1 (wide) or 2 (split), got %d", form);
-    g_pk_form = form;
-    return D3P_OK;
-}
+int d3p_pair_knn_set_form(int32_t form) { return pair_set_form("d3p_pair_knn_set_form", form, &g_pk_form); }
 
 int d3p_pair_knn(void* stream, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld, uint32_t na, uint32_t nb,
                  uint32_t d, uint32_t k, int32_t exclude_diagonal, const float* qr_b_dev, float* q_dev, float* dist_dev, uint32_t* index_dev,
@@ -416,25 +375,16 @@ int d3p_pair_knn(void* stream, const void* a_dev, const void* b_dev, int32_t dty
           (uintptr_t)count_dev) & 3u) != 0)
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if (((uintptr_t)ws_dev & 7u) != 0) return fail(D3P_E_INVALID_ARG, "%s: ws_dev is not aligned to 8 bytes", what);
-    if (dtype != 0 && dtype != 1) return fail(D3P_E_INVALID_ARG, "%s: dtype must be 0 (float32) or 1 (int32), got %d", what, dtype);
-    if (na < 1 || nb < 1) return fail(D3P_E_INVALID_ARG, "%s: na >= 1 and nb >= 1 are required", what);
-    if (d < 1) return fail(D3P_E_INVALID_ARG, "%s: d >= 1 is required", what);
-    if (a_ld < 0 || (uint64_t)a_ld < d) return fail(D3P_E_INVALID_ARG, "%s: a_ld >= d is required", what);
-    if (b_ld < 0 || (uint64_t)b_ld < d) return fail(D3P_E_INVALID_ARG, "%s: b_ld >= d is required", what);
-    if ((uint64_t)na > (uint64_t)INT64_MAX / (uint64_t)a_ld || (uint64_t)nb > (uint64_t)INT64_MAX / (uint64_t)b_ld)
-        return fail(D3P_E_INVALID_ARG, "%s: na * a_ld or nb * b_ld does not fit 63 bits", what);
+    if (const int rc = pair_check_pair(what, dtype, a_ld, b_ld, na, nb, d)) return rc;
     if (k < 1 || k > D3P_PK_KMAX) return fail(D3P_E_INVALID_ARG, "%s: 1 <= k <= %d is required, got %u", what, D3P_PK_KMAX, k);
-    if (exclude_diagonal != 0 && exclude_diagonal != 1)
-        return fail(D3P_E_INVALID_ARG, "%s: exclude_diagonal must be 0 or 1, got %d", what, exclude_diagonal);
-    if (exclude_diagonal && na != nb)
-        return fail(D3P_E_INVALID_ARG, "%s: exclude_diagonal compares a table with itself: na == nb is required (%u, %u)", what, na, nb);
+    if (const int rc = pair_check_diagonal(what, exclude_diagonal, na, nb)) return rc;
     const uint32_t form = pk_form(na, nb, d, k);
     const size_t need = pk_workspace(na, nb, d, k);
     if (ws_bytes < need || (need && !ws_dev))
         return fail(D3P_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", what, ws_dev ? ws_bytes : (size_t)0, need);
     const uint32_t nseg = pk_segments(na, nb);
     // one workgroup per tile of a (< 2^27) or, split, per tile and segment (<= D3P_PK_MAX_GROUPS + the tiles of a): no grid to refuse
-    const uint64_t groups = (uint64_t)pk_tiles(na) * (form == D3P_PK_FORM_SPLIT ? nseg : 1u);
+    const uint64_t groups = (uint64_t)pair_tiles(na) * (form == D3P_PAIR_FORM_SPLIT ? nseg : 1u);
     if (!is_device_ptr(a_dev) || !is_device_ptr(b_dev) || !is_device_ptr(q_dev) || !is_device_ptr(dist_dev) || !is_device_ptr(index_dev) ||
         (qr_b_dev && (!is_device_ptr(qr_b_dev) || !is_device_ptr(count_dev))) || (need && !is_device_ptr(ws_dev)))
         return fail(D3P_E_INVALID_ARG, "%s: the tables, the radii, the outputs and the workspace must be device memory", what);

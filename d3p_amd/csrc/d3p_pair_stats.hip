@@ -8,9 +8,9 @@
 // (dtype 0) or both int32 (dtype 1: converted to float32 when staged, exact for |v| <= 2^24, which is what the Python layer admits).
 // For a pair of rows (i, j):
 //     t_c = fl32(a_c - b_c)      q = the float32 fmaf chain q <- fmaf(t_c, t_c, q) over c = 0 .. d-1 ascending, from q = 0
-//     dist = sqrtf(q), correctly rounded (the IEEE root: ps_sqrt below, not the native instruction's 1 ulp)
-// which is the chain of d3p_energy.hip: both walk the tile of d3p_pair_tile.h.  The ADMISSIBLE j of row i are all j < nb, without j == i when
-// exclude_diagonal is set (which requires na == nb); duplicate rows are pairs like any other.  Over the admissible j:
+//     dist = sqrtf(q), correctly rounded (the IEEE root: pair_sqrt, not the native instruction's 1 ulp)
+// which is the chain and the root of d3p_energy.hip: both are d3p_pair_tile.h's.  The ADMISSIBLE j of row i are all j < nb, without
+// j == i when exclude_diagonal is set (which requires na == nb); duplicate rows are pairs like any other.  Over the admissible j:
 //     sum[i]    = sum_j (double)dist(i, j)     in float64, in the order below, not rounded further
 //     min[i]    = sqrtf(q_min),  q_min the smallest q
 //     argmin[i] = the SMALLEST j whose q equals q_min   (the tie rule is on q, not on the rounded root)
@@ -50,10 +50,6 @@
 #include "d3p_pair_tile.h"
 
 #define D3P_PS_G 16          // tiles of b per segment (a multiple of the slots)
-#define D3P_PS_FORM_WIDE 1
-#define D3P_PS_FORM_SPLIT 2
-#define D3P_PS_WIDE_MIN_TILES 1024u  // the wide form is chosen where the tiles of a alone fill the chip: 256 CUs x 4 resident workgroups
-#define D3P_PS_NONE 0xFFFFFFFFFFFFFFFFull
 #define D3P_PS_CELL 20u      // bytes per (segment, row) of the split form: a double, a packed minimum, a flag word
 
 static int32_t g_ps_form = 0;   // d3p_pair_stats_set_form: 0 = the rule below
@@ -66,29 +62,16 @@ struct PsArgs {
     double* ws_sum; unsigned long long* ws_min; uint32_t* ws_flag;
 };
 
-// the items of one table: its n rows
-struct PsItems {
-    typedef uint64_t index;
-    const uint32_t* base; int64_t ld; uint32_t n;
-    __device__ __forceinline__ bool live(uint64_t row) const { return row < n; }
-    __device__ __forceinline__ uint32_t word(uint64_t row, uint32_t col) const { return base[(int64_t)row * ld + col]; }
-};
-
-// the IEEE root.  sqrtf is correctly rounded under the compiler's default -fhip-fp32-correctly-rounded-divide-sqrt; the rounded-root
-// intrinsic of this toolchain's headers is the NATIVE instruction (1 ulp) unless OCML_BASIC_ROUNDED_OPERATIONS is defined, which the
-// by-value tests of non-square q tell apart
-__device__ __forceinline__ float ps_sqrt(float q) { return __builtin_sqrtf(q); }
-
 // the tiles of one slot of one segment against tile I of a: adds onto the lane's four sums, lowers its four packed minima, ors bad_b.
 // With a_resident (d <= C) tile I of a already lies in A.
 __device__ __forceinline__ void ps_segment_slot(const PsArgs& a, uint32_t I, uint32_t seg, uint32_t slot, float* A, float* B, uint32_t* aflag,
                                                 bool a_resident, int lane, double (&ls)[4], unsigned long long (&pm)[4], bool& bad_b)
 {
-    const uint32_t ntb = (uint32_t)(((uint64_t)a.nb + D3P_PAIR_T - 1u) / D3P_PAIR_T);
+    const uint32_t ntb = pair_tiles(a.nb);
     const uint32_t j_lo = seg * D3P_PS_G, j_hi = ntb - j_lo < D3P_PS_G ? ntb : j_lo + D3P_PS_G;
     const uint32_t ti = (uint32_t)lane >> 3, tj = (uint32_t)lane & 7u;
     bool bad_a = false;   // (the rows' flags go to aflag)
-    const PsItems rows_a = {a.a, a.a_ld, a.na}, rows_b = {a.b, a.b_ld, a.nb};
+    const PairRows rows_a = {a.a, a.a_ld, a.na}, rows_b = {a.b, a.b_ld, a.nb};
     for (uint32_t J = j_lo + slot; J < j_hi; J += D3P_PAIR_WAVES) {
         float q[4][4];
         pair_zero(q);
@@ -124,39 +107,24 @@ __device__ __forceinline__ void ps_segment_slot(const PsArgs& a, uint32_t I, uin
 #pragma unroll
             for (int kj = 0; kj < 4; ++kj) {
                 const uint64_t j = (uint64_t)J * D3P_PAIR_T + tj + 8u * kj;
-                const bool ok = j < a.nb && !(a.excl && j == i);
+                const bool ok = pair_admissible(i, j, a.nb, a.excl);
                 const float qv = q[ki][kj];
-                const double dist = (double)ps_sqrt(qv);
+                const double dist = (double)pair_sqrt(qv);
                 ls[ki] += ok ? dist : 0.0;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(qv) << 32) | (unsigned long long)j;
+                const unsigned long long key = pair_key(qv, j);
                 pm[ki] = ok && key < pm[ki] ? key : pm[ki];
             }
         }
     }
 }
 
-__device__ __forceinline__ double ps_row_sum(double v)
-{
-    for (int off = 4; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long ps_row_min(unsigned long long v)
-{
-    for (int off = 4; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 // the three outputs of row i from its float64 sum, its packed minimum and its flags
 __device__ __forceinline__ void ps_finish(const PsArgs& a, uint64_t i, double total, unsigned long long key, bool bad)
 {
     const float nan = __builtin_nanf("");
-    const bool none = key == D3P_PS_NONE;
+    const bool none = key == D3P_PAIR_NONE;
     a.sum[i] = bad ? (double)nan : total;
-    a.min[i] = bad ? nan : none ? __builtin_inff() : ps_sqrt(__uint_as_float((uint32_t)(key >> 32)));
+    a.min[i] = bad ? nan : none ? __builtin_inff() : pair_sqrt(__uint_as_float((uint32_t)(key >> 32)));
     a.argmin[i] = bad || none ? 0xFFFFFFFFu : (uint32_t)(key & 0xFFFFFFFFull);
 }
 
@@ -173,22 +141,18 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_stats(PsArgs a)
     float* A = lds[wave][0];
     float* B = lds[wave][1];
     uint32_t* aflag = slot_aflag[wave];
-    const uint32_t I = FORM == D3P_PS_FORM_WIDE ? blockIdx.x : blockIdx.x / a.nseg;
-    const uint32_t seg_lo = FORM == D3P_PS_FORM_WIDE ? 0u : blockIdx.x % a.nseg;
-    const uint32_t seg_hi = FORM == D3P_PS_FORM_WIDE ? a.nseg : seg_lo + 1u;
+    const uint32_t I = FORM == D3P_PAIR_FORM_WIDE ? blockIdx.x : pair_split_tile(a.nseg);
+    const uint32_t seg_lo = FORM == D3P_PAIR_FORM_WIDE ? 0u : pair_split_segment(a.nseg);
+    const uint32_t seg_hi = FORM == D3P_PAIR_FORM_WIDE ? a.nseg : seg_lo + 1u;
     if (lane < D3P_PAIR_T) aflag[lane] = 0u;
     pair_wave_sync();
     const bool a_resident = a.d <= D3P_PAIR_C;
     bool bad_b = false;
-    if (a_resident) {   // one chunk: tile I of a is staged once, by every wavefront for itself
-        const int lw = pair_lanes_log2(a.d);
-        uint32_t wa[16];
+    if (a_resident) {
         bool bad_a = false;
-        pair_load(PsItems{a.a, a.a_ld, a.na}, I, 0u, a.d, lw, lane, wa);
-        pair_store(a.dtype, A, aflag, lw, lane, wa, bad_a);
-        pair_wave_sync();
+        pair_stage_resident(PairRows{a.a, a.a_ld, a.na}, I, a.d, a.dtype, A, aflag, lane, bad_a);
     }
-    unsigned long long pm[4] = {D3P_PS_NONE, D3P_PS_NONE, D3P_PS_NONE, D3P_PS_NONE};
+    unsigned long long pm[4] = {D3P_PAIR_NONE, D3P_PAIR_NONE, D3P_PAIR_NONE, D3P_PAIR_NONE};
     double total = 0.0;   // (threads 0 .. 31: row 32 I + threadIdx.x)
     for (uint32_t seg = seg_lo; seg < seg_hi; ++seg) {
         double ls[4] = {0.0, 0.0, 0.0, 0.0};
@@ -196,7 +160,7 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_stats(PsArgs a)
         const uint32_t par = seg & 1u;
 #pragma unroll
         for (int ki = 0; ki < 4; ++ki) {
-            const double s = ps_row_sum(ls[ki]);
+            const double s = pair_row_reduce(ls[ki], PairSum());
             if (tj == 0) slot_sum[par][wave][ti + 8u * ki] = s;
         }
         // one barrier per segment: the sums of segment s + 2 are written after the barrier of segment s + 1, which follows the reads below
@@ -209,7 +173,7 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_stats(PsArgs a)
     }
 #pragma unroll
     for (int ki = 0; ki < 4; ++ki) {
-        const unsigned long long m = ps_row_min(pm[ki]);
+        const unsigned long long m = pair_row_reduce(pm[ki], PairMin());
         if (tj == 0) slot_min[wave][ti + 8u * ki] = m;
     }
     bad_b = __builtin_amdgcn_ballot_w64(bad_b) != 0ull;
@@ -218,20 +182,20 @@ __global__ __launch_bounds__(64 * D3P_PAIR_WAVES) void k_pair_stats(PsArgs a)
     if (threadIdx.x < D3P_PAIR_T) {
         const uint64_t i = (uint64_t)I * D3P_PAIR_T + threadIdx.x;
         if (i < a.na) {
-            unsigned long long key = D3P_PS_NONE;
+            unsigned long long key = D3P_PAIR_NONE;
             uint32_t fa = 0u, fb = 0u;
             for (int w = 0; w < D3P_PAIR_WAVES; ++w) {
                 key = slot_min[w][threadIdx.x] < key ? slot_min[w][threadIdx.x] : key;
                 fa |= slot_aflag[w][threadIdx.x];
                 fb |= slot_bflag[w];
             }
-            if (FORM == D3P_PS_FORM_WIDE) {
+            if (FORM == D3P_PAIR_FORM_WIDE) {
                 ps_finish(a, i, total, key, (fa | fb) != 0u);
             } else {
-                const uint64_t cell = (uint64_t)seg_lo * a.na + i;
+                const uint64_t cell = pair_cell(seg_lo, a.na, i);
                 a.ws_sum[cell] = total;
                 a.ws_min[cell] = key;
-                a.ws_flag[cell] = fa | (fb << 1);
+                a.ws_flag[cell] = pair_flag_word(fa, fb);
             }
         }
     }
@@ -243,10 +207,10 @@ __global__ __launch_bounds__(256) void k_pair_stats_merge(PsArgs a)
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= a.na) return;
     double total = 0.0;
-    unsigned long long key = D3P_PS_NONE;
+    unsigned long long key = D3P_PAIR_NONE;
     uint32_t flags = 0u;
     for (uint32_t seg = 0; seg < a.nseg; ++seg) {
-        const uint64_t cell = (uint64_t)seg * a.na + i;
+        const uint64_t cell = pair_cell(seg, a.na, i);
         total += a.ws_sum[cell];
         key = a.ws_min[cell] < key ? a.ws_min[cell] : key;
         flags |= a.ws_flag[cell];
@@ -254,22 +218,17 @@ __global__ __launch_bounds__(256) void k_pair_stats_merge(PsArgs a)
     ps_finish(a, i, total, key, flags != 0u);
 }
 
-static uint32_t ps_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + D3P_PAIR_T - 1u) / D3P_PAIR_T); }
-
-static uint32_t ps_segments(uint32_t nb) { return (ps_tiles(nb) + D3P_PS_G - 1u) / D3P_PS_G; }
+static uint32_t ps_segments(uint32_t nb) { return (pair_tiles(nb) + D3P_PS_G - 1u) / D3P_PS_G; }
 
 static uint32_t ps_form(uint32_t na, uint32_t nb, uint32_t d)
 {
     if (na < 1 || nb < 1 || d < 1) return 0;
-    if (g_ps_form) return (uint32_t)g_ps_form;
-    // the split form where the tiles of a alone cannot fill the chip and b has more than one segment to deal out; the forms agree bit
-    // for bit, so the choice may look at na
-    return ps_tiles(na) < D3P_PS_WIDE_MIN_TILES && ps_segments(nb) > 1u ? D3P_PS_FORM_SPLIT : D3P_PS_FORM_WIDE;
+    return pair_form(g_ps_form, pair_tiles(na), ps_segments(nb));
 }
 
 static size_t ps_workspace(uint32_t na, uint32_t nb, uint32_t d)
 {
-    if (ps_form(na, nb, d) != D3P_PS_FORM_SPLIT) return 0;
+    if (ps_form(na, nb, d) != D3P_PAIR_FORM_SPLIT) return 0;
     return (size_t)ps_segments(nb) * (size_t)na * D3P_PS_CELL;   // < 2^23 x 2^32 x 20: no wrap
 }
 
@@ -289,13 +248,7 @@ uint32_t d3p_pair_stats_form(uint32_t na, uint32_t nb, uint32_t d) { return ps_f
 
 size_t d3p_pair_stats_workspace(uint32_t na, uint32_t nb, uint32_t d) { return ps_workspace(na, nb, d); }
 
-int d3p_pair_stats_set_form(int32_t form)
-{
-    if (form != 0 && form != D3P_PS_FORM_WIDE && form != D3P_PS_FORM_SPLIT)
-        return fail(D3P_E_INVALID_ARG, "d3p_pair_stats_set_form: form must be 0 (the rule), 1 (wide) or 2 (split), got %d", form);
-    g_ps_form = form;
-    return D3P_OK;
-}
+int d3p_pair_stats_set_form(int32_t form) { return pair_set_form("d3p_pair_stats_set_form", form, &g_ps_form); }
 
 int d3p_pair_stats(void* stream, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld, uint32_t na, uint32_t nb,
                    uint32_t d, int32_t exclude_diagonal, double* sum_dev, float* min_dev, uint32_t* argmin_dev, void* ws_dev, size_t ws_bytes)
@@ -306,22 +259,13 @@ int d3p_pair_stats(void* stream, const void* a_dev, const void* b_dev, int32_t d
         return fail(D3P_E_INVALID_ARG, "%s: a pointer is not aligned to 4 bytes", what);
     if ((((uintptr_t)sum_dev | (uintptr_t)ws_dev) & 7u) != 0)
         return fail(D3P_E_INVALID_ARG, "%s: sum_dev or ws_dev is not aligned to 8 bytes", what);
-    if (dtype != 0 && dtype != 1) return fail(D3P_E_INVALID_ARG, "%s: dtype must be 0 (float32) or 1 (int32), got %d", what, dtype);
-    if (na < 1 || nb < 1) return fail(D3P_E_INVALID_ARG, "%s: na >= 1 and nb >= 1 are required", what);
-    if (d < 1) return fail(D3P_E_INVALID_ARG, "%s: d >= 1 is required", what);
-    if (a_ld < 0 || (uint64_t)a_ld < d) return fail(D3P_E_INVALID_ARG, "%s: a_ld >= d is required", what);
-    if (b_ld < 0 || (uint64_t)b_ld < d) return fail(D3P_E_INVALID_ARG, "%s: b_ld >= d is required", what);
-    if ((uint64_t)na > (uint64_t)INT64_MAX / (uint64_t)a_ld || (uint64_t)nb > (uint64_t)INT64_MAX / (uint64_t)b_ld)
-        return fail(D3P_E_INVALID_ARG, "%s: na * a_ld or nb * b_ld does not fit 63 bits", what);
-    if (exclude_diagonal != 0 && exclude_diagonal != 1)
-        return fail(D3P_E_INVALID_ARG, "%s: exclude_diagonal must be 0 or 1, got %d", what, exclude_diagonal);
-    if (exclude_diagonal && na != nb)
-        return fail(D3P_E_INVALID_ARG, "%s: exclude_diagonal compares a table with itself: na == nb is required (%u, %u)", what, na, nb);
+    if (const int rc = pair_check_pair(what, dtype, a_ld, b_ld, na, nb, d)) return rc;
+    if (const int rc = pair_check_diagonal(what, exclude_diagonal, na, nb)) return rc;
     const uint32_t form = ps_form(na, nb, d);
     const size_t need = ps_workspace(na, nb, d);
     if (ws_bytes < need || (need && !ws_dev))
         return fail(D3P_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", what, ws_dev ? ws_bytes : (size_t)0, need);
-    const uint64_t groups = (uint64_t)ps_tiles(na) * (form == D3P_PS_FORM_SPLIT ? ps_segments(nb) : 1u);
+    const uint64_t groups = (uint64_t)pair_tiles(na) * (form == D3P_PAIR_FORM_SPLIT ? ps_segments(nb) : 1u);
     if (groups > 0x7fffffffull) return fail(D3P_E_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (one per tile of a and segment of b)", what);
     if (!is_device_ptr(a_dev) || !is_device_ptr(b_dev) || !is_device_ptr(sum_dev) || !is_device_ptr(min_dev) || !is_device_ptr(argmin_dev) ||
         (need && !is_device_ptr(ws_dev)))
@@ -334,15 +278,11 @@ int d3p_pair_stats(void* stream, const void* a_dev, const void* b_dev, int32_t d
     a.ws_sum = static_cast<double*>(ws_dev);
     a.ws_min = need ? reinterpret_cast<unsigned long long*>(static_cast<char*>(ws_dev) + 8u * cells) : nullptr;
     a.ws_flag = need ? reinterpret_cast<uint32_t*>(static_cast<char*>(ws_dev) + 16u * cells) : nullptr;
-    if (form == D3P_PS_FORM_WIDE) {
-        hipLaunchKernelGGL(k_pair_stats<D3P_PS_FORM_WIDE>, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
+    if (form == D3P_PAIR_FORM_WIDE) {
+        hipLaunchKernelGGL(k_pair_stats<D3P_PAIR_FORM_WIDE>, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
         return check_launch(what);
     }
-    hipLaunchKernelGGL(k_pair_stats<D3P_PS_FORM_SPLIT>, dim3((unsigned)groups), dim3(64 * D3P_PAIR_WAVES), 0, (hipStream_t)stream, a);
-    const int rc = check_launch(what);
-    if (rc != D3P_OK) return rc;
-    hipLaunchKernelGGL(k_pair_stats_merge, dim3((unsigned)(((uint64_t)na + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, a);
-    return check_launch(what);
+    return pair_launch_merged(what, k_pair_stats<D3P_PAIR_FORM_SPLIT>, k_pair_stats_merge, (unsigned)groups, na, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

@@ -1422,8 +1422,8 @@ int d3p_binary_curve(void* stream, const float* p_dev, const int32_t* y_dev, uin
  * draws_dev[s * ld_draw + r * ld_row + c] is draw s < n of row r < rows in column c < d (column stride 1), float32 (dtype 0) or int32
  * (dtype 1: converted to float32 when staged, which is exact for |v| <= 2^24; the Python layer refuses larger magnitudes);
  * y_dev[r * y_ld + c] the observation, of the same dtype.  For row r the items are z_0 .. z_{n-1} (the draws) and z_n = y_r; per pair
- *   t_c = fl32(a_c - b_c),  q = the float32 fmaf chain over c ascending from 0,  dist = the native root of q, widened to float64
- * (1 ulp, exact on perfect squares; the bound of tests/energy_ref.bound carries it; d3p_pair_stats below takes the IEEE root)
+ *   t_c = fl32(a_c - b_c),  q = the float32 fmaf chain over c ascending from 0,  dist = sqrtf(q), the IEEE root, widened to float64
+ * (the one root of d3p_pair_stats below: d3p_pair_tile.h's pair_sqrt; the bound of tests/energy_ref.bound allows it 1 ulp)
  * and with S1 = sum_i dist(z_i, y), S2 = sum_{i != j} dist(z_i, z_j) in float64 in the fixed order d3p_energy.hip states (each
  * unordered pair computed once, counted twice):
  *   out_dev[0 * out_ld + r] = es      = mae - spread

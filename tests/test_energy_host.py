@@ -226,9 +226,9 @@ def test_source_text_rules():
     header = text[:text.index("#include")]
     for said in ("THE RULE", "THE ORDER", "DETERMINISM", "fmaf chain", "2^24", "follow IEEE", "NaN or +-inf", "bit for bit", "Gram matrix"):
         assert said in header, said
-    # the chain is the tile's (tests/test_fidelity_host.py pins its text there); the root is this file's own
+    # the chain and the root are the tile's (tests/test_fidelity_host.py pins their text there): this file restates neither
     assert tile_code.count("__fmaf_rn(") == 4 and "__fmaf_rn(" not in code and "pair_chain(" in code
-    assert "__fsqrt_rn(" in code and "sqrtf(" not in code.replace("__fsqrt_rn(", "") and "sqrt" not in tile_code
+    assert code.count("pair_sqrt(") == 1 and "sqrtf(" not in code and "__fsqrt_rn" not in code and tile_code.count("sqrtf(") == 1
     assert not re.search(r"#define D3P_(ES|PS)_(T|C|LD|WAVES)\b", text)
     num = {k: int(re.search(r"#define D3P_PAIR_" + k + r" (\d+)", tile).group(1)) for k in ("T", "C", "LD", "WAVES")}
     lds = num["T"] * num["LD"] * 4 * 2 * num["WAVES"]

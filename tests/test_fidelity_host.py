@@ -208,8 +208,26 @@ def test_source_text_rules():
                  "SMALLEST j", "(bits(q) << 32) | j", "0xFFFFFFFF", "J mod 4", "butterfly 4, 2, 1", "ascending segment order", "exclude_diagonal",
                  "not on na", "the form"):
         assert said in header, said
-    # the IEEE root: this toolchain's __fsqrt_rn is the native instruction (1 ulp) unless OCML_BASIC_ROUNDED_OPERATIONS is defined
-    assert code.count("sqrtf(") == 1 and "__builtin_sqrtf(q)" in code and "__fsqrt_rn" not in code and "sqrt" not in tile_code
+    # the IEEE root, ONCE, in the tile's header: this toolchain's __fsqrt_rn goes to OCML's native root unless
+    # OCML_BASIC_ROUNDED_OPERATIONS is defined
+    assert tile_code.count("sqrtf(") == 1 and "pair_sqrt(float q) { return __builtin_sqrtf(q); }" in tile_code and "__fsqrt_rn" not in tile_code
+    assert "sqrtf(" not in code and "__fsqrt_rn" not in code and code.count("pair_sqrt(") == 2
+    # what the walkers share is stated in the header alone: no walker defines the items of a row table, a root, a tile count, a form
+    # rule with the chip's 1024 resident workgroups, the admissible pairs or the packed key of its own
+    assert tile_code.count("struct PairRows") == 1 and tile_code.count("D3P_PAIR_WIDE_MIN_TILES") == 2 and "1024u" in tile_code
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith(".hip"):
+            continue
+        src = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, name)).read().splitlines())
+        assert not re.search(r"\b(ps|pk|ls|es)_(sqrt|tiles|row_sum|row_min|row_count|make)\b|struct (Ps|Pk|Ls)Items\b", src), name
+        assert not re.search(r"uint32_t word\(uint64_t row, uint32_t col\)", src), name                     # an items struct of a row table
+        if '"d3p_pair_tile.h"' in src:
+            assert not re.search(r"\w+_sqrt\(float|\w+_tiles\(uint32_t \w+\) \{|_WIDE_MIN_TILES\s+\d|<\s*1024|_FORM_(WIDE|SPLIT) \d|_NONE 0x", src), name
+            assert "__builtin_sqrtf" not in src and "__fsqrt_rn" not in src and "__float_as_uint" not in src and "j == i" not in src, name
+    knn = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, "d3p_pair_knn.hip")).read().splitlines())
+    for name, src in (("d3p_pair_stats.hip", code), ("d3p_pair_knn.hip", knn)):
+        assert "pair_admissible(i, j, a.nb, a.excl)" in src and "pair_key(" in src and "D3P_PAIR_NONE" in src and "pair_form(g_p" in src, name
+        assert "pair_check_pair(what, dtype, a_ld, b_ld, na, nb, d)" in src and "pair_check_diagonal(what, exclude_diagonal, na, nb)" in src, name
     assert "native" not in code and "fast" not in code and "native" not in tile_code and "fast" not in tile_code
     num = {k: int(re.search(r"#define D3P_PAIR_" + k + r" (\d+)", tile).group(1)) for k in ("T", "C", "LD", "WAVES")}
     num["G"] = int(re.search(r"#define D3P_PS_G (\d+)", text).group(1))

@@ -94,6 +94,15 @@ def test_k_1_equals_pair_stats_bit_for_bit(form, TCS):
     for x, y, excl in ((a, b, False), (b, b, True)):
         ps, nn = F.pair_stats(x, y, excl), N.knn(x, y, 1, excl)
         assert torch.equal(nn["distance"][:, 0].view(torch.int32), ps["min"].view(torch.int32)) and torch.equal(nn["index"][:, 0], ps["argmin"])
+    # a partial tile on each side, two column chunks and the diagonal, both entries in the same forced form
+    c = torch.tensor(rng.normal(size=(T + 1, C + 1)).astype(np.float32)).cuda()
+    import d3p_amd._lib as L
+    try:
+        assert L.load().d3p_pair_stats_set_form(form) == 0
+        ps, nn = F.pair_stats(c, c, True), N.knn(c, c, 1, True)
+    finally:
+        assert L.load().d3p_pair_stats_set_form(0) == 0
+    assert torch.equal(nn["distance"][:, 0].view(torch.int32), ps["min"].view(torch.int32)) and torch.equal(nn["index"][:, 0], ps["argmin"])
 
 
 @pytest.mark.parametrize("name", ["normal", "d784", "far-cluster"])

@@ -79,6 +79,21 @@ def test_the_c_entry_refuses_on_the_host_as_declared(lib):
     assert not buf.any()
 
 
+def test_source_text_rules():
+    """What d3p_pair_knn.hip shares with d3p_pair_stats.hip it takes from d3p_pair_tile.h (tests/test_fidelity_host.py holds every walker
+    to that); what is its own stays: the guard of 4096 tiles ahead of the forced form, and k refused between the shape and the diagonal."""
+    import re
+    text = open(os.path.join(ROOT, "d3p_amd", "csrc", "d3p_pair_knn.hip")).read()
+    assert re.findall(r'#include "([^"]+)"', text) == ["d3p_device.h", "d3p_host.h", "d3p_pair_tile.h"]
+    code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    assert "sqrtf(" not in code and code.count("pair_sqrt(") == 1 and "__fmaf_rn(" not in code and "pair_chain(va[ki], vb[kj], q[ki][kj])" in code
+    assert code.count("pair_admissible(i, j, a.nb, a.excl)") == 2 and code.count("pair_key(") == 2 and "pk_make" not in code
+    assert not re.search(r"#define D3P_PK_(T|C|LD|WAVES|NONE|FORM_WIDE|FORM_SPLIT|WIDE_MIN_TILES)\b", text)
+    assert code.index("pair_tiles(na) > D3P_PK_MAX_GROUPS) return D3P_PAIR_FORM_WIDE") < code.index("pair_form(g_pk_form, pair_tiles(na), pk_segments(na, nb))")
+    assert code.index("pair_check_pair(") < code.index("1 <= k <= %d is required") < code.index("pair_check_diagonal(")
+    assert 'pair_set_form("d3p_pair_knn_set_form", form, &g_pk_form)' in code and "pair_launch_merged(" in code
+
+
 def test_python_layer_refuses_before_the_device(monkeypatch):
     import d3p_amd._lib as L
     from d3p_amd import neighbours as N

@@ -233,7 +233,11 @@ def test_source_text_rules():
                  "No floating-point atomics", "no scratch", "no dynamic LDS", "D_ii is exactly +0.0"):
         assert said in header, said
     # the IEEE root, once; the tile's chain, not a restatement of it; the tile's constants, not copies
-    assert code.count("sqrtf(") == 1 and "__builtin_sqrtf(q)" in code and "__fsqrt_rn" not in code
+    tile_code = "\n".join(line.split("//")[0] for line in tile.splitlines())
+    assert tile_code.count("sqrtf(") == 1 and "__builtin_sqrtf(q)" in tile_code and "__fsqrt_rn" not in tile_code
+    assert "sqrtf(" not in code and "__fsqrt_rn" not in code and code.count("pair_sqrt(") == 1
+    assert "struct" not in code.replace("struct LsArgs", "") and "ls_tiles" not in code and "const PairRows rows = {a.z, a.ld, a.m};" in code
+    assert "pair_check_table(what, dtype, ld, m, d" in code and "pair_launch_merged(what, k_pair_label_sums, k_pair_label_sums_merge" in code
     assert "__fmaf_rn(" not in text and "pair_chain(va[ki], vb[kj], q[ki][kj])" in code
     assert not re.search(r"#define D3P_LS_(T|C|LD|WAVES)\b", text)
     num = {k: int(re.search(r"#define D3P_PAIR_" + k + r" (\d+)", tile).group(1)) for k in ("T", "C", "LD", "WAVES")}

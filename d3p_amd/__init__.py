@@ -9,7 +9,7 @@ from .version import __version__  # noqa: F401
 
 __all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "loo", "posterior_loo", "LOOResult",
            "diagnostics", "log_likelihood_total", "log_joint", "guide_diagnostic", "GuideDiagnostic", "mixture_diagnostics", "intervals", "clipping",
-           "scoring", "model_weights", "ppc", "discrepancy", "classification", "univariate", "neighbours", "covariance", "permutation", "marginals", "fidelity", "energy"]
+           "scoring", "model_weights", "ppc", "discrepancy", "classification", "mixed", "univariate", "neighbours", "covariance", "permutation", "marginals", "fidelity", "energy"]
 
 
 def __getattr__(name):
@@ -27,9 +27,10 @@ def __getattr__(name):
     # table) and d3p_amd.marginals (binned one- and two-way marginal fidelity of a synthetic table) and d3p_amd.permutation (the permutation test of
     # the energy distance) and d3p_amd.covariance (column means, covariance, correlation and the Frechet distance of a synthetic table) and
     # d3p_amd.neighbours (k nearest neighbours of two tables; precision, recall, density, coverage and authenticity of a synthetic table) and
-    # d3p_amd.univariate (column sorts over all rows, midranks, Spearman correlation, KS and Wasserstein-1 per column) without making `import d3p_amd` import torch
+    # d3p_amd.univariate (column sorts over all rows, midranks, Spearman correlation, KS and Wasserstein-1 per column) and
+    # d3p_amd.mixed (Gower pair statistics, energy distance and closest record of tables with categorical columns) without making `import d3p_amd` import torch
     if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "diagnostics", "mixture_diagnostics",
-                "intervals", "clipping", "scoring", "model_weights", "ppc", "discrepancy", "classification", "energy", "fidelity", "marginals", "permutation", "covariance", "neighbours", "univariate"):
+                "intervals", "clipping", "scoring", "model_weights", "ppc", "discrepancy", "classification", "energy", "fidelity", "marginals", "permutation", "covariance", "neighbours", "univariate", "mixed"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("loo", "posterior_loo", "LOOResult"):   # PSIS-LOO (d3p_amd.criteria), under the same lazy rule

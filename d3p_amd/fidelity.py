@@ -4,7 +4,7 @@ nearest-neighbour adversarial accuracy.
     pair_stats(a, b, exclude_diagonal=False)  -> {"sum": (na,) float64, "min": (na,) float32, "argmin": (na,) int64}
     energy_distance(x, y)                     -> EnergyDistance(d2, d2_unbiased, exy, exx, eyy, n_x, n_y, dim)
     closest_record(synthetic, real)           -> {"distance": (n,) float32, "index": (n,) int64}
-    fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95)) -> FidelityReport
+    fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95), schema=None) -> FidelityReport
 
 PRIVACY.  Every number here is computed from the PRIVATE table, without noise.  Releasing a report, or choosing a model by looking at
 it, is NOT covered by the accountant (``DPSVI.get_epsilon``): the accountant covers the noised steps of training and nothing else.  The
@@ -52,6 +52,10 @@ its nearest row of ``B`` (``d_AA``: the diagonal excluded):
     aa_holdout, privacy_loss       the same with H for T, and aa_holdout - aa (None without a holdout)
     closer_to_train                the share of S with d_ST(j) < d_SH(j), a tie counting 1/2 (None without a holdout)
     n_train, n_synthetic, n_holdout, dim
+
+With ``schema=`` (a ``d3p_amd.mixed.MixedSchema``: some columns hold category codes, on which a Euclidean distance means nothing) every
+walk of the report is Gower's distance of ``d3p_amd.mixed`` (``d3p_pair_stats_mixed``) and every distance is in its units, rounded to
+float32 after the division by the total weight; with ``None`` nothing changes, bit for bit.
 
 Every other host check runs before the device is touched; there is no CPU fallback.
 """
@@ -216,10 +220,11 @@ def _share(flags):
     return float(flags.to(torch.float64).mean())
 
 
-def fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95)):
+def fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95), schema=None):
     """Energy distance, distance to the closest record and nearest-neighbour adversarial accuracy of ``synthetic`` against ``train``
     and, if given, ``holdout`` (module docstring): a ``FidelityReport``.  These are functions of the PRIVATE tables and are not covered
-    by the accountant."""
+    by the accountant.  With a ``schema`` (``d3p_amd.mixed.mixed_schema``: some columns are categorical) every walk is Gower's distance
+    of ``d3p_amd.mixed`` and every distance is in its units; with ``None`` the walks are the Euclidean ones, bit for bit."""
     what = "fidelity_report"
     dt, ds = _check_pair(train, synthetic, ("train", "synthetic"), what)
     tables = [("train", train), ("synthetic", synthetic)]
@@ -228,12 +233,20 @@ def fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95)):
         dh, _ = _check_pair(holdout, synthetic, ("holdout", "synthetic"), what)
         tables.append(("holdout", holdout))
     ps = CL._check_probs(probs)
+    walk = _walk
+    if schema is not None:
+        from . import mixed
+        mixed._check_schema(schema, dt[1], what)
+
+        def walk(a, da, b, db, exclude):
+            out = mixed._walk(a, da, b, db, exclude, schema)
+            return {"sum": out["sum"], "min": out["min"].to(torch.float32), "argmin": out["argmin"]}   # (the profile takes float32)
     _check_devices(tables, what)
     _lib.require_device()   # (every check above runs without a device)
     with torch.cuda.device(train.device):
         _check_exact(tables, what)
-        st, ss, tt = _walk(synthetic, ds, train, dt, False), _walk(synthetic, ds, synthetic, ds, True), _walk(train, dt, train, dt, True)
-        ts = _walk(train, dt, synthetic, ds, False)
+        st, ss, tt = walk(synthetic, ds, train, dt, False), walk(synthetic, ds, synthetic, ds, True), walk(train, dt, train, dt, True)
+        ts = walk(train, dt, synthetic, ds, False)
         e_train = _energy(st["sum"], ss["sum"], tt["sum"], ds[0], dt[0], ds[1])
         dcr = st["min"]
         quant = CL.norm_profile(dcr, (), ps).quantiles if ps else ()
@@ -241,7 +254,7 @@ def fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95)):
         aa = 0.5 * (aa_truth + aa_synth)
         e_hold = aa_hold = loss = closer = None
         if holdout is not None:
-            sh, hh, hs = _walk(synthetic, ds, holdout, dh, False), _walk(holdout, dh, holdout, dh, True), _walk(holdout, dh, synthetic, ds, False)
+            sh, hh, hs = walk(synthetic, ds, holdout, dh, False), walk(holdout, dh, holdout, dh, True), walk(holdout, dh, synthetic, ds, False)
             e_hold = _energy(sh["sum"], ss["sum"], hh["sum"], ds[0], dh[0], ds[1])
             aa_hold = 0.5 * (_share(hs["min"] > hh["min"]) + _share(sh["min"] > ss["min"]))
             loss = aa_hold - aa

@@ -37,7 +37,9 @@ in the data's own units; smaller is better.
 predictive and adds two lines: its energy distance (Szekely & Rizzo) to the training and to the test split, and the quantiles of the
 distance to the closest training record, the number of exact copies, the nearest-neighbour adversarial accuracy (Yale et al. 2020; 0.5:
 indistinguishable) against the training and the held-out split and their difference, the privacy loss.  The numbers are functions of
-the private table and are not covered by the accountant.
+the private table and are not covered by the accountant.  With --with-component (d3p_amd.mixed) the component of every row -- the
+sampled one of a synthetic row, the assigned one of a real row -- is appended as ONE categorical column, and the same report under
+Gower's distance (range-scaled L1 on the numeric columns plus a mismatch count, in [0, 1]) is printed beside the Euclidean one.
 
 --marginal-fidelity [BINS] (off by default; d3p_amd.marginals) draws the same synthetic table and adds two lines of its own: the mean
 and the worst total variation distance of the binned one-way marginals (BINS quantile bins of the training split, default 16) and of
@@ -160,6 +162,20 @@ def synthetic_fidelity_report(X_train, X_test, params, k, seed=4325):
     synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
                                                      params)["obs"][0]
     return fidelity.fidelity_report(X_train, synthetic, holdout=X_test)
+
+
+def mixed_fidelity_report(X_train, X_test, params, k, modes, pis, seed=4325):
+    """The FidelityReport under Gower's distance (d3p_amd.mixed) of the synthetic table of synthetic_fidelity_report with the COMPONENT
+    of every row appended as one categorical column: the sampled component of a synthetic row, mixture.assign's of a real one."""
+    from d3p_amd import fidelity, mixed, mixture
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    obs, (zs,) = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model), params,
+                                                      with_intermediates=True)["obs"]
+    synthetic = torch.cat([obs[0], zs[0].to(torch.float32)[:, None]], dim=1)
+    train, test = (torch.cat([X, mixture.assign(X, modes, 1.0, pis).to(torch.float32)[:, None]], dim=1) for X in (X_train, X_test))
+    schema = mixed.mixed_schema(train, (X_train.shape[1],))
+    return fidelity.fidelity_report(train, synthetic, holdout=test, schema=schema)
 
 
 def marginal_fidelity_report(X_train, X_test, params, k, bins, seed=4325):
@@ -322,6 +338,13 @@ def main(args):
               "privacy loss {:.4f}".format("/".join("{:g}%".format(100 * p) for p in res.dcr_probs),
                                            "/".join("{:.4f}".format(v) for v in res.dcr_quantiles), res.n_exact_copies, res.aa,
                                            res.aa_holdout, res.privacy_loss))
+        if getattr(args, "with_component", False):
+            res = mixed_fidelity_report(X_train, X_test, params, k, modes, pis)
+            print("with the component as a categorical column (Gower units, d = {}): energy distance to train {:.5f}, to test {:.5f}; "
+                  "closest training record quantiles {}, exact copies {}; adversarial accuracy train {:.4f}, held-out {:.4f}, privacy loss "
+                  "{:.4f}".format(res.dim, float(res.energy_train.d2), float(res.energy_holdout.d2),
+                                  "/".join("{:.4f}".format(v) for v in res.dcr_quantiles), res.n_exact_copies, res.aa, res.aa_holdout,
+                                  res.privacy_loss))
     if getattr(args, "marginal_fidelity", None) is not None:
         res = marginal_fidelity_report(X_train, X_test, params, k, args.marginal_fidelity)
         pair = lambda r: "columns {} and {} ({:.4f})".format(r.worst_pairs[0][0][0], r.worst_pairs[0][0][1], r.worst_pairs[0][1]) \
@@ -399,6 +422,9 @@ def parse_args(argv=None):
     parser.add_argument('--synthetic-fidelity', action='store_true',
                         help='after training, draw one synthetic table of the training split\'s size and report its energy distance to the '
                              'train and test splits, the distance to the closest record and the nearest-neighbour adversarial accuracy')
+    parser.add_argument('--with-component', action='store_true',
+                        help='with --synthetic-fidelity: append every row\'s mixture component as one categorical column and print the '
+                             'report under Gower\'s distance (d3p_amd.mixed) beside the Euclidean one')
     parser.add_argument('--marginal-fidelity', nargs='?', const=16, default=None, type=int, metavar='BINS',
                         help='after training, draw one synthetic table of the training split\'s size and report the total variation '
                              'distance of its binned one- and two-way marginals (BINS quantile bins of the training split, default 16) and '

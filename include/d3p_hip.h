@@ -1745,6 +1745,58 @@ int d3p_column_cdf_distance(void* stream, const void* a_dev, int64_t ld_a, uint6
 size_t d3p_column_cdf_distance_workspace(uint64_t n_a, uint64_t n_b, uint32_t d);
 uint32_t d3p_column_cdf_distance_roundings(uint64_t n_a, uint64_t n_b);
 
+/* Mixed-type (Gower) pair statistics of two tables (model-free; d3p_amd/mixed.py; d3p_pair_mixed.hip); added symbols,
+ * ABI 9 unchanged.  d3p_pair_stats' three outputs under a distance for tables whose columns are partly category codes.
+ * a_dev, b_dev, dtype, a_ld, b_ld, na, nb and d are d3p_pair_stats' (int32 converts exactly for |v| <= 2^24).  THE SCHEMA: kind[c]
+ * (0 numeric, 1 categorical) and scale[c] (finite, >= 0, read for numeric columns only: weight_c / range_c, 0 for a constant column)
+ * are HOST arrays of d elements, checked here and carried to the device in launch arguments (no copy call, no host synchronisation);
+ * w_cat >= 0 is the one weight of a categorical mismatch.  dn columns are numeric and dc categorical, d = dn + dc >= 1 in any split.
+ * THE PACK, one launch and one coalesced pass per table: a row becomes d3p_pair_mixed_packed_words(dn, dc) = 4 ceil(dn / 4) + ceil(dc /
+ * 4) words -- the numeric columns in ascending c as floats u = fl32(x_c * scale_c), zero-padded to a multiple of 4 words, then the
+ * categorical columns in ascending c as byte codes four to a word, lowest byte first, pad bytes 0 -- and a flag word, set when a numeric
+ * value or its product is NaN or +-inf or a categorical value is not an integer in [0, 255] (-0 is the code 0).
+ * THE RULE of a pair:
+ *   qn = the float32 chain qn <- qn + |fl32(u_ik - u_jk)| over the numeric words k ascending from +0 (a subtract, then an add of its
+ *        absolute value: two roundings a column, nothing to contract)
+ *   m  = the number of categorical columns whose codes differ, an exact integer
+ *   dist = fmaf(w_cat, (float)m, qn), one rounding; no root.  Zero padding adds +0 and never a mismatch.
+ * For row i over the admissible j (all j < nb, without j == i when exclude_diagonal is 1, which needs na == nb):
+ *   sum_dev[i]    = sum_j (double)dist(i, j) in float64, in THE ORDER of d3p_pair_stats (tiles of 32, segments of
+ *                   d3p_pair_stats_mixed_segment_tiles() = 16 tiles, slot J mod 4, kj fastest, the xor butterfly 4, 2, 1, slots then
+ *                   segments ascending): d3p_pair_stats_mixed_roundings(nb) = 16 (a lane's chain in a segment) + 3 (the butterfly) + 4
+ *                   (the slots) + the segments of b float64 additions lie on a row's sum, the conversions being exact
+ *   min_dev[i]    = the smallest dist
+ *   argmin_dev[i] = the SMALLEST j attaining it: one unsigned 64-bit minimum of (bits(dist) << 32) | j
+ * No admissible j: 0, +inf, 0xFFFFFFFF.  A flagged row i of a: NaN, NaN, 0xFFFFFFFF for that row alone; a flagged row of b: for every
+ * row.  Finite values whose difference or sum overflows float32 follow IEEE.  Two forms that agree bit for bit, d3p_pair_stats' wide (1)
+ * and split (2: cells and a merge launch); d3p_pair_stats_mixed_form(na, nb, d) is the one taken (0: a zero argument),
+ * d3p_pair_stats_mixed_set_form(form) (a test aid; 0: the rule) forces one and changes no result.  The walker stages raw words of the
+ * packed tables in chunks of 32 words; a 16-byte group is wholly numeric or wholly categorical, and a categorical group counts the
+ * non-zero bytes of a ^ b without unpacking.
+ * d3p_pair_stats_mixed_workspace(na, nb, dn, dc) bytes, never 0 for arguments in range (0: one out of range): the split form's cells,
+ * the packed positions, the two packed tables and their row flags.  Every word read is written earlier in the same call.
+ * Deterministic: no atomics, no scratch, no dynamic LDS, no host synchronisation or allocation; repeated calls give equal bits, and a
+ * row's outputs do not depend on na, the other rows of a, a_ld, b_ld, the form or the workspace's previous contents.
+ * Checked before any launch, in this order, with nothing touched: a null a_dev / b_dev / kind / scale / sum_dev / min_dev / argmin_dev, a
+ * pointer not aligned to 4 bytes (sum_dev, ws_dev: 8), a dtype other than 0 / 1, na < 1, nb < 1, d < 1, a_ld < d, b_ld < d, a kind other
+ * than 0 / 1, a scale of a numeric column or a w_cat that is negative or not finite, exclude_diagonal other than 0 / 1 or set with na !=
+ * nb: D3P_E_INVALID_ARG; ws_bytes below d3p_pair_stats_mixed_workspace or a null ws_dev: D3P_E_WORKSPACE; more than 2^31 - 1
+ * workgroups, or d above 2^28: D3P_E_UNSUPPORTED; last, a table, an output or the workspace that is not device memory:
+ * D3P_E_INVALID_ARG. */
+int d3p_pair_stats_mixed(void* stream, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld, uint32_t na,
+                         uint32_t nb, uint32_t d,
+                         const uint8_t* kind, const float* scale, float w_cat,    /* host: d each */
+                         int32_t exclude_diagonal,
+                         double* sum_dev, float* min_dev, uint32_t* argmin_dev,   /* na each */
+                         void* ws_dev, size_t ws_bytes);
+/* host only, no device call */
+uint64_t d3p_pair_mixed_packed_words(uint32_t dn, uint32_t dc);
+size_t d3p_pair_stats_mixed_workspace(uint32_t na, uint32_t nb, uint32_t dn, uint32_t dc);
+uint32_t d3p_pair_stats_mixed_form(uint32_t na, uint32_t nb, uint32_t d);
+uint32_t d3p_pair_stats_mixed_segment_tiles(void);
+uint32_t d3p_pair_stats_mixed_roundings(uint32_t nb);
+int d3p_pair_stats_mixed_set_form(int32_t form);
+
 #ifdef __cplusplus
 }
 #endif

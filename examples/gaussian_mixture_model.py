@@ -57,6 +57,11 @@ Kolmogorov-Smirnov statistic over the columns with its column, the largest scale
 absolute difference of the pairwise Spearman correlations, followed by the floor.  Functions of the private table too, not covered by
 the accountant.
 
+--sliced-wasserstein [N_DIRS] (off by default; d3p_amd.sliced) draws the same synthetic table and adds one line: the sliced 1- and
+2-Wasserstein distances to the training split over N_DIRS random directions (default 128) in units of the training columns' standard
+deviations, and the max-sliced 2-Wasserstein distance with its direction, followed by the floor.  Functions of the private table too,
+not covered by the accountant.
+
 --energy-test [N_PERM] (off by default; d3p_amd.permutation) draws the same synthetic table and adds one line: the permutation test of
 its energy distance (Szekely & Rizzo; N_PERM relabellings of the pooled rows, default 199) against the training and against the test
 split -- the statistic, its p-value and the 95 % quantile of the relabelled statistics.  A function of the private table too, not
@@ -222,6 +227,17 @@ def prdc_report(X_train, X_test, params, k, n_neighbours, seed=4325):
     return neighbours.prdc(X_train, synthetic, k=n_neighbours, holdout=X_test)
 
 
+def sliced_wasserstein_report(X_train, X_test, params, k, n_dirs, seed=4325):
+    """The SlicedWasserstein (d3p_amd.sliced) of the synthetic table of synthetic_fidelity_report against the training split, with the
+    test split as the holdout (the noise floor)."""
+    from d3p_amd import mixture, sliced
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    return sliced.sliced_wasserstein(X_train, synthetic, n_dirs=n_dirs, holdout=X_test)
+
+
 def energy_test_report(X_train, X_test, params, k, n_perm, seed=4325):
     """The EnergyTests (d3p_amd.permutation) of the synthetic table of synthetic_fidelity_report against the training and against the
     test split, n_perm relabellings each."""
@@ -369,6 +385,11 @@ def main(args):
                   res.dim, res.n_synthetic, res.worst_columns[0][1], res.worst_columns[0][0], float(res.w1_scaled.max()),
                   res.spearman_diff_mean, res.spearman_diff_max, res.floor.n_synthetic, float(res.floor.ks.max()),
                   float(res.floor.w1_scaled.max()), res.floor.spearman_diff_mean, res.floor.spearman_diff_max))
+    if getattr(args, "sliced_wasserstein", None) is not None:
+        res = sliced_wasserstein_report(X_train, X_test, params, k, args.sliced_wasserstein)
+        print("sliced Wasserstein ({} directions, {} synthetic rows): SW1 {:.4f}, SW2 {:.4f}, max-sliced W2 {:.4f} (direction {}); held-out "
+              "floor ({} rows): {:.4f}, {:.4f}, {:.4f}".format(res.n_dirs, res.n_synthetic, res.sw1, res.sw2, res.max_w2, res.max_w2_at,
+                                                            res.floor.n_synthetic, res.floor.sw1, res.floor.sw2, res.floor.max_w2))
     if getattr(args, "energy_test", None) is not None:
         tr, te = energy_test_report(X_train, X_test, params, k, args.energy_test)
         print("energy distance permutation test ({} relabellings): to train statistic {:.4f}, p {:.4f} (null 95% {:.4f}); to test statistic "
@@ -437,6 +458,10 @@ def parse_args(argv=None):
                         help='after training, draw one synthetic table of the training split\'s size and report the per-column '
                              'Kolmogorov-Smirnov and Wasserstein-1 distances and the differences of the pairwise Spearman correlations '
                              'to the training split, with the test split\'s scores as the noise floor')
+    parser.add_argument('--sliced-wasserstein', nargs='?', const=128, default=None, type=int, metavar='N_DIRS',
+                        help='after training, draw one synthetic table of the training split\'s size and report its sliced 1- and '
+                             '2-Wasserstein distances to the training split over N_DIRS random directions (default 128), with the test '
+                             'split\'s scores as the noise floor')
     parser.add_argument('--energy-test', nargs='?', const=199, default=None, type=int, metavar='N_PERM',
                         help='after training, draw one synthetic table of the training split\'s size and report the permutation test of its '
                              'energy distance to the train and test splits (N_PERM relabellings, default 199): statistic, p-value and the '

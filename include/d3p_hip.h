@@ -1797,6 +1797,63 @@ uint32_t d3p_pair_stats_mixed_segment_tiles(void);
 uint32_t d3p_pair_stats_mixed_roundings(uint32_t nb);
 int d3p_pair_stats_mixed_set_form(int32_t form);
 
+/* The projection of a table's rows onto L directions on the matrix cores (model-free; d3p_amd/sliced.py; d3p_sliced.hip; DESIGN.md
+ * 4zd); added symbols, ABI 9 unchanged.  x_dev is n x ld (row i in column c at i * ld + c), float32 (dtype 0) or int32 (dtype 1:
+ * converted when loaded, exact for |v| <= 2^24); theta_dev is d x ld_t float32 (direction l of column c at c * ld_t + l); shift_dev is
+ * d float32, or null (no shift: t = x); p_dev is n x ld_p float32, the table d3p_sort_columns takes.
+ *   t_ic = fl32(x_ic - shift_c)            p_dev[i * ld_p + l] = sum_c t_ic theta_cl
+ * THE ORDER: the columns in chunks of d3p_project_rows_chunk_cols() = 32, ascending; a chunk in 16 pairs (2 q, 2 q + 1), ascending; a
+ * pair is ONE v_mfma_f32_32x32x2_f32 onto the float32 accumulator, which started at +0 (the instruction's order over its two products
+ * is not documented); the last chunk padded with t = theta = 0 to dp = 32 ceil(d / 32) columns.  p[i][l] is a function of row i, column
+ * l of theta, shift, d and the dtype alone: not of n, ld, ld_p, ld_t, L, the other rows or directions, the tile or the slab of
+ * d3p_project_rows_max_launch_dirs() = 128 directions l fell into, or the alignment of x_dev.  A workgroup owns
+ * d3p_project_rows_tile_rows() = 128 rows.
+ * BOUND against the float64 dot product of the same float32 t and theta, u = 2^-24, gamma_m = m u / (1 - m u):
+ *   |p^ - p| <= gamma_dp sum_c |t_ic| |theta_cl| + dp 2^-126      (any order, rounded or fused products; flushed subnormals)
+ * A NaN in a row gives NaN in every projection of that row and touches no other; infinities follow IEEE.  Nothing outside p[i][0 .. L),
+ * i < n, is written; the ld - d padding words of x and the ld_t - L of theta may hold anything.  No workspace, no atomics, no scratch,
+ * no host synchronisation, no allocation; static LDS (37376 bytes).
+ * Checked before any launch, in this order: a null x_dev / theta_dev / p_dev; a pointer not aligned to 4 bytes; a dtype other than 0 /
+ * 1; d < 1; ld < d; ld_p < L; ld_t < L; n * ld, n * ld_p or d * ld_t beyond 63 bits: D3P_E_INVALID_ARG; n >= 2^31 or more than 2^31 - 1
+ * workgroups (strips of rows x slabs of directions): D3P_E_UNSUPPORTED; n == 0 or L == 0: D3P_OK with nothing touched; last, a pointer
+ * that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_project_rows(void* stream, const void* x_dev, int32_t dtype, int64_t ld, uint64_t n, uint32_t d,
+                     const float* theta_dev, int64_t ld_t, uint32_t L,
+                     const float* shift_dev,                          /* d, or null */
+                     float* p_dev, int64_t ld_p);
+/* host only, no device call */
+uint32_t d3p_project_rows_tile_rows(void);
+uint32_t d3p_project_rows_chunk_cols(void);
+uint32_t d3p_project_rows_max_launch_dirs(void);
+
+/* The squared 2-Wasserstein distance per column of two SORTED tables (d3p_sort_columns' output, as d3p_column_cdf_distance takes them);
+ * added symbols, ABI 9 unchanged.  On the integer grid of n_a n_b levels element i of a covers [i n_b, (i + 1) n_b) and element j of b
+ * covers [j n_a, (j + 1) n_a):
+ *   w2sq_dev[c] = (1 / (n_a n_b)) sum over the pairs (i, j) whose levels overlap of  overlap (a_(i) - b_(j))^2
+ * The entry names the longer column a; element i meets j0 = floor(i n_b / n_a) and at most j0 + 1; the overlaps are exact integers.
+ * ORDER: a term is delta = (double)a - (double)b, delta delta, times (double)overlap: three roundings; a block is 4096 consecutive i of
+ * a column; thread t of 256 adds, for its 16 consecutive i from block 4096 + 16 t in ascending order, the j0 term and then the j1 term
+ * onto +0; the threads merge in the tree red[t] += red[t + w], w = 128 .. 1; the blocks' partials are added in ascending order onto +0
+ * by a second launch, which divides once by (double)n_a (double)n_b.  Swapping the tables gives equal bits; equal tables give exactly 0.
+ * BOUND: |w2sq - exact| <= gamma_k sum |term| / (n_a n_b), gamma_k = k u / (1 - k u), u = 2^-53, k = 3 (a term) +
+ * d3p_column_w2_distance_roundings(n_a, n_b) = 32 (a thread's chain) + 8 (the tree) + the blocks of the longer column + 2 (the
+ * denominator, the division).
+ * A float32 column whose first or last stored word is not finite (by the sort's order: exactly a column that holds a NaN or an
+ * infinity), in either table, gives NaN and touches no other column.  No atomics, no scratch.
+ * d3p_column_w2_distance_workspace: 8 bytes per (column, block of the longer column); 0: an argument out of range.  Every word read is
+ * written before in the same call.
+ * Checked before any launch, in this order: a null pointer; a_dev or b_dev not aligned to 4 bytes; w2sq_dev or ws_dev not aligned to 8; a
+ * dtype other than 0 / 1; n_a or n_b outside [1, 2^31 - 1]; d < 1; ld_a < n_a or ld_b < n_b; d * ld_a or d * ld_b beyond 63 bits:
+ * D3P_E_INVALID_ARG; more than 2^31 - 1 workgroups: D3P_E_UNSUPPORTED; ws_bytes below the workspace: D3P_E_WORKSPACE, with nothing
+ * touched; last, a pointer that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_column_w2_distance(void* stream, const void* a_dev, int64_t ld_a, uint64_t n_a, const void* b_dev, int64_t ld_b, uint64_t n_b,
+                           int32_t dtype, uint32_t d,
+                           double* w2sq_dev,                          /* d */
+                           void* ws_dev, size_t ws_bytes);
+/* host only, no device call (0: an argument out of range) */
+size_t d3p_column_w2_distance_workspace(uint64_t n_a, uint64_t n_b, uint32_t d);
+uint32_t d3p_column_w2_distance_roundings(uint64_t n_a, uint64_t n_b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libd3p_hip.so")
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip", "d3p_label_sums.hip", "d3p_column_moments.hip", "d3p_pair_knn.hip", "d3p_sort_columns.hip", "d3p_pair_mixed.hip", "d3p_sliced.hip")]
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip", "d3p_label_sums.hip", "d3p_column_moments.hip", "d3p_pair_knn.hip", "d3p_sort_columns.hip", "d3p_pair_mixed.hip", "d3p_sliced.hip", "d3p_mmd.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_outcome.h", "d3p_row_sums.h", "d3p_pair_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_sort_columns.h", "d3p_colsort_global_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
@@ -102,7 +102,9 @@ _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # d3p_pair_mixed.hip has it for d3p_pair_knn.hip's reason: its sub / add-of-|t| chain over 4 x 4 pairs is promised bit for bit.
 # d3p_sliced.hip has it for the subtraction of the shift in front of the matrix instruction (four independent ones a lane and pass), whose
-# result is promised to the bit as well.
+# result is promised to the bit as well.  d3p_mmd.hip does NOT have it: its promise is equal bits for repeated calls, every operation of its
+# rule is one IEEE operation whose packed form rounds the same, and its epilogue's 16 B independent multiply / add pairs are what the packed
+# instructions are for (the contraction of k * k into the partial's addition is switched off by pragma in the source).
 _EXTRA_FLAGS = {"d3p_column_moments.hip": _NO_PACKED_FP32, "d3p_pair_knn.hip": _NO_PACKED_FP32, "d3p_quantiles.hip": _NO_PACKED_FP32,
                 "d3p_pair_mixed.hip": _NO_PACKED_FP32, "d3p_sliced.hip": _NO_PACKED_FP32}
 
@@ -454,6 +456,18 @@ SIGNATURES = {
     "d3p_column_w2_distance": (C.c_int, [_V, _V, C.c_int64, _U64, _V, C.c_int64, _U64, _I32, _U32, _V, _V, _SZ]),
     "d3p_column_w2_distance_workspace": (_SZ, [_U64, _U64, _U32]),
     "d3p_column_w2_distance_roundings": (C.c_uint32, [_U64, _U64]),
+    # Gaussian-kernel row sums of two tables over a ladder of bandwidths, a Gram walk on the matrix cores (d3p_amd/mmd.py): added symbols,
+    # ABI 9 unchanged
+    "d3p_kernel_sums": (C.c_int, [_V, _V, _V, _I32, C.c_int64, C.c_int64, _U32, _U32, _U32, _V, _V, _F, _U32, _I32, _V, _V, _SZ]),
+    "d3p_kernel_sums_workspace": (_SZ, [_U32, _U32, _U32]),
+    "d3p_kernel_sums_strip_rows": (C.c_uint32, []),
+    "d3p_kernel_sums_group_tiles": (C.c_uint32, []),
+    "d3p_kernel_sums_resident_cols": (C.c_uint32, []),
+    "d3p_kernel_sums_max_bandwidths": (C.c_uint32, []),
+    "d3p_kernel_sums_segments": (C.c_uint32, [_U32, _U32]),
+    "d3p_kernel_sums_segment_tiles": (C.c_uint32, [_U32, _U32]),
+    "d3p_kernel_sums_roundings": (C.c_uint32, [_U32, _U32]),
+    "d3p_kernel_sums_set_segments": (C.c_int, [_I32]),
 }
 
 _lib = None

@@ -62,6 +62,11 @@ the accountant.
 deviations, and the max-sliced 2-Wasserstein distance with its direction, followed by the floor.  Functions of the private table too,
 not covered by the accountant.
 
+--mmd [N_BANDWIDTHS] (off by default; d3p_amd.mmd) draws the same synthetic table and adds one line per bandwidth of a ladder centred
+on the median heuristic (default 5 bandwidths): sigma^2, the squared maximum mean discrepancy to the training split under that Gaussian
+kernel (V-statistic and unbiased), the test split's MMD^2 as the floor, and the synthetic row where the witness function is largest in
+magnitude.  Functions of the private table too, not covered by the accountant.
+
 --energy-test [N_PERM] (off by default; d3p_amd.permutation) draws the same synthetic table and adds one line: the permutation test of
 its energy distance (Szekely & Rizzo; N_PERM relabellings of the pooled rows, default 199) against the training and against the test
 split -- the statistic, its p-value and the 95 % quantile of the relabelled statistics.  A function of the private table too, not
@@ -238,6 +243,19 @@ def sliced_wasserstein_report(X_train, X_test, params, k, n_dirs, seed=4325):
     return sliced.sliced_wasserstein(X_train, synthetic, n_dirs=n_dirs, holdout=X_test)
 
 
+def mmd_report(X_train, X_test, params, k, n_bandwidths, seed=4325):
+    """The MMD (d3p_amd.mmd) of the synthetic table of synthetic_fidelity_report against the training split, and of the test split
+    against it (the noise floor) on the same bandwidths."""
+    from d3p_amd import mixture, mmd
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    res = mmd.mmd(X_train, synthetic, n_bandwidths=n_bandwidths)
+    centre = float(res.sigma2[0]) * 2.0 ** (-0.5 * (n_bandwidths - 1))
+    return res, mmd.mmd(X_train, X_test, bandwidth=centre, n_bandwidths=n_bandwidths)
+
+
 def energy_test_report(X_train, X_test, params, k, n_perm, seed=4325):
     """The EnergyTests (d3p_amd.permutation) of the synthetic table of synthetic_fidelity_report against the training and against the
     test split, n_perm relabellings each."""
@@ -390,6 +408,13 @@ def main(args):
         print("sliced Wasserstein ({} directions, {} synthetic rows): SW1 {:.4f}, SW2 {:.4f}, max-sliced W2 {:.4f} (direction {}); held-out "
               "floor ({} rows): {:.4f}, {:.4f}, {:.4f}".format(res.n_dirs, res.n_synthetic, res.sw1, res.sw2, res.max_w2, res.max_w2_at,
                                                             res.floor.n_synthetic, res.floor.sw1, res.floor.sw2, res.floor.max_w2))
+    if getattr(args, "mmd", None) is not None:
+        res, floor = mmd_report(X_train, X_test, params, k, args.mmd)
+        for b in range(args.mmd):
+            at = int(res.witness_y[b].abs().argmax())
+            print("MMD (sigma^2 {:.4g}, {} synthetic rows): MMD^2 {:.3e}, unbiased {:.3e}; held-out floor ({} rows): {:.3e}; largest witness "
+                  "{:+.4f} at synthetic row {}".format(float(res.sigma2[b]), res.n_y, float(res.mmd2[b]), float(res.mmd2_unbiased[b]),
+                                                       floor.n_y, float(floor.mmd2[b]), float(res.witness_y[b][at]), at))
     if getattr(args, "energy_test", None) is not None:
         tr, te = energy_test_report(X_train, X_test, params, k, args.energy_test)
         print("energy distance permutation test ({} relabellings): to train statistic {:.4f}, p {:.4f} (null 95% {:.4f}); to test statistic "
@@ -462,6 +487,10 @@ def parse_args(argv=None):
                         help='after training, draw one synthetic table of the training split\'s size and report its sliced 1- and '
                              '2-Wasserstein distances to the training split over N_DIRS random directions (default 128), with the test '
                              'split\'s scores as the noise floor')
+    parser.add_argument('--mmd', nargs='?', const=5, default=None, type=int, metavar='N_BANDWIDTHS',
+                        help='after training, draw one synthetic table of the training split\'s size and report, per bandwidth of a ladder '
+                             'centred on the median heuristic (default 5), its squared Gaussian-kernel maximum mean discrepancy to the '
+                             'training split, the test split\'s as the floor, and the row of the largest witness value')
     parser.add_argument('--energy-test', nargs='?', const=199, default=None, type=int, metavar='N_PERM',
                         help='after training, draw one synthetic table of the training split\'s size and report the permutation test of its '
                              'energy distance to the train and test splits (N_PERM relabellings, default 199): statistic, p-value and the '

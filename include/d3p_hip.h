@@ -1854,6 +1854,60 @@ int d3p_column_w2_distance(void* stream, const void* a_dev, int64_t ld_a, uint64
 size_t d3p_column_w2_distance_workspace(uint64_t n_a, uint64_t n_b, uint32_t d);
 uint32_t d3p_column_w2_distance_roundings(uint64_t n_a, uint64_t n_b);
 
+/* Gaussian-kernel row sums of two tables over a ladder of bandwidths: a Gram walk on the matrix cores (model-free; d3p_amd/mmd.py;
+ * d3p_mmd.hip); added symbols, ABI 9 unchanged.  a_dev is na x a_ld, b_dev nb x b_ld (row i in column c at i * ld + c),
+ * both float32 (dtype 0) or both int32 (dtype 1: converted when loaded, exact for |v| <= 2^24); shift_dev and scale_dev are d float32
+ * each, or null (that step is skipped); gamma0 is finite and > 0; n_bandwidths = B in 1 .. d3p_kernel_sums_max_bandwidths() = 8.
+ *   t_c    = fl32(fl32(x_c - shift_c) * scale_c)
+ *   r_i    = the float32 chain r <- fmaf(t_c, t_c, r), c ascending, from +0
+ *   g_ij   = sum_c ta_ic tb_jc                 (v_mfma_f32_32x32x2_f32 onto a float32 accumulator from +0: chunks of 32 columns ascending,
+ *                                               the 16 pairs (2 p, 2 p + 1) of a chunk ascending, one instruction a pair; t = 0 padding)
+ *   q_ij   = fmaf(-2, g_ij, fl32(ra_i + rb_j)), 0 where that is < 0 (a select: a NaN stays)
+ *   k_ij^0 = exp2(fl32(-gamma0 q_ij)) (v_exp_f32)          k_ij^b = fl32(k_ij^(b-1) k_ij^(b-1)), b = 1 .. B - 1
+ *   out_dev[b * na + i] = sum over the admissible j of k_ij^b, float64
+ * Bandwidth b has the exponent coefficient gamma0 2^b.  Admissible: j < nb, without j == i when exclude_diagonal is set (na == nb); no
+ * admissible j: 0.  A NaN or +-inf element in row i of a makes that row NaN for every b; one anywhere in b every row (flags of the loaded
+ * words).  THE ORDER of a row's sum: the rows of b in tiles of 32, d3p_kernel_sums_segments(na, nb) segments of
+ * d3p_kernel_sums_segment_tiles(na, nb) consecutive tiles (from (na, nb) alone: about 1024 workgroups, one per strip of
+ * d3p_kernel_sums_strip_rows() = 128 rows of a and segment), groups of d3p_kernel_sums_group_tiles() = 64 consecutive tiles from a
+ * segment's first; a float32 partial per (row, j mod 32, b) adds a group's tiles in ascending order onto +0; at the group's end the 32
+ * partials, widened, are added 0 .. 15 ascending, 16 .. 31 ascending, first plus second; the groups ascending onto +0; the segments
+ * ascending onto +0 (a second launch).  Repeated calls with equal arguments and an equal forced segment count give equal bits; a row's
+ * bits depend on that row, b, d, the dtype, shift, scale, gamma0, the flag and the segment geometry (so on na through it), not on the
+ * other rows of a, the strides, the alignment of either table (16-byte or word loads), B or the workspace's contents.  d <=
+ * d3p_kernel_sums_resident_cols() = 64 keeps the operands of a in registers; above, both tables stream through LDS in chunks of 32.
+ * BOUND against the float64 k of the same float32 t (q by differences), u = 2^-24, gamma_m = m u / (1 - m u), dp = 32 ceil(d / 32), A_ij =
+ * sum_c |ta_ic| |tb_jc|:
+ *   dq = gamma_(dp+2) (ra + rb) + 2 gamma_dp A + u (q + that) + (2 dp + 4) 2^-126
+ *   E_0 = 2^(gamma0 (dq + u (q + dq))) (1 + 2 u) - 1 (v_exp_f32: 1 ulp)       E_b = (1 + E_(b-1))^2 (1 + u) - 1
+ *   |out^ - out| <= (1 + gamma_63) sum_j (E_b k_ij^b + 2^-125) + (gamma_63 + gamma64_R) sum_j k^_ij^b,  R = d3p_kernel_sums_roundings(na, nb)
+ * = 16 + 1 + ceil(segment_tiles / 64) + segments float64 additions (gamma64: u = 2^-53).
+ * d3p_kernel_sums_workspace(na, nb, B): 8 B + 4 bytes per (segment, row of a) and 4 per row of a and of b; 0: an argument out of range.
+ * Every word read is written earlier in the same call; nothing outside out_dev and the workspace is written.  No atomics, no scratch,
+ * no host synchronisation, no allocation; static LDS (34052 or 59652 bytes).
+ * Checked before any launch, in this order: a null a_dev / b_dev / out_dev / ws_dev; a_dev, b_dev, shift_dev or scale_dev not aligned
+ * to 4 bytes; out_dev or ws_dev not aligned to 8; a dtype other than 0 / 1; na < 1 or nb < 1; d < 1; a_ld < d; b_ld < d; na * a_ld or
+ * nb * b_ld beyond 63 bits; exclude_diagonal other than 0 / 1, or set with na != nb; B outside 1 .. 8; gamma0 not finite or <= 0:
+ * D3P_E_INVALID_ARG; na or nb >= 2^31, or more than 2^31 - 1 workgroups: D3P_E_UNSUPPORTED; ws_bytes below the workspace:
+ * D3P_E_WORKSPACE, with nothing touched; last, a pointer that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_kernel_sums(void* stream, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld, uint32_t na, uint32_t nb,
+                    uint32_t d,
+                    const float* shift_dev, const float* scale_dev,    /* d each; or null */
+                    float gamma0, uint32_t n_bandwidths, int32_t exclude_diagonal,
+                    double* out_dev,                                   /* n_bandwidths x na */
+                    void* ws_dev, size_t ws_bytes);
+/* host only, no device call (0: an argument out of range) */
+size_t d3p_kernel_sums_workspace(uint32_t na, uint32_t nb, uint32_t n_bandwidths);
+uint32_t d3p_kernel_sums_strip_rows(void);
+uint32_t d3p_kernel_sums_group_tiles(void);
+uint32_t d3p_kernel_sums_resident_cols(void);
+uint32_t d3p_kernel_sums_max_bandwidths(void);
+uint32_t d3p_kernel_sums_segments(uint32_t na, uint32_t nb);
+uint32_t d3p_kernel_sums_segment_tiles(uint32_t na, uint32_t nb);
+uint32_t d3p_kernel_sums_roundings(uint32_t na, uint32_t nb);
+/* test aid: 0 = the rule, n >= 1 = at most n segments (never more than the tiles of b); the workspace and the order follow it */
+int d3p_kernel_sums_set_segments(int32_t segments);
+
 #ifdef __cplusplus
 }
 #endif

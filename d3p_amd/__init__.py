@@ -9,7 +9,7 @@ from .version import __version__  # noqa: F401
 
 __all__ = ["infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "loo", "posterior_loo", "LOOResult",
            "diagnostics", "log_likelihood_total", "log_joint", "guide_diagnostic", "GuideDiagnostic", "mixture_diagnostics", "intervals", "clipping",
-           "scoring", "model_weights", "ppc", "discrepancy", "classification", "mmd", "sliced", "mixed", "univariate", "neighbours", "covariance", "permutation", "marginals", "fidelity", "energy"]
+           "scoring", "model_weights", "ppc", "discrepancy", "classification", "sinkhorn", "mmd", "sliced", "mixed", "univariate", "neighbours", "covariance", "permutation", "marginals", "fidelity", "energy"]
 
 
 def __getattr__(name):
@@ -31,9 +31,10 @@ def __getattr__(name):
     # d3p_amd.mixed (Gower pair statistics, energy distance and closest record of tables with categorical columns) and d3p_amd.sliced (row
     # projections on the matrix cores, the 2-Wasserstein distance of sorted columns and the sliced Wasserstein distance of a synthetic table)
     # and d3p_amd.mmd (Gaussian-kernel row sums from a Gram walk on the matrix cores, the maximum mean discrepancy and its witness function)
+    # and d3p_amd.sinkhorn (soft-min rows from the same walk with an online log-sum-exp, the debiased Sinkhorn divergence of two tables)
     # without making `import d3p_amd` import torch
     if name in ("infer_util", "prediction", "predictive", "mixture", "mixture_density", "criteria", "diagnostics", "mixture_diagnostics",
-                "intervals", "clipping", "scoring", "model_weights", "ppc", "discrepancy", "classification", "energy", "fidelity", "marginals", "permutation", "covariance", "neighbours", "univariate", "mixed", "sliced", "mmd"):
+                "intervals", "clipping", "scoring", "model_weights", "ppc", "discrepancy", "classification", "energy", "fidelity", "marginals", "permutation", "covariance", "neighbours", "univariate", "mixed", "sliced", "mmd", "sinkhorn"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("loo", "posterior_loo", "LOOResult"):   # PSIS-LOO (d3p_amd.criteria), under the same lazy rule

@@ -10,8 +10,8 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libd3p_hip.so")
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip", "d3p_label_sums.hip", "d3p_column_moments.hip", "d3p_pair_knn.hip", "d3p_sort_columns.hip", "d3p_pair_mixed.hip", "d3p_sliced.hip", "d3p_mmd.hip")]
-_DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_outcome.h", "d3p_row_sums.h", "d3p_pair_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_sort_columns.h", "d3p_colsort_global_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("d3p_rng.hip", "d3p_dpvi.hip", "d3p_stages.hip", "d3p_gmm.hip", "d3p_gemm.hip", "d3p_vae.hip", "d3p_fmesh.hip", "d3p_predict.hip", "d3p_loglik.hip", "d3p_moments.hip", "d3p_predict_glm.hip", "d3p_predict_gmm.hip", "d3p_gmm_density.hip", "d3p_psis.hip", "d3p_draw_sums.hip", "d3p_vae_density.hip", "d3p_quantiles.hip", "d3p_grad_norms.hip", "d3p_hpdi.hip", "d3p_crps.hip", "d3p_model_weights.hip", "d3p_rep_stats.hip", "d3p_discrepancy.hip", "d3p_classify.hip", "d3p_energy.hip", "d3p_pair_stats.hip", "d3p_marginals.hip", "d3p_label_sums.hip", "d3p_column_moments.hip", "d3p_pair_knn.hip", "d3p_sort_columns.hip", "d3p_pair_mixed.hip", "d3p_sliced.hip", "d3p_mmd.hip", "d3p_sinkhorn.hip")]
+_DEPS = _SRC + [os.path.join(_HERE, "csrc", f) for f in ("d3p_device.h", "d3p_host.h", "d3p_glm_tile.h", "d3p_outcome.h", "d3p_row_sums.h", "d3p_pair_tile.h", "d3p_gram_tile.h", "d3p_shifted_sums.h", "d3p_colreduce.h", "d3p_colsort.h", "d3p_crps.h", "d3p_crps_kernel.h", "d3p_sort_columns.h", "d3p_colsort_global_kernel.h", "d3p_gemm.h", "d3p_logreg_kernel.h", "d3p_logreg_chain.h", "d3p_logreg_persist.h", "d3p_logreg_wide.h", "d3p_logreg_particles.h", "d3p_fmesh.h", "d3p_ipc_arena.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "d3p_hip.h")]
 
 D3P_BATCH_EXPLICIT, D3P_BATCH_FEISTEL, D3P_BATCH_POISSON = 0, 1, 2
@@ -105,6 +105,10 @@ _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # result is promised to the bit as well.  d3p_mmd.hip does NOT have it: its promise is equal bits for repeated calls, every operation of its
 # rule is one IEEE operation whose packed form rounds the same, and its epilogue's 16 B independent multiply / add pairs are what the packed
 # instructions are for (the contraction of k * k into the partial's addition is switched off by pragma in the source).
+# d3p_sinkhorn.hip decides as d3p_mmd.hip did and does NOT have it: it shares d3p_mmd.hip's staging and promises what that file promises,
+# equal bits for repeated calls; every operation of its epilogue (the add, the two fmaf, the floor, the subtraction of the reference, the
+# addition onto s) is one IEEE operation that a packed form rounds the same, the rescale is an exact ldexp, and its 16 independent pairs a
+# lane are the shape the packed add is for.
 _EXTRA_FLAGS = {"d3p_column_moments.hip": _NO_PACKED_FP32, "d3p_pair_knn.hip": _NO_PACKED_FP32, "d3p_quantiles.hip": _NO_PACKED_FP32,
                 "d3p_pair_mixed.hip": _NO_PACKED_FP32, "d3p_sliced.hip": _NO_PACKED_FP32}
 
@@ -468,6 +472,15 @@ SIGNATURES = {
     "d3p_kernel_sums_segment_tiles": (C.c_uint32, [_U32, _U32]),
     "d3p_kernel_sums_roundings": (C.c_uint32, [_U32, _U32]),
     "d3p_kernel_sums_set_segments": (C.c_int, [_I32]),
+    # soft-min rows of two tables, the Gram walk with an online log-sum-exp epilogue (d3p_amd/sinkhorn.py): added symbols, ABI 9 unchanged
+    "d3p_softmin_rows": (C.c_int, [_V, _V, _V, _I32, C.c_int64, C.c_int64, _U32, _U32, _U32, _V, _V, _F, _V, _V, C.c_double, _V, _V, _V, _V, _SZ]),
+    "d3p_softmin_rows_workspace": (_SZ, [_U32, _U32]),
+    "d3p_softmin_rows_group_tiles": (C.c_uint32, []),
+    "d3p_softmin_rows_resident_cols": (C.c_uint32, []),
+    "d3p_softmin_rows_segments": (C.c_uint32, [_U32, _U32]),
+    "d3p_softmin_rows_segment_tiles": (C.c_uint32, [_U32, _U32]),
+    "d3p_softmin_rows_roundings": (C.c_uint32, [_U32, _U32]),
+    "d3p_softmin_rows_set_segments": (C.c_int, [_I32]),
 }
 
 _lib = None

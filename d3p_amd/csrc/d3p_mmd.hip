@@ -65,7 +65,7 @@
 //     It adds ra (16 registers, loaded once) and rb (one load a tile, issued a tile ahead), clamps, takes ONE exp2, squares B - 1
 //     times and adds into 16 x B float32 partials.  At a group's end the partials pass through 32 x 33 floats of the wavefront's own
 //     LDS to the row's two lanes (order above); lane r < 32 keeps row r's B float64 totals.
-//   * STATIC LDS only: RES 16640 + 16896 + 516 = 34052 bytes; streaming 8448 + 33792 + 16896 + 516 = 59652 bytes.  The streaming
+//   * STATIC LDS only (GramLds, d3p_gram_tile.h): RES 16640 + 8 + 16896 + 516 = 34060 bytes; streaming 8448 + 33792 + 16896 + 516 = 59652 bytes.  The streaming
 //     form takes 328 .. 454 registers (the compiler keeps the 20 row addresses of both load forms and a chunk's 32 operands ahead):
 //     one workgroup a CU, no scratch; a cap at 256 spills, so there is none.  Open gain: the load form as a template argument.
 // k_mmd_merge: a thread per row adds the segments' cells in ascending order and writes NaN where a flag is set.
@@ -90,22 +90,14 @@
 #include "d3p_device.h"
 #include "d3p_host.h"
 #include "d3p_pair_tile.h"
+#include "d3p_gram_tile.h"   // the staging, the load forms, the product loop and the segment rule: shared with d3p_sinkhorn.hip
 
-#define D3P_MM_WAVES 4u
-#define D3P_MM_TILE 32u                               // rows of a wavefront, rows of a tile of b
-#define D3P_MM_STRIP (D3P_MM_WAVES * D3P_MM_TILE)     // rows of a workgroup
-#define D3P_MM_CHUNK 32u                              // columns staged at a time by the streaming form
-#define D3P_MM_RES 64u                                // d up to which the A operands stay in registers
 #define D3P_MM_GROUP 64u                              // G: tiles of b a float32 partial adds before it is widened
 #define D3P_MM_MAX_B 8u
-#define D3P_MM_TARGET 1024u                           // workgroups the segment rule aims at
-#define D3P_MM_RED 33u                                // row pitch of the group-end transpose
 
 static int32_t g_mm_segments = 0;   // d3p_kernel_sums_set_segments: 0 = the rule
 
 namespace d3p {
-
-typedef float mm_f16v __attribute__((ext_vector_type(16)));
 
 struct MmArgs {
     const uint32_t* a; const uint32_t* b; int32_t dtype; int64_t a_ld, b_ld; uint32_t na, nb, d, excl, nseg, tps, B, vec_a, vec_b;
@@ -114,266 +106,87 @@ struct MmArgs {
     double* out;
 };
 
-struct MmTable { const uint32_t* base; int64_t ld; uint32_t n, vec; };
-
-__device__ __forceinline__ float mm_value(int32_t dtype, uint32_t w) { return dtype ? (float)(int32_t)w : __uint_as_float(w); }
-__device__ __forceinline__ bool mm_not_finite(float v) { return !(fabsf(v) <= 3.402823466e38f); }
-
-// THE t of one element in column c < d
-__device__ __forceinline__ float mm_t(float v, float sh, float sc, bool shifted, bool scaled)
-{
-#pragma clang fp contract(off)
-    float t = v;
-    if (shifted) t = t - sh;
-    if (scaled) t = t * sc;
-    return t;
-}
-
-// 2^lw >= units threads share a row, lw >= 3 (a tile of 32 rows is then one pass of the 256 threads at the least)
-__device__ __forceinline__ uint32_t mm_lanes_log2(uint32_t units) { return units > 32u ? 6u : units > 16u ? 5u : units > 8u ? 4u : 3u; }
-
-// Thread t of 256 takes UNIT u = t % 2^lw -- four columns from c0 + 4 u with the 16-byte loads, else column c0 + u -- of the rows
-// row0 + t / 2^lw + p (256 / 2^lw) of `rows` rows: up to NW words.  A dead row reads the table's last row, a dead column column 0: every
-// load is inside the table and none sits behind a divergent branch.
-template <uint32_t NW>
-__device__ __forceinline__ void mm_load(const MmTable& T, uint32_t row0, uint32_t rows, uint32_t c0, uint32_t d, uint32_t lw, uint32_t t,
-                                        uint32_t (&w)[NW])
-{
-    const uint32_t u = t & ((1u << lw) - 1u), rl = t >> lw, rpp = 256u >> lw, passes = rows / rpp;
-    if (T.vec) {
-        const uint32_t c = c0 + 4u * u, cr = c < d ? c : 0u;   // (c < d: c + 3 < ld, both multiples of 4)
-#pragma unroll
-        for (uint32_t p = 0; p < NW / 4u; ++p) {
-            if (p < passes) {
-                const uint32_t row = row0 + rl + p * rpp;
-                const uint4 v = *reinterpret_cast<const uint4*>(T.base + (int64_t)(row < T.n ? row : T.n - 1u) * T.ld + cr);
-                w[4u * p] = v.x; w[4u * p + 1u] = v.y; w[4u * p + 2u] = v.z; w[4u * p + 3u] = v.w;
-            }
-        }
-    } else {
-        const uint32_t c = c0 + u, cr = c < d ? c : 0u;
-#pragma unroll
-        for (uint32_t p = 0; p < NW; ++p) {
-            if (p < passes) {
-                const uint32_t row = row0 + rl + p * rpp;
-                w[p] = T.base[(int64_t)(row < T.n ? row : T.n - 1u) * T.ld + cr];
-            }
-        }
-    }
-}
-
-// shift and scale of the unit's columns (0 and 1 where the pointer is null or the column dead: mm_t does not read them then)
-__device__ __forceinline__ void mm_coeffs(const MmArgs& a, uint32_t vec, uint32_t c0, uint32_t u, float (&sh)[4], float (&sc)[4])
-{
-#pragma unroll
-    for (uint32_t e = 0; e < 4u; ++e) {
-        const uint32_t c = vec ? c0 + 4u * u + e : c0 + u, cr = c < a.d ? c : 0u;
-        sh[e] = a.shift ? a.shift[cr] : 0.0f;
-        sc[e] = a.scale ? a.scale[cr] : 1.0f;
-    }
-}
-
-// the words of mm_load as t into lds[row * pitch + column - c0]: units below `units` only; a dead row or column is 0 (by select, after
-// the arithmetic); a live element that is NaN or +-inf sets `bad` and, with rowflag, its row's word
-template <uint32_t NW>
-__device__ __forceinline__ void mm_store(const MmArgs& a, const MmTable& T, uint32_t row0, uint32_t rows, uint32_t c0, uint32_t lw, uint32_t units,
-                                         uint32_t t, const uint32_t (&w)[NW], const float (&sh)[4], const float (&sc)[4], float* lds, uint32_t pitch,
-                                         uint32_t* rowflag, bool& bad)
-{
-    const uint32_t u = t & ((1u << lw) - 1u), rl = t >> lw, rpp = 256u >> lw, passes = rows / rpp;
-    const uint32_t per = T.vec ? 4u : 1u;
-    if (u >= units) return;
-#pragma unroll
-    for (uint32_t p = 0; p < NW; ++p) {
-        const uint32_t pass = T.vec ? p >> 2 : p, e = T.vec ? p & 3u : 0u;
-        if (pass < passes) {
-            const uint32_t lr = rl + pass * rpp, lc = per * u + e;
-            const bool live = row0 + lr < T.n && c0 + lc < a.d;
-            const float v = mm_value(a.dtype, w[p]);
-            const bool nf = live && mm_not_finite(v);
-            bad |= nf;
-            if (rowflag && nf) rowflag[lr] = 1u;
-            const float tv = mm_t(v, sh[e], sc[e], a.shift != nullptr, a.scale != nullptr);
-            lds[lr * pitch + lc] = live ? tv : 0.0f;
-        }
-    }
-}
-
-// the tile's 16 x 32 pairs of lane (half, sub): q, the clamp, ONE exp2, the ladder, the partials
+// THE EPILOGUE of gram_walk: the partials of a group and the float64 totals of the segment
 template <int NB>
-__device__ __forceinline__ void mm_epilogue(const mm_f16v& acc, const float (&ra)[16], float rb, float ngamma, uint32_t r0, uint32_t half, uint32_t j,
-                                            uint32_t nb, uint32_t excl, float (&part)[NB][16])
-{
-#pragma clang fp contract(off)
-#pragma unroll
-    for (uint32_t v = 0; v < 16u; ++v) {
-        const uint32_t i = r0 + 8u * (v >> 2) + 4u * half + (v & 3u);
-        const float s = ra[v] + rb;
-        float q = __fmaf_rn(-2.0f, acc[v], s);
-        q = q < 0.0f ? 0.0f : q;                               // (a NaN compares false and stays)
-        float k = __builtin_amdgcn_exp2f(ngamma * q);
-        k = pair_admissible(i, j, nb, excl) ? k : 0.0f;        // (0 squared is 0: masked once for every rung)
-        part[0][v] = part[0][v] + k;
-#pragma unroll
-        for (int b = 1; b < NB; ++b) {
-            k = k * k;
-            part[b][v] = part[b][v] + k;
-        }
-    }
-}
-
-// a group's end: the partials, widened, to the rows' float64 totals (lanes r and r + 32 hold row r's; THE ORDER) and back to +0
-template <int NB>
-__device__ __forceinline__ void mm_flush(float (&part)[NB][16], float* red, uint32_t lane, double (&tot)[NB])
-{
-#pragma clang fp contract(off)
-    const uint32_t half = lane >> 5, sub = lane & 31u;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-#pragma unroll
-        for (uint32_t v = 0; v < 16u; ++v) {
-            red[(8u * (v >> 2) + 4u * half + (v & 3u)) * D3P_MM_RED + sub] = part[b][v];
-            part[b][v] = 0.0f;
-        }
-        pair_wave_sync();
-        double s = 0.0;
-#pragma unroll
-        for (uint32_t e = 0; e < 16u; ++e) s = s + (double)red[sub * D3P_MM_RED + 16u * half + e];
-        const double o = __shfl_xor(s, 32, 64);
-        tot[b] = tot[b] + (s + o);                             // (a + b is commutative: both lanes end with equal bits)
-        pair_wave_sync();
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mmd_norms(MmArgs a)
-{
-    const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (idx >= (uint64_t)a.na + a.nb) return;
-    const bool second = idx >= a.na;
-    const uint64_t row = second ? idx - a.na : idx;
-    const uint32_t* x = (second ? a.b : a.a) + (int64_t)row * (second ? a.b_ld : a.a_ld);
-    float r = 0.0f;
-    for (uint32_t c = 0; c < a.d; ++c) {
-        const float t = mm_t(mm_value(a.dtype, x[c]), a.shift ? a.shift[c] : 0.0f, a.scale ? a.scale[c] : 1.0f, a.shift != nullptr, a.scale != nullptr);
-        r = __fmaf_rn(t, t, r);
-    }
-    (second ? a.rb : a.ra)[row] = r;
-}
-
-template <int NB, bool RES>
-__global__ __launch_bounds__(64 * D3P_MM_WAVES, (RES && NB <= 5) ? 2 : 1) void k_mmd_walk(MmArgs a)
-{
-    constexpr uint32_t KW = RES ? D3P_MM_RES : D3P_MM_CHUNK, PITCH = KW + 1u, NWB = RES ? 8u : 4u, NWA = RES ? 1u : 16u;
-    __shared__ float bs[2][D3P_MM_TILE * PITCH];
-    __shared__ float as[2][RES ? 1u : D3P_MM_STRIP * PITCH];
-    __shared__ float red[D3P_MM_WAVES][D3P_MM_TILE * D3P_MM_RED];
-    __shared__ uint32_t aflag[D3P_MM_STRIP];
-    __shared__ uint32_t bflag;
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6, half = lane >> 5, sub = lane & 31u;
-    const uint32_t strip = pair_split_tile(a.nseg), seg = pair_split_segment(a.nseg);
-    const uint32_t s0 = strip * D3P_MM_STRIP, r0 = s0 + wave * D3P_MM_TILE;     // (na < 2^31: no wrap)
-    const uint32_t ntb = pair_tiles(a.nb), j_lo = seg * a.tps, j_hi = ntb - j_lo < a.tps ? ntb : j_lo + a.tps;
-    const uint32_t nchunk = RES ? 1u : (a.d + D3P_MM_CHUNK - 1u) / D3P_MM_CHUNK, nq = (a.d + 1u) / 2u;
-    const MmTable ta = {a.a, a.a_ld, a.na, a.vec_a}, tb = {a.b, a.b_ld, a.nb, a.vec_b};
-    // the units of a staged row: RES all d columns of b (to an even count: the pair 2 p, 2 p + 1), else a chunk of 32
-    const uint32_t ub = RES ? (tb.vec ? (a.d + 3u) / 4u : 2u * nq) : (tb.vec ? 8u : 32u), lwb = mm_lanes_log2(ub);
-    const uint32_t ua = ta.vec ? 8u : 32u, lwa = ta.vec ? 3u : 5u;
-    if (t < D3P_MM_STRIP) aflag[t] = 0u;
-    if (t == 0u) bflag = 0u;
-    __syncthreads();
-
-    bool bad_a = false, bad_b = false;
-    float areg[RES ? D3P_MM_RES / 2u : 1u];
-    if constexpr (RES) {   // lane (half, sub) holds column 2 p + half of row r0 + sub
-        const uint32_t row = r0 + sub;
-        const uint32_t* x = a.a + (int64_t)(row < a.na ? row : a.na - 1u) * a.a_ld;
-#pragma unroll
-        for (uint32_t p = 0; p < D3P_MM_RES / 2u; ++p) {
-            areg[p] = 0.0f;
-            if (p < nq) {   // (uniform)
-                const uint32_t c = 2u * p + half, cr = c < a.d ? c : 0u;
-                const bool live = row < a.na && c < a.d;
-                const float v = mm_value(a.dtype, x[cr]);
-                bad_a |= live && mm_not_finite(v);
-                const float tv = mm_t(v, a.shift ? a.shift[cr] : 0.0f, a.scale ? a.scale[cr] : 1.0f, a.shift != nullptr, a.scale != nullptr);
-                areg[p] = live ? tv : 0.0f;
-            }
-        }
-    }
-    float ra[16];
-#pragma unroll
-    for (uint32_t v = 0; v < 16u; ++v) {
-        const uint32_t i = r0 + 8u * (v >> 2) + 4u * half + (v & 3u);
-        ra[v] = a.ra[i < a.na ? i : a.na - 1u];
-    }
-
-    uint32_t wb[NWB], wa[NWA];
-    float shb[4], scb[4], sha[4], sca[4];
-    auto load = [&](uint32_t J, uint32_t c0) {
-        mm_load<NWB>(tb, J * D3P_MM_TILE, D3P_MM_TILE, c0, a.d, lwb, t, wb);
-        if constexpr (!RES) {
-            mm_load<NWA>(ta, s0, D3P_MM_STRIP, c0, a.d, lwa, t, wa);
-            mm_coeffs(a, tb.vec, c0, t & ((1u << lwb) - 1u), shb, scb);
-            mm_coeffs(a, ta.vec, c0, t & ((1u << lwa) - 1u), sha, sca);
-        }
-    };
-    auto store = [&](uint32_t J, uint32_t c0, uint32_t buf) {
-        mm_store<NWB>(a, tb, J * D3P_MM_TILE, D3P_MM_TILE, c0, lwb, ub, t, wb, shb, scb, bs[buf], PITCH, nullptr, bad_b);
-        if constexpr (!RES) mm_store<NWA>(a, ta, s0, D3P_MM_STRIP, c0, lwa, ua, t, wa, sha, sca, as[buf], PITCH, aflag, bad_a);
-    };
-
+struct MmEpilogue {
     float part[NB][16];
     double tot[NB];
+    float ngamma;
+    uint32_t nb, excl;
+
+    __device__ __forceinline__ MmEpilogue(const MmArgs& a) : ngamma(-a.gamma0), nb(a.nb), excl(a.excl)
+    {
 #pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        tot[b] = 0.0;
+        for (int b = 0; b < NB; ++b) {
+            tot[b] = 0.0;
 #pragma unroll
-        for (int v = 0; v < 16; ++v) part[b][v] = 0.0f;
-    }
-    const float ngamma = -a.gamma0;
-    if constexpr (RES) mm_coeffs(a, tb.vec, 0u, t & ((1u << lwb) - 1u), shb, scb);
-    float rb_next = j_lo * D3P_MM_TILE + sub < a.nb ? a.rb[j_lo * D3P_MM_TILE + sub] : 0.0f;
-    load(j_lo, 0u);
-    uint32_t step = 0u;
-    for (uint32_t J = j_lo; J < j_hi; ++J) {
-        const float rb = rb_next;
-        {
-            const uint32_t jn = (J + 1u) * D3P_MM_TILE + sub;
-            rb_next = J + 1u < j_hi && jn < a.nb ? a.rb[jn] : 0.0f;
+            for (int v = 0; v < 16; ++v) part[b][v] = 0.0f;
         }
-        mm_f16v acc;
+    }
+    __device__ __forceinline__ void ahead(uint32_t, bool) {}
+    __device__ __forceinline__ void advance() {}
+    __device__ __forceinline__ bool bad() const { return false; }
+
+    // the tile's 16 x 32 pairs of lane (half, sub): q, the clamp, ONE exp2, the ladder, the partials; a group's end
+    __device__ __forceinline__ void tile(const gram_f16v& acc, const float (&ra)[16], float rb, uint32_t r0, uint32_t half, uint32_t j, uint32_t k,
+                                         bool last, float* red, uint32_t lane)
+    {
+#pragma clang fp contract(off)
 #pragma unroll
-        for (int v = 0; v < 16; ++v) acc[v] = 0.0f;
-        for (uint32_t c = 0; c < nchunk; ++c, ++step) {
-            const uint32_t buf = step & 1u;
-            store(J, c * D3P_MM_CHUNK, buf);
-            __syncthreads();   // ONE a step: this buffer was last read two steps ago, before the barrier of the step between
-            if (c + 1u < nchunk) load(J, (c + 1u) * D3P_MM_CHUNK);
-            else if (J + 1u < j_hi) load(J + 1u, 0u);
-            const float* brow = bs[buf] + sub * PITCH + half;
-            if constexpr (RES) {
+        for (uint32_t v = 0; v < 16u; ++v) {
+            const uint32_t i = r0 + gram_acc_row(v, half);
+            const float s = ra[v] + rb;
+            float q = __fmaf_rn(-2.0f, acc[v], s);
+            q = q < 0.0f ? 0.0f : q;                               // (a NaN compares false and stays)
+            float kv = __builtin_amdgcn_exp2f(ngamma * q);
+            kv = pair_admissible(i, j, nb, excl) ? kv : 0.0f;      // (0 squared is 0: masked once for every rung)
+            part[0][v] = part[0][v] + kv;
 #pragma unroll
-                for (uint32_t p = 0; p < D3P_MM_RES / 2u; ++p)
-                    if (p < nq) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[p], brow[2u * p], acc, 0, 0, 0);   // (uniform)
-            } else {
-                const float* arow = as[buf] + (wave * D3P_MM_TILE + sub) * PITCH + half;
-#pragma unroll
-                for (uint32_t p = 0; p < D3P_MM_CHUNK / 2u; ++p) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[2u * p], brow[2u * p], acc, 0, 0, 0);
+            for (int b = 1; b < NB; ++b) {
+                kv = kv * kv;
+                part[b][v] = part[b][v] + kv;
             }
         }
-        mm_epilogue<NB>(acc, ra, rb, ngamma, r0, half, J * D3P_MM_TILE + sub, a.nb, a.excl, part);
-        if ((J - j_lo + 1u) % D3P_MM_GROUP == 0u || J + 1u == j_hi) mm_flush<NB>(part, red[wave], lane, tot);
+        if ((k + 1u) % D3P_MM_GROUP == 0u || last) flush(red, lane);
     }
 
-    const unsigned long long abits = __builtin_amdgcn_ballot_w64(bad_a);   // RES: lanes r and r + 32 loaded row r
-    if (bad_b) bflag = 1u;
-    __syncthreads();
-    const uint32_t row = r0 + lane;
-    if (lane < D3P_MM_TILE && row < a.na) {
-        const uint32_t fa = RES ? (uint32_t)(((abits >> lane) | (abits >> (lane + 32u))) & 1ull) : aflag[wave * D3P_MM_TILE + lane];
+    // a group's end: the partials, widened, to the rows' float64 totals (lanes r and r + 32 hold row r's; THE ORDER) and back to +0
+    __device__ __forceinline__ void flush(float* red, uint32_t lane)
+    {
+#pragma clang fp contract(off)
+        const uint32_t half = lane >> 5, sub = lane & 31u;
 #pragma unroll
-        for (int b = 0; b < NB; ++b) a.cell[(uint64_t)b * a.nseg * a.na + pair_cell(seg, a.na, row)] = tot[b];
-        a.flag[pair_cell(seg, a.na, row)] = pair_flag_word(fa, bflag);
+        for (int b = 0; b < NB; ++b) {
+#pragma unroll
+            for (uint32_t v = 0; v < 16u; ++v) {
+                red[gram_acc_row(v, half) * D3P_GRAM_RED + sub] = part[b][v];
+                part[b][v] = 0.0f;
+            }
+            pair_wave_sync();
+            double s = 0.0;
+#pragma unroll
+            for (uint32_t e = 0; e < 16u; ++e) s = s + (double)red[sub * D3P_GRAM_RED + 16u * half + e];
+            const double o = __shfl_xor(s, 32, 64);
+            tot[b] = tot[b] + (s + o);                             // (a + b is commutative: both lanes end with equal bits)
+            pair_wave_sync();
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void k_mmd_norms(MmArgs a) { gram_norms(a); }
+
+template <int NB, bool RES>
+__global__ __launch_bounds__(64 * D3P_GRAM_WAVES, (RES && NB <= 5) ? 2 : 1) void k_mmd_walk(MmArgs a)
+{
+    __shared__ GramLds<RES> lds;
+    MmEpilogue<NB> epi(a);
+    const uint32_t flags = gram_walk<RES>(a, lds, epi);
+    const uint32_t lane = threadIdx.x & 63u, seg = pair_split_segment(a.nseg);
+    const uint32_t row = pair_split_tile(a.nseg) * D3P_GRAM_STRIP + (threadIdx.x >> 6) * D3P_GRAM_TILE + lane;
+    if (lane < D3P_GRAM_TILE && row < a.na) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) a.cell[(uint64_t)b * a.nseg * a.na + pair_cell(seg, a.na, row)] = epi.tot[b];
+        a.flag[pair_cell(seg, a.na, row)] = flags;
     }
 }
 
@@ -392,27 +205,15 @@ __global__ __launch_bounds__(256) void k_mmd_merge(MmArgs a)
     }
 }
 
-static const uint32_t MM_MAX_N = 0x7fffffffu;
+static const uint32_t MM_MAX_N = GRAM_MAX_N;
 
-static uint32_t mm_strips(uint32_t na) { return (uint32_t)(((uint64_t)na + D3P_MM_STRIP - 1u) / D3P_MM_STRIP); }
+static uint32_t mm_strips(uint32_t na) { return gram_strips(na); }
 
-// THE segment rule: from (na, nb) alone (and the forced count)
-static uint32_t mm_segment_tiles(uint32_t na, uint32_t nb)
-{
-    const uint32_t ntb = pair_tiles(nb), strips = mm_strips(na);
-    uint32_t want = g_mm_segments > 0 ? (uint32_t)g_mm_segments : (D3P_MM_TARGET + strips - 1u) / strips;
-    if (want > ntb) want = ntb;
-    return (ntb + want - 1u) / want;
-}
+static uint32_t mm_segment_tiles(uint32_t na, uint32_t nb) { return gram_segment_tiles(na, nb, g_mm_segments); }
 
-static bool mm_sizes_ok(uint32_t na, uint32_t nb) { return na >= 1 && nb >= 1 && na <= MM_MAX_N && nb <= MM_MAX_N; }
+static bool mm_sizes_ok(uint32_t na, uint32_t nb) { return gram_sizes_ok(na, nb); }
 
-static uint32_t mm_segments(uint32_t na, uint32_t nb)
-{
-    if (!mm_sizes_ok(na, nb)) return 0;
-    const uint32_t tps = mm_segment_tiles(na, nb);
-    return (pair_tiles(nb) + tps - 1u) / tps;
-}
+static uint32_t mm_segments(uint32_t na, uint32_t nb) { return gram_segments(na, nb, g_mm_segments); }
 
 static size_t mm_workspace(uint32_t na, uint32_t nb, uint32_t B)
 {
@@ -434,11 +235,11 @@ using namespace d3p;
 
 extern "C" {
 
-uint32_t d3p_kernel_sums_strip_rows(void) { return D3P_MM_STRIP; }
+uint32_t d3p_kernel_sums_strip_rows(void) { return D3P_GRAM_STRIP; }
 
 uint32_t d3p_kernel_sums_group_tiles(void) { return D3P_MM_GROUP; }
 
-uint32_t d3p_kernel_sums_resident_cols(void) { return D3P_MM_RES; }
+uint32_t d3p_kernel_sums_resident_cols(void) { return D3P_GRAM_RES; }
 
 uint32_t d3p_kernel_sums_max_bandwidths(void) { return D3P_MM_MAX_B; }
 
@@ -498,7 +299,7 @@ int d3p_kernel_sums(void* stream, const void* a_dev, const void* b_dev, int32_t 
     a.rb = a.ra + na;
     hipLaunchKernelGGL(k_mmd_norms, dim3((unsigned)(((uint64_t)na + nb + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, a);
     if (const int rc = check_launch(what)) return rc;
-    const bool res = d <= D3P_MM_RES;
+    const bool res = d <= D3P_GRAM_RES;
     switch (n_bandwidths) {
         case 1: return mm_launch<1>(what, res, (unsigned)groups, (hipStream_t)stream, a);
         case 2: return mm_launch<2>(what, res, (unsigned)groups, (hipStream_t)stream, a);

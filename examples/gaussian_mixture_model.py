@@ -67,6 +67,12 @@ on the median heuristic (default 5 bandwidths): sigma^2, the squared maximum mea
 kernel (V-statistic and unbiased), the test split's MMD^2 as the floor, and the synthetic row where the witness function is largest in
 magnitude.  Functions of the private table too, not covered by the accountant.
 
+--sinkhorn [EPSILON_SHARE] (off by default; d3p_amd.sinkhorn) draws the same synthetic table and adds one line: the debiased Sinkhorn
+divergence to the training split under the cost |x - y|^2 / 2 in units of the training columns' standard deviations, at a
+regularisation of EPSILON_SHARE (default 0.05) times the median squared distance, the transport cost ot_xy, the iterations run and
+whether they converged, followed by the test split's divergence at the same epsilon as the floor.  Functions of the private table too,
+not covered by the accountant.
+
 --energy-test [N_PERM] (off by default; d3p_amd.permutation) draws the same synthetic table and adds one line: the permutation test of
 its energy distance (Szekely & Rizzo; N_PERM relabellings of the pooled rows, default 199) against the training and against the test
 split -- the statistic, its p-value and the 95 % quantile of the relabelled statistics.  A function of the private table too, not
@@ -256,6 +262,18 @@ def mmd_report(X_train, X_test, params, k, n_bandwidths, seed=4325):
     return res, mmd.mmd(X_train, X_test, bandwidth=centre, n_bandwidths=n_bandwidths)
 
 
+def sinkhorn_report(X_train, X_test, params, k, epsilon_share, seed=4325):
+    """The SinkhornDivergence (d3p_amd.sinkhorn) of the synthetic table of synthetic_fidelity_report against the training split, and of
+    the test split against it (the noise floor) at the same epsilon."""
+    from d3p_amd import mixture, sinkhorn
+    from d3p_amd.random import debug as threefry
+    model = GaussianMixtureModel()
+    synthetic = mixture.posterior_predictive_samples(threefry.PRNGKey(seed), 1, model, (k, X_train), GaussianMixtureGuide(model),
+                                                     params)["obs"][0]
+    res = sinkhorn.sinkhorn_divergence(X_train, synthetic, epsilon_share=epsilon_share)
+    return res, sinkhorn.sinkhorn_divergence(X_train, X_test, epsilon=res.epsilon)
+
+
 def energy_test_report(X_train, X_test, params, k, n_perm, seed=4325):
     """The EnergyTests (d3p_amd.permutation) of the synthetic table of synthetic_fidelity_report against the training and against the
     test split, n_perm relabellings each."""
@@ -415,6 +433,11 @@ def main(args):
             print("MMD (sigma^2 {:.4g}, {} synthetic rows): MMD^2 {:.3e}, unbiased {:.3e}; held-out floor ({} rows): {:.3e}; largest witness "
                   "{:+.4f} at synthetic row {}".format(float(res.sigma2[b]), res.n_y, float(res.mmd2[b]), float(res.mmd2_unbiased[b]),
                                                        floor.n_y, float(floor.mmd2[b]), float(res.witness_y[b][at]), at))
+    if getattr(args, "sinkhorn", None) is not None:
+        res, floor = sinkhorn_report(X_train, X_test, params, k, args.sinkhorn)
+        print("Sinkhorn divergence (epsilon {:.4g}, {} synthetic rows): {:.4e}, ot_xy {:.4e}, {} iterations, converged {}; held-out floor "
+              "({} rows): {:.4e}".format(res.epsilon, res.n_y, float(res.divergence), float(res.ot_xy), res.n_iter_run, res.converged,
+                                         floor.n_y, float(floor.divergence)))
     if getattr(args, "energy_test", None) is not None:
         tr, te = energy_test_report(X_train, X_test, params, k, args.energy_test)
         print("energy distance permutation test ({} relabellings): to train statistic {:.4f}, p {:.4f} (null 95% {:.4f}); to test statistic "
@@ -491,6 +514,10 @@ def parse_args(argv=None):
                         help='after training, draw one synthetic table of the training split\'s size and report, per bandwidth of a ladder '
                              'centred on the median heuristic (default 5), its squared Gaussian-kernel maximum mean discrepancy to the '
                              'training split, the test split\'s as the floor, and the row of the largest witness value')
+    parser.add_argument('--sinkhorn', nargs='?', const=0.05, default=None, type=float, metavar='EPSILON_SHARE',
+                        help='after training, draw one synthetic table of the training split\'s size and report its debiased Sinkhorn '
+                             'divergence to the training split at a regularisation of EPSILON_SHARE (default 0.05) times the median '
+                             'squared distance, with the test split\'s divergence as the floor')
     parser.add_argument('--energy-test', nargs='?', const=199, default=None, type=int, metavar='N_PERM',
                         help='after training, draw one synthetic table of the training split\'s size and report the permutation test of its '
                              'energy distance to the train and test splits (N_PERM relabellings, default 199): statistic, p-value and the '

@@ -1908,6 +1908,66 @@ uint32_t d3p_kernel_sums_roundings(uint32_t na, uint32_t nb);
 /* test aid: 0 = the rule, n >= 1 = at most n segments (never more than the tiles of b); the workspace and the order follow it */
 int d3p_kernel_sums_set_segments(int32_t segments);
 
+/* Soft-min rows of two tables: the base-2 log-sum-exp of a potential minus the scaled squared distance, the primitive of log-domain
+ * Sinkhorn iterations, from d3p_kernel_sums' Gram walk with an online epilogue (model-free; d3p_amd/sinkhorn.py; d3p_sinkhorn.hip;
+ * DESIGN.md 4zf); added symbols, ABI 9 unchanged.  a_dev, b_dev, dtype, a_ld, b_ld, na, nb, d, shift_dev and scale_dev are
+ * d3p_kernel_sums', and so are t, r, g (v_mfma_f32_32x32x2_f32, its order) and q = fmaf(-2, g, fl32(ra + rb)), 0 where that is < 0 (a
+ * select).  gamma is finite and > 0; h_dev nb float32 in base-2 units; prev_dev na float64 or null; omega a double in (0, 1]; logw_dev na
+ * float32 and out_h_dev na float32, given together or both null.
+ *   v_ij    = fmaf(-gamma, q_ij, h_j)                                float32
+ *   L_i     = log2 sum_j 2^(v_ij)          over all j < nb           float64
+ *   pot_i   = -L_i                          if prev_dev is null
+ *           = prev_i + omega * ((-L_i) - prev_i)   otherwise         float64, these three operations
+ *   out_h_i = fl32(pot_i + logw_i)          if logw_dev is given
+ * pot_dev (na float64) is always written; out_h_dev is the h of the opposite walk.  h_j = -inf: a row of zero weight, adds nothing;
+ * every h_j = -inf: L = -inf, pot = +inf (prev null), no NaN.  A NaN or +inf in h: every row NaN.  A NaN or +-inf element in row i of
+ * a: row i NaN, no other touched; one anywhere in b: every row NaN (flags of the loaded words).  A finite v below -2^127 counts as -inf.
+ * THE ORDER of a row's sum: tiles of 32 rows of b, d3p_softmin_rows_segments(na, nb) segments of d3p_softmin_rows_segment_tiles(na, nb)
+ * consecutive tiles (d3p_kernel_sums' rule, from (na, nb) alone), groups of d3p_softmin_rows_group_tiles() = 64 consecutive tiles from a
+ * segment's first.  A float32 pair (m, s) per (row, j mod 32) runs over a group's tiles ascending from (F, +0), F = -2^127: m' = max(m,
+ * floor(v)), s <- ldexp(s, max(m - m', -300)) + exp2(fl32(v - m')), m <- m': m is integer-valued, the rescale an exact power of two
+ * (skipped by a wavefront where no lane's reference rises: equal bits).  At the group's end the 32 pairs of a row are merged in float64:
+ * 0 .. 15 ascending to their largest m (each s scaled by ldexp, the sum onto +0), 16 .. 31 likewise, the two halves scaled to the larger
+ * m and added; the groups ascending onto (F, +0) by M' = max(M, M2), S <- ldexp(S, M - M') + ldexp(S2, M2 - M') (a scaling below 2^-1100
+ * gives 0); the segments likewise (a second launch), which takes L = M + log2(S).  Repeated calls with equal arguments and an equal forced
+ * segment count give equal bits; a row's bits depend on that row, b, h, d, the dtype, shift, scale, gamma, prev_i, omega, logw_i and the
+ * segment geometry, not on the other rows of a, the strides, the alignment of either table or the workspace's contents.  d <=
+ * d3p_softmin_rows_resident_cols() = 64 keeps the operands of a in registers; above, both tables stream through LDS in chunks of 32.
+ * BOUND in BITS of L against the float64 log-sum-exp of the same float32 t and h (q by differences); u = 2^-24, dq d3p_kernel_sums', p_ij
+ * = 2^(v_ij - L_i):
+ *   dv_ij = gamma dq_ij + u (|h_j| + gamma (q_ij + dq_ij)) + 127 u + log2(1 + 2 u)
+ *   |dL_i| <= log2(sum_j p_ij 2^(dv_ij)) + log2(1 + gamma_64 + gamma64_R) + log2(1 + nb 2^-126) + 2^-53 (4 + 2 |L_i|)
+ * R = d3p_softmin_rows_roundings(na, nb) = 16 + 1 + ceil(segment_tiles / 64) + segments float64 additions; the pot step adds 2^-53 (|L| +
+ * 2 |prev|) and out_h the conversion's u |pot + logw|.
+ * d3p_softmin_rows_workspace(na, nb): 20 bytes per (segment, row of a) and 4 per row of a and of b; 0: an argument out of range.  Every
+ * word read is written earlier in the same call; nothing outside pot_dev, out_h_dev and the workspace is written.  No atomics, no
+ * scratch, no host synchronisation, no allocation; static LDS.
+ * Checked before any launch, in this order: a null a_dev / b_dev / h_dev / pot_dev / ws_dev; a_dev, b_dev, shift_dev, scale_dev, h_dev,
+ * logw_dev or out_h_dev not aligned to 4 bytes; pot_dev, prev_dev or ws_dev not aligned to 8; a dtype other than 0 / 1; na < 1 or nb < 1;
+ * d < 1; a_ld < d; b_ld < d; na * a_ld or nb * b_ld beyond 63 bits; gamma not finite or <= 0; omega outside (0, 1]; one of logw_dev and
+ * out_h_dev without the other: D3P_E_INVALID_ARG; na or nb >= 2^31, or more than 2^31 - 1 workgroups: D3P_E_UNSUPPORTED; ws_bytes below
+ * the workspace: D3P_E_WORKSPACE, with nothing touched; last, a pointer that is not device memory: D3P_E_INVALID_ARG. */
+int d3p_softmin_rows(void* stream, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld, uint32_t na, uint32_t nb,
+                     uint32_t d,
+                     const float* shift_dev, const float* scale_dev,    /* d each; or null */
+                     float gamma,
+                     const float* h_dev,                                /* nb */
+                     const double* prev_dev,                            /* na; or null */
+                     double omega,
+                     const float* logw_dev,                             /* na; or null */
+                     double* pot_dev,                                   /* na */
+                     float* out_h_dev,                                  /* na; null exactly when logw_dev is */
+                     void* ws_dev, size_t ws_bytes);
+/* host only, no device call (0: an argument out of range) */
+size_t d3p_softmin_rows_workspace(uint32_t na, uint32_t nb);
+uint32_t d3p_softmin_rows_group_tiles(void);
+uint32_t d3p_softmin_rows_resident_cols(void);
+uint32_t d3p_softmin_rows_segments(uint32_t na, uint32_t nb);
+uint32_t d3p_softmin_rows_segment_tiles(uint32_t na, uint32_t nb);
+uint32_t d3p_softmin_rows_roundings(uint32_t na, uint32_t nb);
+/* test aid: 0 = the rule, n >= 1 = at most n segments (never more than the tiles of b); the workspace and the order follow it */
+int d3p_softmin_rows_set_segments(int32_t segments);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,9 +47,9 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
-from . import fidelity as FD
+from . import _tables as T
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["column_moments", "covariance", "correlation", "correlation_fidelity", "ColumnMoments", "CorrelationFidelity", "INT_EXACT"]
 
@@ -83,9 +83,17 @@ def _moments(x, dx):
     mean = torch.empty(d, dtype=torch.float64, device=x.device)
     m2 = torch.empty((d, d), dtype=torch.float64, device=x.device)
     ws = torch.empty(int(lib.d3p_column_moments_workspace(n, d)), dtype=torch.uint8, device=x.device)
-    check(lib.d3p_column_moments(stream_ptr(), ptr(x), 0 if x.dtype == torch.float32 else 1, ld, n, d, ptr(mean), ptr(m2), d, ptr(ws),
-                                 int(ws.numel())))
+    check(lib.d3p_column_moments(stream_ptr(), ptr(x), T.dtype_code(x), ld, n, d, ptr(mean), ptr(m2), d, ptr(ws), int(ws.numel())))
     return ColumnMoments(n, mean, m2)
+
+
+def standardise(x, dx):
+    """(shift, inverse std) of a checked table from ONE ``_moments`` call, for the walkers that centre and scale on load: the float32
+    rounding of the column means, and ``1 / std`` (``ddof = 1``) in float64 with 0 for a constant column and for every column of a
+    one-row table."""
+    mom = _moments(x, dx)
+    sd = (mom.m2.diagonal() / float(dx[0] - 1)).sqrt() if dx[0] > 1 else torch.zeros_like(mom.mean)
+    return mom.mean.to(torch.float32), torch.where(sd > 0, 1.0 / sd, torch.zeros_like(sd))
 
 
 def _check_ddof(ddof, n, what):
@@ -97,23 +105,17 @@ def _check_ddof(ddof, n, what):
 def column_moments(x):
     """The column means and the centred cross-product matrix of ``x`` (module docstring): a ``ColumnMoments`` on the table's device."""
     what = "column_moments"
-    dx = FD._check_table(x, "x", what)
-    FD._check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        FD._check_exact((("x", x),), what)
+    dx = T.check_table(x, "x", what)
+    with T.on_device((("x", x),), what, exact=(("x", x),)):
         return _moments(x, dx)
 
 
 def covariance(x, ddof=1):
     """The ``(d, d)`` float64 covariance matrix of the columns of ``x``: ``m2 / (n - ddof)`` (module docstring)."""
     what = "covariance"
-    dx = FD._check_table(x, "x", what)
+    dx = T.check_table(x, "x", what)
     _check_ddof(ddof, dx[0], what)
-    FD._check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        FD._check_exact((("x", x),), what)
+    with T.on_device((("x", x),), what, exact=(("x", x),)):
         return _moments(x, dx).m2 / float(dx[0] - ddof)
 
 
@@ -134,11 +136,8 @@ def _corr(m2):
 def correlation(x):
     """The ``(d, d)`` float64 Pearson correlation matrix of the columns of ``x`` (module docstring)."""
     what = "correlation"
-    dx = FD._check_table(x, "x", what)
-    FD._check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        FD._check_exact((("x", x),), what)
+    dx = T.check_table(x, "x", what)
+    with T.on_device((("x", x),), what, exact=(("x", x),)):
         return _corr(_moments(x, dx).m2)
 
 
@@ -169,19 +168,10 @@ def _report(mr, ms, top):
     ranked = torch.nan_to_num(smd, nan=-1.0)
     w1 = torch.topk(ranked, min(top, d)) if top else None
     worst_c = tuple((i, float(smd[i])) for i in w1.indices.tolist()) if w1 is not None else ()
-    diff = (_corr(ms.m2) - _corr(mr.m2)).abs()
-    iu = torch.triu_indices(d, d, offset=1, device=diff.device)
-    vals = diff[iu[0], iu[1]]
-    ok = ~torch.isnan(vals)
-    kept = vals[ok]
-    worst_p = ()
-    if top and kept.numel():
-        w2 = torch.topk(kept, min(top, kept.numel()))
-        at = ok.nonzero().flatten()[w2.indices]
-        worst_p = tuple(((int(iu[0][a]), int(iu[1][a])), float(v)) for a, v in zip(at.tolist(), w2.values.tolist()))
+    kept, n_skipped, worst_p = T.worst_pairs((_corr(ms.m2) - _corr(mr.m2)).abs(), top)
     nan = float("nan")
     return CorrelationFidelity(smd, ratio, worst_c, float(kept.mean()) if kept.numel() else nan, float(kept.max()) if kept.numel() else nan,
-                               float(torch.sqrt((kept * kept).sum())) if kept.numel() else nan, worst_p, int((~ok).sum()),
+                               float(torch.sqrt((kept * kept).sum())) if kept.numel() else nan, worst_p, n_skipped,
                                _frechet(mr.mean, c_r, ms.mean, c_s), mr.n, ms.n, d, None)
 
 
@@ -190,20 +180,12 @@ def correlation_fidelity(real, synthetic, holdout=None, top=5):
     that the holdout scores against ``real`` (module docstring): a ``CorrelationFidelity``.  These are functions of the PRIVATE tables
     and are not covered by the accountant."""
     what = "correlation_fidelity"
-    dr, ds = FD._check_pair(real, synthetic, ("real", "synthetic"), what)
-    tables = [("real", real), ("synthetic", synthetic)]
-    dh = None
-    if holdout is not None:
-        dh, _ = FD._check_pair(holdout, real, ("holdout", "real"), what)
-        tables.append(("holdout", holdout))
+    tables = T.check_group(real, synthetic, holdout, ("real", "synthetic", "holdout"), what)
     if isinstance(top, bool) or not isinstance(top, int) or top < 0:
         raise ValueError(f"{what}: top must be a non-negative int")
-    FD._check_devices(tables, what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(real.device):
-        FD._check_exact(tables, what)
-        mr = _moments(real, dr)
-        rep = _report(mr, _moments(synthetic, ds), top)
+    with T.on_device(tables, what, exact=tables):
+        mr, *others = [_moments(t, dims) for _, t, dims in tables]
+        rep = _report(mr, others[0], top)
         if holdout is not None:
-            rep = rep._replace(floor=_report(mr, _moments(holdout, dh), top))
+            rep = rep._replace(floor=_report(mr, others[1], top))
         return rep

@@ -5,7 +5,7 @@
 // and hand the 32 x 32 accumulator of a tile to an EPILOGUE, the part that varies.  Here: the constants of the geometry, the value, the
 // flag and the t of a loaded word, the load / store pair that stages a tile, the walk over the tiles of a segment (gram_walk: the
 // double-buffered staging, the resident or streaming operands of a, the product loop, the norm of b a tile ahead, the flags) and --
-// HOST, at the end -- the segment rule.  d3p_mmd.hip's header states the order of g and the layout in full; this file is that text's
+// HOST, at the end -- the segment rule and the host steps of the two entries (gram_prepare, gram_launch_norms).  d3p_mmd.hip's header states the order of g and the layout in full; this file is that text's
 // code.  What a walker's argument struct must carry under these names (ARGS): a, b (uint32_t words), dtype, a_ld, b_ld, na, nb, d, nseg,
 // tps, vec_a, vec_b, shift, scale, ra, rb.  An EPILOGUE (EPI) has
 //     ahead(j, live)     the loads of column j that ride with rb_j, issued a tile ahead (live: j < nb and inside the segment)
@@ -279,6 +279,39 @@ inline uint32_t gram_segments(uint32_t na, uint32_t nb, int32_t forced)
     if (!gram_sizes_ok(na, nb)) return 0;
     const uint32_t tps = gram_segment_tiles(na, nb, forced);
     return (pair_tiles(nb) + tps - 1u) / tps;
+}
+
+// What an entry does between the refusals of its own arguments and that of its workspace (the tables have passed pair_check_pair):
+// the refusals of the sizes, the geometry under the entry's forced segment count, and the fields of ARGS that gram_walk and
+// gram_norms read but ra and rb, which the entry carves from its workspace.  Returns the workgroups of the walk, one per strip of a
+// and segment of b -- or 0 behind a refusal, which is D3P_E_UNSUPPORTED with the message set
+template <class ARGS>
+inline unsigned gram_prepare(const char* what, int32_t forced, const void* a_dev, const void* b_dev, int32_t dtype, int64_t a_ld, int64_t b_ld,
+                             uint32_t na, uint32_t nb, uint32_t d, const float* shift_dev, const float* scale_dev, ARGS& a)
+{
+    if (na > GRAM_MAX_N || nb > GRAM_MAX_N) {
+        fail(D3P_E_UNSUPPORTED, "%s: %u x %u rows; at most 2^31 - 1 each", what, na, nb);
+        return 0;
+    }
+    const uint32_t tps = gram_segment_tiles(na, nb, forced), nseg = gram_segments(na, nb, forced);
+    const uint64_t groups = (uint64_t)gram_strips(na) * nseg;
+    if (groups > 0x7fffffffull) {
+        fail(D3P_E_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (one per strip of a and segment of b)", what);
+        return 0;
+    }
+    a.a = static_cast<const uint32_t*>(a_dev); a.b = static_cast<const uint32_t*>(b_dev); a.dtype = dtype; a.a_ld = a_ld; a.b_ld = b_ld;
+    a.na = na; a.nb = nb; a.d = d; a.nseg = nseg; a.tps = tps;
+    a.vec_a = ((uintptr_t)a_dev & 15u) == 0 && (a_ld & 3) == 0; a.vec_b = ((uintptr_t)b_dev & 15u) == 0 && (b_ld & 3) == 0;
+    a.shift = shift_dev; a.scale = scale_dev;
+    return (unsigned)groups;
+}
+
+// the first launch of both entries: a walker's norms kernel (gram_norms), a thread per row of a and of b
+template <class ARGS>
+inline int gram_launch_norms(const char* what, void (*norms)(ARGS), hipStream_t stream, const ARGS& a)
+{
+    hipLaunchKernelGGL(norms, dim3((unsigned)(((uint64_t)a.na + a.nb + 255u) / 256u)), dim3(256), 0, stream, a);
+    return check_launch(what);
 }
 
 }  // namespace d3p

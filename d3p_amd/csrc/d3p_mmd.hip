@@ -205,20 +205,10 @@ __global__ __launch_bounds__(256) void k_mmd_merge(MmArgs a)
     }
 }
 
-static const uint32_t MM_MAX_N = GRAM_MAX_N;
-
-static uint32_t mm_strips(uint32_t na) { return gram_strips(na); }
-
-static uint32_t mm_segment_tiles(uint32_t na, uint32_t nb) { return gram_segment_tiles(na, nb, g_mm_segments); }
-
-static bool mm_sizes_ok(uint32_t na, uint32_t nb) { return gram_sizes_ok(na, nb); }
-
-static uint32_t mm_segments(uint32_t na, uint32_t nb) { return gram_segments(na, nb, g_mm_segments); }
-
 static size_t mm_workspace(uint32_t na, uint32_t nb, uint32_t B)
 {
-    if (!mm_sizes_ok(na, nb) || B < 1 || B > D3P_MM_MAX_B) return 0;
-    const size_t cells = (size_t)mm_segments(na, nb) * na;   // < 2^26 x 2^31
+    if (!gram_sizes_ok(na, nb) || B < 1 || B > D3P_MM_MAX_B) return 0;
+    const size_t cells = (size_t)gram_segments(na, nb, g_mm_segments) * na;   // < 2^26 x 2^31
     return cells * 8u * B + cells * 4u + ((size_t)na + nb) * 4u;
 }
 
@@ -243,15 +233,15 @@ uint32_t d3p_kernel_sums_resident_cols(void) { return D3P_GRAM_RES; }
 
 uint32_t d3p_kernel_sums_max_bandwidths(void) { return D3P_MM_MAX_B; }
 
-uint32_t d3p_kernel_sums_segments(uint32_t na, uint32_t nb) { return mm_segments(na, nb); }
+uint32_t d3p_kernel_sums_segments(uint32_t na, uint32_t nb) { return gram_segments(na, nb, g_mm_segments); }
 
-uint32_t d3p_kernel_sums_segment_tiles(uint32_t na, uint32_t nb) { return mm_sizes_ok(na, nb) ? mm_segment_tiles(na, nb) : 0u; }
+uint32_t d3p_kernel_sums_segment_tiles(uint32_t na, uint32_t nb) { return gram_sizes_ok(na, nb) ? gram_segment_tiles(na, nb, g_mm_segments) : 0u; }
 
 uint32_t d3p_kernel_sums_roundings(uint32_t na, uint32_t nb)
 {
-    if (!mm_sizes_ok(na, nb)) return 0u;
+    if (!gram_sizes_ok(na, nb)) return 0u;
     // a half row's sixteen; the halves; the groups of a segment; the segments
-    return 16u + 1u + (mm_segment_tiles(na, nb) + D3P_MM_GROUP - 1u) / D3P_MM_GROUP + mm_segments(na, nb);
+    return 16u + 1u + (gram_segment_tiles(na, nb, g_mm_segments) + D3P_MM_GROUP - 1u) / D3P_MM_GROUP + gram_segments(na, nb, g_mm_segments);
 }
 
 size_t d3p_kernel_sums_workspace(uint32_t na, uint32_t nb, uint32_t n_bandwidths) { return mm_workspace(na, nb, n_bandwidths); }
@@ -277,38 +267,32 @@ int d3p_kernel_sums(void* stream, const void* a_dev, const void* b_dev, int32_t 
     if (n_bandwidths < 1 || n_bandwidths > D3P_MM_MAX_B)
         return fail(D3P_E_INVALID_ARG, "%s: n_bandwidths must be in 1 .. %u, got %u", what, D3P_MM_MAX_B, n_bandwidths);
     if (!(gamma0 > 0.0f) || !std::isfinite(gamma0)) return fail(D3P_E_INVALID_ARG, "%s: gamma0 must be finite and > 0", what);
-    if (na > MM_MAX_N || nb > MM_MAX_N) return fail(D3P_E_UNSUPPORTED, "%s: %u x %u rows; at most 2^31 - 1 each", what, na, nb);
-    const uint32_t tps = mm_segment_tiles(na, nb), nseg = mm_segments(na, nb);
-    const uint64_t groups = (uint64_t)mm_strips(na) * nseg;
-    if (groups > 0x7fffffffull) return fail(D3P_E_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (one per strip of a and segment of b)", what);
+    MmArgs a;
+    const unsigned groups = gram_prepare(what, g_mm_segments, a_dev, b_dev, dtype, a_ld, b_ld, na, nb, d, shift_dev, scale_dev, a);
+    if (!groups) return D3P_E_UNSUPPORTED;
     const size_t need = mm_workspace(na, nb, n_bandwidths);
     if (ws_bytes < need) return fail(D3P_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", what, ws_bytes, need);
     if (!is_device_ptr(a_dev) || !is_device_ptr(b_dev) || !is_device_ptr(out_dev) || !is_device_ptr(ws_dev) || (shift_dev && !is_device_ptr(shift_dev)) ||
         (scale_dev && !is_device_ptr(scale_dev)))
         return fail(D3P_E_INVALID_ARG, "%s: the tables, the shift, the scale, the output and the workspace must be device memory", what);
-    MmArgs a;
-    a.a = static_cast<const uint32_t*>(a_dev); a.b = static_cast<const uint32_t*>(b_dev); a.dtype = dtype; a.a_ld = a_ld; a.b_ld = b_ld;
-    a.na = na; a.nb = nb; a.d = d; a.excl = (uint32_t)exclude_diagonal; a.nseg = nseg; a.tps = tps; a.B = n_bandwidths;
-    a.vec_a = ((uintptr_t)a_dev & 15u) == 0 && (a_ld & 3) == 0; a.vec_b = ((uintptr_t)b_dev & 15u) == 0 && (b_ld & 3) == 0;
-    a.shift = shift_dev; a.scale = scale_dev; a.gamma0 = gamma0; a.out = out_dev;
-    const size_t cells = (size_t)nseg * na;
+    a.excl = (uint32_t)exclude_diagonal; a.B = n_bandwidths; a.gamma0 = gamma0; a.out = out_dev;
+    const size_t cells = (size_t)a.nseg * na;
     char* ws = static_cast<char*>(ws_dev);
     a.cell = reinterpret_cast<double*>(ws);
     a.flag = reinterpret_cast<uint32_t*>(ws + cells * 8u * n_bandwidths);
     a.ra = reinterpret_cast<float*>(ws + cells * 8u * n_bandwidths + cells * 4u);
     a.rb = a.ra + na;
-    hipLaunchKernelGGL(k_mmd_norms, dim3((unsigned)(((uint64_t)na + nb + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, a);
-    if (const int rc = check_launch(what)) return rc;
+    if (const int rc = gram_launch_norms(what, k_mmd_norms, (hipStream_t)stream, a)) return rc;
     const bool res = d <= D3P_GRAM_RES;
     switch (n_bandwidths) {
-        case 1: return mm_launch<1>(what, res, (unsigned)groups, (hipStream_t)stream, a);
-        case 2: return mm_launch<2>(what, res, (unsigned)groups, (hipStream_t)stream, a);
-        case 3: return mm_launch<3>(what, res, (unsigned)groups, (hipStream_t)stream, a);
-        case 4: return mm_launch<4>(what, res, (unsigned)groups, (hipStream_t)stream, a);
-        case 5: return mm_launch<5>(what, res, (unsigned)groups, (hipStream_t)stream, a);
-        case 6: return mm_launch<6>(what, res, (unsigned)groups, (hipStream_t)stream, a);
-        case 7: return mm_launch<7>(what, res, (unsigned)groups, (hipStream_t)stream, a);
-        default: return mm_launch<8>(what, res, (unsigned)groups, (hipStream_t)stream, a);
+        case 1: return mm_launch<1>(what, res, groups, (hipStream_t)stream, a);
+        case 2: return mm_launch<2>(what, res, groups, (hipStream_t)stream, a);
+        case 3: return mm_launch<3>(what, res, groups, (hipStream_t)stream, a);
+        case 4: return mm_launch<4>(what, res, groups, (hipStream_t)stream, a);
+        case 5: return mm_launch<5>(what, res, groups, (hipStream_t)stream, a);
+        case 6: return mm_launch<6>(what, res, groups, (hipStream_t)stream, a);
+        case 7: return mm_launch<7>(what, res, groups, (hipStream_t)stream, a);
+        default: return mm_launch<8>(what, res, groups, (hipStream_t)stream, a);
     }
 }
 

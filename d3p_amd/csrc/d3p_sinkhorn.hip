@@ -233,14 +233,10 @@ __global__ __launch_bounds__(256) void k_sk_merge(SkArgs a)
     if (a.logw && a.out_h) a.out_h[i] = (float)(pot + (double)a.logw[i]);
 }
 
-static uint32_t sk_segment_tiles(uint32_t na, uint32_t nb) { return gram_segment_tiles(na, nb, g_sk_segments); }
-
-static uint32_t sk_segments(uint32_t na, uint32_t nb) { return gram_segments(na, nb, g_sk_segments); }
-
 static size_t sk_workspace(uint32_t na, uint32_t nb)
 {
     if (!gram_sizes_ok(na, nb)) return 0;
-    const size_t cells = (size_t)sk_segments(na, nb) * na;   // < 2^26 x 2^31
+    const size_t cells = (size_t)gram_segments(na, nb, g_sk_segments) * na;   // < 2^26 x 2^31
     return cells * 20u + ((size_t)na + nb) * 4u;
 }
 
@@ -254,15 +250,15 @@ uint32_t d3p_softmin_rows_group_tiles(void) { return D3P_SK_GROUP; }
 
 uint32_t d3p_softmin_rows_resident_cols(void) { return D3P_GRAM_RES; }
 
-uint32_t d3p_softmin_rows_segments(uint32_t na, uint32_t nb) { return sk_segments(na, nb); }
+uint32_t d3p_softmin_rows_segments(uint32_t na, uint32_t nb) { return gram_segments(na, nb, g_sk_segments); }
 
-uint32_t d3p_softmin_rows_segment_tiles(uint32_t na, uint32_t nb) { return gram_sizes_ok(na, nb) ? sk_segment_tiles(na, nb) : 0u; }
+uint32_t d3p_softmin_rows_segment_tiles(uint32_t na, uint32_t nb) { return gram_sizes_ok(na, nb) ? gram_segment_tiles(na, nb, g_sk_segments) : 0u; }
 
 uint32_t d3p_softmin_rows_roundings(uint32_t na, uint32_t nb)
 {
     if (!gram_sizes_ok(na, nb)) return 0u;
     // a half row's sixteen; the halves; the groups of a segment; the segments
-    return 16u + 1u + (sk_segment_tiles(na, nb) + D3P_SK_GROUP - 1u) / D3P_SK_GROUP + sk_segments(na, nb);
+    return 16u + 1u + (gram_segment_tiles(na, nb, g_sk_segments) + D3P_SK_GROUP - 1u) / D3P_SK_GROUP + gram_segments(na, nb, g_sk_segments);
 }
 
 size_t d3p_softmin_rows_workspace(uint32_t na, uint32_t nb) { return sk_workspace(na, nb); }
@@ -288,33 +284,26 @@ int d3p_softmin_rows(void* stream, const void* a_dev, const void* b_dev, int32_t
     if (!(gamma > 0.0f) || !std::isfinite(gamma)) return fail(D3P_E_INVALID_ARG, "%s: gamma must be finite and > 0", what);
     if (!(omega > 0.0 && omega <= 1.0)) return fail(D3P_E_INVALID_ARG, "%s: omega must be in (0, 1]", what);
     if ((logw_dev == nullptr) != (out_h_dev == nullptr)) return fail(D3P_E_INVALID_ARG, "%s: logw_dev and out_h_dev are given together or not at all", what);
-    if (na > GRAM_MAX_N || nb > GRAM_MAX_N) return fail(D3P_E_UNSUPPORTED, "%s: %u x %u rows; at most 2^31 - 1 each", what, na, nb);
-    const uint32_t tps = sk_segment_tiles(na, nb), nseg = sk_segments(na, nb);
-    const uint64_t groups = (uint64_t)gram_strips(na) * nseg;
-    if (groups > 0x7fffffffull) return fail(D3P_E_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (one per strip of a and segment of b)", what);
+    SkArgs a;
+    const unsigned groups = gram_prepare(what, g_sk_segments, a_dev, b_dev, dtype, a_ld, b_ld, na, nb, d, shift_dev, scale_dev, a);
+    if (!groups) return D3P_E_UNSUPPORTED;
     const size_t need = sk_workspace(na, nb);
     if (ws_bytes < need) return fail(D3P_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", what, ws_bytes, need);
     if (!is_device_ptr(a_dev) || !is_device_ptr(b_dev) || !is_device_ptr(h_dev) || !is_device_ptr(pot_dev) || !is_device_ptr(ws_dev) ||
         (shift_dev && !is_device_ptr(shift_dev)) || (scale_dev && !is_device_ptr(scale_dev)) || (prev_dev && !is_device_ptr(prev_dev)) ||
         (logw_dev && !is_device_ptr(logw_dev)) || (out_h_dev && !is_device_ptr(out_h_dev)))
         return fail(D3P_E_INVALID_ARG, "%s: the tables, the vectors, the outputs and the workspace must be device memory", what);
-    SkArgs a;
-    a.a = static_cast<const uint32_t*>(a_dev); a.b = static_cast<const uint32_t*>(b_dev); a.dtype = dtype; a.a_ld = a_ld; a.b_ld = b_ld;
-    a.na = na; a.nb = nb; a.d = d; a.nseg = nseg; a.tps = tps;
-    a.vec_a = ((uintptr_t)a_dev & 15u) == 0 && (a_ld & 3) == 0; a.vec_b = ((uintptr_t)b_dev & 15u) == 0 && (b_ld & 3) == 0;
-    a.shift = shift_dev; a.scale = scale_dev; a.gamma = gamma; a.h = h_dev; a.prev = prev_dev; a.omega = omega; a.logw = logw_dev;
-    a.pot = pot_dev; a.out_h = out_h_dev;
-    const size_t cells = (size_t)nseg * na;
+    a.gamma = gamma; a.h = h_dev; a.prev = prev_dev; a.omega = omega; a.logw = logw_dev; a.pot = pot_dev; a.out_h = out_h_dev;
+    const size_t cells = (size_t)a.nseg * na;
     char* ws = static_cast<char*>(ws_dev);
     a.cell_m = reinterpret_cast<double*>(ws);
     a.cell_s = a.cell_m + cells;
     a.flag = reinterpret_cast<uint32_t*>(ws + cells * 16u);
     a.ra = reinterpret_cast<float*>(ws + cells * 20u);
     a.rb = a.ra + na;
-    hipLaunchKernelGGL(k_sk_norms, dim3((unsigned)(((uint64_t)na + nb + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, a);
-    if (const int rc = check_launch(what)) return rc;
-    if (d <= D3P_GRAM_RES) return pair_launch_merged(what, k_sk_walk<true>, k_sk_merge, (unsigned)groups, na, (hipStream_t)stream, a);
-    return pair_launch_merged(what, k_sk_walk<false>, k_sk_merge, (unsigned)groups, na, (hipStream_t)stream, a);
+    if (const int rc = gram_launch_norms(what, k_sk_norms, (hipStream_t)stream, a)) return rc;
+    if (d <= D3P_GRAM_RES) return pair_launch_merged(what, k_sk_walk<true>, k_sk_merge, groups, na, (hipStream_t)stream, a);
+    return pair_launch_merged(what, k_sk_walk<false>, k_sk_merge, groups, na, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

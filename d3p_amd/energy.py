@@ -38,13 +38,12 @@ from . import _lib
 from . import infer_util as U
 from . import mixture as MX
 from ._lib import check, ptr, stream_ptr
+from ._tables import INT_EXACT, check_exact, dtype_code
 from .models import GaussianMixtureGuide, GaussianMixtureModel
 from .scoring import _mean_and_se, _observations
 
 __all__ = ["energy_score_draws", "energy_score", "draws_limit", "posterior_predictive_energy_score", "compare_energy_scores",
            "EnergyScoreResult", "EnergyScoreComparison", "INT_EXACT"]
-
-INT_EXACT = 2 ** 24   # |v| <= 2^24: every int32 the float32 conversion keeps exactly
 
 
 class EnergyScoreResult(NamedTuple):
@@ -107,7 +106,7 @@ def _score(draws, dims, y):
     n, rows, d, ld_draw, ld_row = dims
     out = torch.empty((4, rows), dtype=torch.float32, device=draws.device)
     if rows:
-        check(_lib.load().d3p_energy_score(stream_ptr(), ptr(draws), 0 if draws.dtype == torch.float32 else 1, ld_draw, ld_row, n, rows, d,
+        check(_lib.load().d3p_energy_score(stream_ptr(), ptr(draws), dtype_code(draws), ld_draw, ld_row, n, rows, d,
                                            ptr(y), d, ptr(out), rows))
     return {"es": out[0], "es_fair": out[1], "mae": out[2], "spread": out[3]}
 
@@ -120,11 +119,7 @@ def _energy_score_draws(draws, y, what):
     _lib.require_device()   # (every check above runs without a device)
     with torch.cuda.device(draws.device):
         y = y.to(draws.device).contiguous()
-        if draws.dtype == torch.int32 and draws.numel():
-            # the one check that has to read the draws
-            if bool(((draws > INT_EXACT) | (draws < -INT_EXACT)).any()) or bool(((y > INT_EXACT) | (y < -INT_EXACT)).any()):
-                raise ValueError(f"{what}: int32 values beyond 2^24 in magnitude: the kernel converts to float32, which is exact only up "
-                                 "to there (score a float32 tensor instead)")
+        check_exact(((None, draws), (None, y)), what, advice="score")   # the one check that has to read the draws
         return _score(draws, dims, y)
 
 

@@ -64,13 +64,12 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
+from . import _tables as T
 from . import clipping as CL
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["pair_stats", "energy_distance", "closest_record", "fidelity_report", "EnergyDistance", "FidelityReport", "INT_EXACT"]
-
-_MAX_ROWS = 2 ** 32 - 2   # (argmin is a uint32 and 0xFFFFFFFF stands for "none")
 
 
 class EnergyDistance(NamedTuple):
@@ -102,51 +101,6 @@ class FidelityReport(NamedTuple):
     dim: int
 
 
-def _check_table(t, name, what):
-    """(n, d, ld) of one table after the host checks."""
-    if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.dtype not in (torch.float32, torch.int32):
-        raise ValueError(f"{what}: {name}: a 2-D float32 or int32 CUDA tensor (rows, d) is required (1-D (rows,): d = 1)")
-    n = int(t.shape[0])
-    d = int(t.shape[1]) if t.dim() == 2 else 1
-    if n < 1:
-        raise ValueError(f"{what}: {name}: at least one row")
-    if d < 1:
-        raise ValueError(f"{what}: {name}: d >= 1 is required")
-    if n > _MAX_ROWS:
-        raise ValueError(f"{what}: {name}: {n} rows; at most {_MAX_ROWS} (the nearest row's index is a uint32)")
-    if t.dim() == 2 and d > 1 and t.stride(1) != 1:
-        raise ValueError(f"{what}: {name}: the columns must have unit stride (the rows may be strided)")
-    ld = int(t.stride(0)) if n > 1 else d
-    if ld < d:
-        raise ValueError(f"{what}: {name}: the rows of the tensor overlap (strides {tuple(t.stride())})")
-    return n, d, ld
-
-
-def _check_pair(a, b, names, what):
-    da, db = _check_table(a, names[0], what), _check_table(b, names[1], what)
-    if a.dtype != b.dtype:
-        raise ValueError(f"{what}: {names[0]} is {a.dtype} and {names[1]} is {b.dtype}: one dtype for both tables")
-    if da[1] != db[1]:
-        raise ValueError(f"{what}: {names[0]} has {da[1]} columns and {names[1]} has {db[1]}: one d for both tables")
-    return da, db
-
-
-def _check_devices(tables, what):
-    for name, t in tables:
-        if not t.is_cuda:
-            raise ValueError(f"{what}: {name}: a 2-D float32 or int32 CUDA tensor (rows, d) is required (1-D (rows,): d = 1)")
-    if len({t.device for _, t in tables}) != 1:
-        raise ValueError(f"{what}: the tables lie on different devices")
-
-
-def _check_exact(tables, what):
-    """The one check that has to read the tables (on the device)."""
-    for name, t in tables:
-        if t.dtype == torch.int32 and bool(((t > INT_EXACT) | (t < -INT_EXACT)).any()):
-            raise ValueError(f"{what}: {name}: int32 values beyond 2^24 in magnitude: the kernel converts to float32, which is exact only "
-                             "up to there (pass a float32 tensor instead)")
-
-
 def _walk(a, da, b, db, exclude):
     """One call of d3p_pair_stats on checked tables: the three per-row outputs."""
     (na, d, a_ld), (nb, _, b_ld) = da, db
@@ -157,7 +111,7 @@ def _walk(a, da, b, db, exclude):
     am = torch.empty(na, dtype=torch.int32, device=dev)
     need = int(lib.d3p_pair_stats_workspace(na, nb, d))
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-    check(lib.d3p_pair_stats(stream_ptr(), ptr(a), ptr(b), 0 if a.dtype == torch.float32 else 1, a_ld, b_ld, na, nb, d, 1 if exclude else 0,
+    check(lib.d3p_pair_stats(stream_ptr(), ptr(a), ptr(b), T.dtype_code(a), a_ld, b_ld, na, nb, d, 1 if exclude else 0,
                              ptr(s), ptr(m), ptr(am), ptr(ws), int(ws.numel()) if need else 0))
     idx = am.to(torch.int64) & 0xFFFFFFFF
     return {"sum": s, "min": m, "argmin": torch.where(idx == 0xFFFFFFFF, torch.full_like(idx, -1), idx)}
@@ -168,16 +122,11 @@ def pair_stats(a, b, exclude_diagonal=False):
     index (module docstring): ``{"sum", "min", "argmin"}`` on the tables' device.  ``exclude_diagonal=True`` leaves out ``j == i`` (a
     table against itself: ``n_a == n_b``)."""
     what = "pair_stats"
-    da, db = _check_pair(a, b, ("a", "b"), what)
-    if not isinstance(exclude_diagonal, (bool, int)) or exclude_diagonal not in (0, 1):
-        raise ValueError(f"{what}: exclude_diagonal must be a bool")
-    if exclude_diagonal and da[0] != db[0]:
-        raise ValueError(f"{what}: exclude_diagonal compares a table with itself: {da[0]} rows against {db[0]}")
-    _check_devices((("a", a), ("b", b)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(a.device):
-        _check_exact((("a", a), ("b", b)), what)
-        return _walk(a, da, b, db, bool(exclude_diagonal))
+    da, db = T.check_pair(a, b, ("a", "b"), what)
+    exclude = T.check_diagonal(exclude_diagonal, da, db, what)
+    tables = (("a", a), ("b", b))
+    with T.on_device(tables, what, exact=tables):
+        return _walk(a, da, b, db, exclude)
 
 
 def _energy(sxy, sxx, syy, nx, ny, d):
@@ -194,11 +143,9 @@ def energy_distance(x, y):
     whole ``x x x`` and ``y x y`` walks are done, not their ``i < j`` halves: twice the minimal work, and what ``fidelity_report`` needs
     of them is then ready."""
     what = "energy_distance"
-    dx, dy = _check_pair(x, y, ("x", "y"), what)
-    _check_devices((("x", x), ("y", y)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        _check_exact((("x", x), ("y", y)), what)
+    dx, dy = T.check_pair(x, y, ("x", "y"), what)
+    tables = (("x", x), ("y", y))
+    with T.on_device(tables, what, exact=tables):
         xy, xx, yy = _walk(x, dx, y, dy, False), _walk(x, dx, x, dx, True), _walk(y, dy, y, dy, True)
         return _energy(xy["sum"], xx["sum"], yy["sum"], dx[0], dy[0], dx[1])
 
@@ -207,11 +154,9 @@ def closest_record(synthetic, real):
     """The distance to the closest record: per row of ``synthetic`` the distance to its nearest row of ``real`` and that row's index,
     ``{"distance": (n,) float32, "index": (n,) int64}``."""
     what = "closest_record"
-    ds, dr = _check_pair(synthetic, real, ("synthetic", "real"), what)
-    _check_devices((("synthetic", synthetic), ("real", real)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(synthetic.device):
-        _check_exact((("synthetic", synthetic), ("real", real)), what)
+    ds, dr = T.check_pair(synthetic, real, ("synthetic", "real"), what)
+    tables = (("synthetic", synthetic), ("real", real))
+    with T.on_device(tables, what, exact=tables):
         out = _walk(synthetic, ds, real, dr, False)
         return {"distance": out["min"], "index": out["argmin"]}
 
@@ -226,12 +171,8 @@ def fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95), sch
     by the accountant.  With a ``schema`` (``d3p_amd.mixed.mixed_schema``: some columns are categorical) every walk is Gower's distance
     of ``d3p_amd.mixed`` and every distance is in its units; with ``None`` the walks are the Euclidean ones, bit for bit."""
     what = "fidelity_report"
-    dt, ds = _check_pair(train, synthetic, ("train", "synthetic"), what)
-    tables = [("train", train), ("synthetic", synthetic)]
-    dh = None
-    if holdout is not None:
-        dh, _ = _check_pair(holdout, synthetic, ("holdout", "synthetic"), what)
-        tables.append(("holdout", holdout))
+    tables = T.check_group(train, synthetic, holdout, ("train", "synthetic", "holdout"), what, against=1)
+    dt, ds, dh = ([dims for _, _, dims in tables] + [None])[:3]
     ps = CL._check_probs(probs)
     walk = _walk
     if schema is not None:
@@ -241,10 +182,7 @@ def fidelity_report(train, synthetic, holdout=None, probs=(0.05, 0.5, 0.95), sch
         def walk(a, da, b, db, exclude):
             out = mixed._walk(a, da, b, db, exclude, schema)
             return {"sum": out["sum"], "min": out["min"].to(torch.float32), "argmin": out["argmin"]}   # (the profile takes float32)
-    _check_devices(tables, what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(train.device):
-        _check_exact(tables, what)
+    with T.on_device(tables, what, exact=tables):
         st, ss, tt = walk(synthetic, ds, train, dt, False), walk(synthetic, ds, synthetic, ds, True), walk(train, dt, train, dt, True)
         ts = walk(train, dt, synthetic, ds, False)
         e_train = _energy(st["sum"], ss["sum"], tt["sum"], ds[0], dt[0], ds[1])

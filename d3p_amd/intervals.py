@@ -62,6 +62,7 @@ from . import modelling as M
 from . import prediction as PM
 from . import predictive as PS
 from ._lib import check, ptr, stream_ptr
+from ._tables import dtype_code
 
 __all__ = ["quantiles", "hpdi", "credible_interval", "posterior_credible_interval", "predictive_interval", "posterior_predictive_interval",
            "latent_summary"]
@@ -159,7 +160,7 @@ class _Rule:
 
     def reduce(self, first, dtype, ld, n, cols, args, out, out_ld):
         """The (n, cols) matrix that starts at tensor `first`, reduced into out (a tensor at the first output element): out_rows rows."""
-        check(getattr(_lib.load(), self.entry)(stream_ptr(), ptr(first), 0 if dtype == torch.float32 else 1, ld, n, cols, len(self.probs), *args,
+        check(getattr(_lib.load(), self.entry)(stream_ptr(), ptr(first), dtype_code(dtype), ld, n, cols, len(self.probs), *args,
                                                ptr(out), out_ld))
 
     def result(self, q):

@@ -64,8 +64,9 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
+from . import _tables as T
 from ._lib import check, ptr, stream_ptr
-from .fidelity import INT_EXACT, _check_devices, _check_exact, _check_table
+from ._tables import INT_EXACT
 
 __all__ = ["bin_edges", "marginal_counts", "marginal_fidelity", "BinEdges", "MarginalCounts", "MarginalFidelity", "MAX_BINS", "INT_EXACT"]
 
@@ -246,14 +247,11 @@ def bin_edges(reference, bins=16, kind="quantile"):
     tensors.  ``bins``: the number of bins per column, or a list of per-column edge sequences (then ``kind`` is ignored and the table is
     not read)."""
     what = "bin_edges"
-    _, d, _ = _check_table(reference, "reference", what)
+    _, d, _ = T.check_table(reference, "reference", what)
     if isinstance(bins, (list, tuple)):
         return _given_edges(bins, d, what)
     bins, kind = _check_bins(bins, what), _check_kind(kind, what)
-    _check_devices((("reference", reference),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(reference.device):
-        _check_exact((("reference", reference),), what)
+    with T.on_device((("reference", reference),), what, exact=(("reference", reference),)):
         rows = _edges_on_device(reference, bins, kind, what)
     edges, nbins, _ = _pack(rows, what)
     full = torch.zeros((d, max(bins - 1, 1)), dtype=torch.float32)
@@ -274,7 +272,7 @@ def _counts(x, dims, e, nb, B):
     two = torch.empty((max(P, 1), K, K), dtype=torch.int32, device=dev)
     need = int(lib.d3p_marginals_workspace(n, d, B))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    check(lib.d3p_marginals(stream_ptr(), ptr(x), 0 if x.dtype == torch.float32 else 1, ld, n, d, B, ptr(nb_dev), ptr(e_dev), ptr(one), ptr(two),
+    check(lib.d3p_marginals(stream_ptr(), ptr(x), T.dtype_code(x), ld, n, d, B, ptr(nb_dev), ptr(e_dev), ptr(one), ptr(two),
                             ptr(ws), int(ws.numel())))
     one, two = one.to(torch.int64), two[:P].to(torch.int64)
     if n >= 2 ** 31:     # (the outputs are uint32)
@@ -287,13 +285,10 @@ def marginal_counts(x, edges, max_bytes=2 ** 30):
     """The one-way and two-way counts of the table ``x`` cut at ``edges`` (module docstring): ``MarginalCounts`` of int64 tensors on the
     table's device.  This is the kernel call."""
     what = "marginal_counts"
-    dims = _check_table(x, "x", what)
+    dims = T.check_table(x, "x", what)
     e, nb, B = _check_edges(edges, dims[1], what)
     _check_size(dims[1], B, max_bytes, what)
-    _check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        _check_exact((("x", x),), what)
+    with T.on_device((("x", x),), what, exact=(("x", x),)):
         return _counts(x, dims, e, nb, B)
 
 
@@ -349,7 +344,7 @@ def marginal_fidelity(real, synthetic, bins=16, kind="quantile", columns=None, h
     PRIVATE tables and are not covered by the accountant."""
     what = "marginal_fidelity"
     tables = [("real", real), ("synthetic", synthetic)] + ([("holdout", holdout)] if holdout is not None else [])
-    dims = [_check_table(t, name, what) for name, t in tables]
+    dims = [T.check_table(t, name, what) for name, t in tables]
     for (name, t), dm in zip(tables[1:], dims[1:]):
         if t.dtype != real.dtype:
             raise ValueError(f"{what}: real is {real.dtype} and {name} is {t.dtype}: one dtype for all tables")
@@ -366,10 +361,7 @@ def marginal_fidelity(real, synthetic, bins=16, kind="quantile", columns=None, h
     if isinstance(top, bool) or not isinstance(top, int) or top < 0:
         raise ValueError(f"{what}: top must be a non-negative int")
     _check_size(d, given.max_bins if given else bins, max_bytes, what)
-    _check_devices(tables, what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(real.device):
-        _check_exact(tables, what)
+    with T.on_device(tables, what, exact=tables):
         if cols is not None:     # a contiguous copy of the chosen columns
             idx = torch.tensor(cols, dtype=torch.int64, device=real.device)
             tables = [(name, _as2d(t).index_select(1, idx).contiguous()) for name, t in tables]

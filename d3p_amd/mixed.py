@@ -38,9 +38,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _tables as T
 from . import fidelity as F
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["MixedSchema", "mixed_schema", "pair_stats", "energy_distance", "closest_record", "INT_EXACT"]
 
@@ -71,7 +72,7 @@ def mixed_schema(real, categorical, weights=None):
     d)``, possibly none or all), ``weights`` is ``None`` (1 each) or ``d`` finite weights ``>= 0`` with a positive sum, equal on the
     categorical columns.  The ranges of the numeric columns are ``max - min`` of ``real`` in float64: functions of the PRIVATE table."""
     what = "mixed_schema"
-    n, d, _ = F._check_table(real, "real", what)
+    n, d, _ = T.check_table(real, "real", what)
     try:
         cats = [int(c) for c in categorical]
         ok = all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) for c in categorical)
@@ -100,11 +101,9 @@ def mixed_schema(real, categorical, weights=None):
     w_cat = float(np.float32(w[cats[0]])) if cats else 0.0
     if not math.isfinite(w_cat):
         raise ValueError(f"{what}: weights: the categorical weight overflows float32")
-    F._check_devices((("real", real),), what)
-    _lib.require_device()   # (every check above runs without a device)
     kind = [1 if c in set(cats) else 0 for c in range(d)]
     table = real if real.dim() == 2 else real[:, None]
-    with torch.cuda.device(real.device):
+    with T.on_device((("real", real),), what):
         t64 = table.to(torch.float64)
         rng = (t64.max(dim=0).values - t64.min(dim=0).values).cpu().tolist()
     scale, ranges = [], []
@@ -136,7 +135,7 @@ def _walk(a, da, b, db, exclude, schema):
     am = torch.empty(na, dtype=torch.int32, device=dev)
     need = int(lib.d3p_pair_stats_mixed_workspace(na, nb, d - dc, dc))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    check(lib.d3p_pair_stats_mixed(stream_ptr(), ptr(a), ptr(b), 0 if a.dtype == torch.float32 else 1, a_ld, b_ld, na, nb, d,
+    check(lib.d3p_pair_stats_mixed(stream_ptr(), ptr(a), ptr(b), T.dtype_code(a), a_ld, b_ld, na, nb, d,
                                    C.cast(kind, C.c_void_p), C.cast(scale, C.c_void_p), schema.w_cat, 1 if exclude else 0,
                                    ptr(s), ptr(m), ptr(am), ptr(ws), need))
     idx = am.to(torch.int64) & 0xFFFFFFFF
@@ -149,17 +148,12 @@ def pair_stats(a, b, schema, exclude_diagonal=False):
     row's index (module docstring): ``{"sum", "min", "argmin"}`` on the tables' device, the kernel's values divided by ``W`` in float64.
     These are functions of the PRIVATE tables and are not covered by the accountant."""
     what = "mixed.pair_stats"
-    da, db = F._check_pair(a, b, ("a", "b"), what)
+    da, db = T.check_pair(a, b, ("a", "b"), what)
     _check_schema(schema, da[1], what)
-    if not isinstance(exclude_diagonal, (bool, int)) or exclude_diagonal not in (0, 1):
-        raise ValueError(f"{what}: exclude_diagonal must be a bool")
-    if exclude_diagonal and da[0] != db[0]:
-        raise ValueError(f"{what}: exclude_diagonal compares a table with itself: {da[0]} rows against {db[0]}")
-    F._check_devices((("a", a), ("b", b)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(a.device):
-        F._check_exact((("a", a), ("b", b)), what)
-        return _walk(a, da, b, db, bool(exclude_diagonal), schema)
+    exclude = T.check_diagonal(exclude_diagonal, da, db, what)
+    tables = (("a", a), ("b", b))
+    with T.on_device(tables, what, exact=tables):
+        return _walk(a, da, b, db, exclude, schema)
 
 
 def energy_distance(x, y, schema):
@@ -167,12 +161,10 @@ def energy_distance(x, y, schema):
     of 0-d float64 tensors, from the three walks of ``fidelity.energy_distance``.  A function of the PRIVATE tables, not covered by the
     accountant."""
     what = "mixed.energy_distance"
-    dx, dy = F._check_pair(x, y, ("x", "y"), what)
+    dx, dy = T.check_pair(x, y, ("x", "y"), what)
     _check_schema(schema, dx[1], what)
-    F._check_devices((("x", x), ("y", y)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        F._check_exact((("x", x), ("y", y)), what)
+    tables = (("x", x), ("y", y))
+    with T.on_device(tables, what, exact=tables):
         xy, xx, yy = _walk(x, dx, y, dy, False, schema), _walk(x, dx, x, dx, True, schema), _walk(y, dy, y, dy, True, schema)
         return F._energy(xy["sum"], xx["sum"], yy["sum"], dx[0], dy[0], dx[1])
 
@@ -181,11 +173,9 @@ def closest_record(synthetic, real, schema):
     """The Gower distance to the closest record: per row of ``synthetic`` the distance to its nearest row of ``real`` and that row's
     index, ``{"distance": (n,) float64, "index": (n,) int64}``.  A function of the PRIVATE tables, not covered by the accountant."""
     what = "mixed.closest_record"
-    ds, dr = F._check_pair(synthetic, real, ("synthetic", "real"), what)
+    ds, dr = T.check_pair(synthetic, real, ("synthetic", "real"), what)
     _check_schema(schema, ds[1], what)
-    F._check_devices((("synthetic", synthetic), ("real", real)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(synthetic.device):
-        F._check_exact((("synthetic", synthetic), ("real", real)), what)
+    tables = (("synthetic", synthetic), ("real", real))
+    with T.on_device(tables, what, exact=tables):
         out = _walk(synthetic, ds, real, dr, False, schema)
         return {"distance": out["min"], "index": out["argmin"]}

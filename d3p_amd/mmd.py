@@ -51,16 +51,14 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
+from . import _tables as T
 from . import covariance as CV
-from . import fidelity as FD
-from . import univariate as UV
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["kernel_sums", "mmd", "MMD", "INT_EXACT"]
 
 MAX_BANDWIDTHS = 8
-_MEDIAN_ROWS = 1024
 
 
 class MMD(NamedTuple):
@@ -83,25 +81,13 @@ def _check_bandwidths(n_bandwidths, what):
     return n_bandwidths
 
 
-def _check_positive(v, name, what):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v > 0 and math.isfinite(v)):
-        raise ValueError(f"{what}: {name} must be a finite number > 0, got {v!r}")
-    return float(v)
-
-
-def _check_vector(v, name, d, what):
-    if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (d,) or not v.is_contiguous()):
-        raise ValueError(f"{what}: {name} must be None or a contiguous float32 tensor of shape ({d},)")
-    return v
-
-
 def _sums(a, da, b, db, gamma0, n_bandwidths, shift, scale, exclude):
     """One call of d3p_kernel_sums on checked tables: the (B, n_a) float64 sums."""
     (na, d, a_ld), (nb, _, b_ld) = da, db
     lib = _lib.load()
     out = torch.empty((n_bandwidths, na), dtype=torch.float64, device=a.device)
     ws = torch.empty(int(lib.d3p_kernel_sums_workspace(na, nb, n_bandwidths)), dtype=torch.uint8, device=a.device)
-    check(lib.d3p_kernel_sums(stream_ptr(), ptr(a), ptr(b), 0 if a.dtype == torch.float32 else 1, a_ld, b_ld, na, nb, d, ptr(shift), ptr(scale),
+    check(lib.d3p_kernel_sums(stream_ptr(), ptr(a), ptr(b), T.dtype_code(a), a_ld, b_ld, na, nb, d, ptr(shift), ptr(scale),
                               gamma0, n_bandwidths, 1 if exclude else 0, ptr(out), ptr(ws), int(ws.numel())))
     return out
 
@@ -110,22 +96,17 @@ def kernel_sums(a, b, gamma0, n_bandwidths=1, shift=None, scale=None, exclude_di
     """Per row of ``a`` and per bandwidth the float64 sum of ``exp2(-gamma0 2^b q)`` over the rows of ``b`` (module docstring): ``(B,
     n_a)`` on the tables' device.  ``exclude_diagonal=True`` leaves out ``j == i`` (a table against itself: ``n_a == n_b``)."""
     what = "kernel_sums"
-    da, db = FD._check_pair(a, b, ("a", "b"), what)
-    UV._check_rows(da, "a", what, False)
-    UV._check_rows(db, "b", what, False)
-    gamma0 = _check_positive(gamma0, "gamma0", what)
+    da, db = T.check_pair(a, b, ("a", "b"), what)
+    T.check_rows(da, "a", what, False)
+    T.check_rows(db, "b", what, False)
+    gamma0 = T.check_positive(gamma0, "gamma0", what)
     _check_bandwidths(n_bandwidths, what)
-    _check_vector(shift, "shift", da[1], what)
-    _check_vector(scale, "scale", da[1], what)
-    if not isinstance(exclude_diagonal, (bool, int)) or exclude_diagonal not in (0, 1):
-        raise ValueError(f"{what}: exclude_diagonal must be a bool")
-    if exclude_diagonal and da[0] != db[0]:
-        raise ValueError(f"{what}: exclude_diagonal compares a table with itself: {da[0]} rows against {db[0]}")
-    FD._check_devices([("a", a), ("b", b)] + [(n, v) for n, v in (("shift", shift), ("scale", scale)) if v is not None], what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(a.device):
-        FD._check_exact((("a", a), ("b", b)), what)
-        return _sums(a, da, b, db, gamma0, n_bandwidths, shift, scale, bool(exclude_diagonal))
+    T.check_column_vector(shift, "shift", da[1], what)
+    T.check_column_vector(scale, "scale", da[1], what)
+    exclude = T.check_diagonal(exclude_diagonal, da, db, what)
+    tables = (("a", a), ("b", b))
+    with T.on_device(tables + (("shift", shift), ("scale", scale)), what, exact=tables):
+        return _sums(a, da, b, db, gamma0, n_bandwidths, shift, scale, exclude)
 
 
 def _ladder(centre, n_bandwidths):
@@ -147,45 +128,28 @@ def _closing(sxy, syx, sxx, syy, sigma2, d):
                witness_x, witness_y, nx, ny, d)
 
 
-def _median_q(x, y, shift, scale):
-    """The median squared distance, in the shifted and scaled space, over the pairs of the pooled strided subsamples (float64)."""
-    rows = []
-    for t in (x, y):
-        n = int(t.shape[0])
-        z = t.reshape(n, -1)[::-(-n // _MEDIAN_ROWS)].to(torch.float32) - shift
-        rows.append((z * scale if scale is not None else z).to(torch.float64))
-    z = torch.cat(rows)
-    q = torch.cdist(z, z, compute_mode="donot_use_mm_for_euclid_dist") ** 2
-    i, j = torch.triu_indices(z.shape[0], z.shape[0], offset=1, device=z.device)
-    return float(q[i, j].median())
-
-
 def mmd(x, y, bandwidth="median", n_bandwidths=5, scale="std"):
     """The squared maximum mean discrepancy of ``y`` against ``x`` under Gaussian kernels of ``n_bandwidths`` bandwidths, with the
     witness function at every row (module docstring): an ``MMD``.  These are functions of the PRIVATE tables and are not covered by the
     accountant."""
     what = "mmd"
-    dx, dy = FD._check_pair(x, y, ("x", "y"), what)
-    UV._check_rows(dx, "x", what, False)
-    UV._check_rows(dy, "y", what, False)
+    dx, dy = T.check_pair(x, y, ("x", "y"), what)
+    T.check_rows(dx, "x", what, False)
+    T.check_rows(dy, "y", what, False)
     if not (isinstance(bandwidth, str) and bandwidth == "median"):
         if isinstance(bandwidth, str):
             raise ValueError(f"{what}: bandwidth must be 'median' or a finite number > 0 (the centre sigma^2), got {bandwidth!r}")
-        bandwidth = _check_positive(bandwidth, "bandwidth", what)
+        bandwidth = T.check_positive(bandwidth, "bandwidth", what)
     _check_bandwidths(n_bandwidths, what)
     if not (scale is None or (isinstance(scale, str) and scale == "std")):
         raise ValueError(f"{what}: scale must be 'std' or None, got {scale!r}")
-    FD._check_devices((("x", x), ("y", y)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        FD._check_exact((("x", x), ("y", y)), what)
-        mom = CV._moments(x, dx)
-        shift = mom.mean.to(torch.float32)
+    tables = (("x", x), ("y", y))
+    with T.on_device(tables, what, exact=tables):
+        shift, inv_std = CV.standardise(x, dx)
         if scale is not None:
-            sd = (mom.m2.diagonal() / float(dx[0] - 1)).sqrt() if dx[0] > 1 else torch.zeros_like(mom.mean)
-            scale = torch.where(sd > 0, 1.0 / sd, torch.zeros_like(sd)).to(torch.float32)
+            scale = inv_std.to(torch.float32)
         if isinstance(bandwidth, str):
-            bandwidth = _median_q(x, y, shift, scale)
+            bandwidth = T.median_q(x, y, shift, scale)
             if not (bandwidth > 0 and math.isfinite(bandwidth)):
                 raise ValueError(f"{what}: the median squared distance of the subsample is {bandwidth}: pass a bandwidth")
         sigma2, gamma0 = _ladder(bandwidth, n_bandwidths)

@@ -56,9 +56,9 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
+from . import _tables as T
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
-from .fidelity import _check_devices, _check_exact, _check_pair
+from ._tables import INT_EXACT
 
 __all__ = ["knn", "kth_neighbour", "ball_counts", "prdc", "max_k", "PRDC", "INT_EXACT"]
 
@@ -87,14 +87,6 @@ def _check_k(k, what):
     return k
 
 
-def _check_flag(exclude_diagonal, da, db, what):
-    if not isinstance(exclude_diagonal, (bool, int)) or exclude_diagonal not in (0, 1):
-        raise ValueError(f"{what}: exclude_diagonal must be a bool")
-    if exclude_diagonal and da[0] != db[0]:
-        raise ValueError(f"{what}: exclude_diagonal compares a table with itself: {da[0]} rows against {db[0]}")
-    return bool(exclude_diagonal)
-
-
 def _check_radius(radius_sq, nb, what):
     if not isinstance(radius_sq, torch.Tensor) or radius_sq.dim() != 1 or radius_sq.dtype != torch.float32 or int(radius_sq.shape[0]) != nb:
         raise ValueError(f"{what}: radius_sq: a 1-D float32 CUDA tensor of {nb} squared radii, one per row of b, is required")
@@ -112,7 +104,7 @@ def _walk(a, da, b, db, k, exclude, radius_sq):
     rad = radius_sq.contiguous() if radius_sq is not None else None
     need = int(lib.d3p_pair_knn_workspace(na, nb, d, k))
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-    check(lib.d3p_pair_knn(stream_ptr(), ptr(a), ptr(b), 0 if a.dtype == torch.float32 else 1, a_ld, b_ld, na, nb, d, k, 1 if exclude else 0,
+    check(lib.d3p_pair_knn(stream_ptr(), ptr(a), ptr(b), T.dtype_code(a), a_ld, b_ld, na, nb, d, k, 1 if exclude else 0,
                            ptr(rad), ptr(sq), ptr(dist), ptr(index), ptr(count), ptr(ws), int(ws.numel()) if need else 0))
     idx = index.to(torch.int64) & 0xFFFFFFFF
     out = {"distance": dist, "sq": sq, "index": torch.where(idx == 0xFFFFFFFF, torch.full_like(idx, -1), idx)}
@@ -127,17 +119,13 @@ def knn(a, b, k, exclude_diagonal=False, radius_sq=None):
     ``radius_sq`` (squared radii, one per row of ``b``) ``"count"``: the number of rows of ``b`` whose ball contains it (module
     docstring).  ``exclude_diagonal=True`` leaves out ``j == i`` (a table against itself: ``n_a == n_b``)."""
     what = "knn"
-    da, db = _check_pair(a, b, ("a", "b"), what)
+    da, db = T.check_pair(a, b, ("a", "b"), what)
     k = _check_k(k, what)
-    exclude = _check_flag(exclude_diagonal, da, db, what)
-    tables = [("a", a), ("b", b)]
+    exclude = T.check_diagonal(exclude_diagonal, da, db, what)
     if radius_sq is not None:
         _check_radius(radius_sq, db[0], what)
-        tables.append(("radius_sq", radius_sq))
-    _check_devices(tables, what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(a.device):
-        _check_exact(tables[:2], what)
+    tables = (("a", a), ("b", b))
+    with T.on_device(tables + (("radius_sq", radius_sq),), what, exact=tables):
         return _walk(a, da, b, db, k, exclude, radius_sq)
 
 
@@ -145,12 +133,9 @@ def kth_neighbour(x, k):
     """The distance of every row of ``x`` to its ``k``-th nearest OTHER row of ``x``: ``{"distance": (n,), "sq": (n,)}`` float32, the
     radius of the row's k-NN ball (``+inf`` where the table has no more than ``k`` rows)."""
     what = "kth_neighbour"
-    dx, _ = _check_pair(x, x, ("x", "x"), what)
+    dx, _ = T.check_pair(x, x, ("x", "x"), what)
     k = _check_k(k, what)
-    _check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        _check_exact((("x", x),), what)
+    with T.on_device((("x", x),), what, exact=(("x", x),)):
         out = _walk(x, dx, x, dx, k, True, None)
         return {"distance": out["distance"][:, k - 1], "sq": out["sq"][:, k - 1]}
 
@@ -158,12 +143,10 @@ def kth_neighbour(x, k):
 def ball_counts(a, b, radius_sq):
     """Per row of ``a`` the number of rows ``j`` of ``b`` with ``sq(i, j) < radius_sq[j]``: ``(n_a,)`` int64 (-1: a flagged row)."""
     what = "ball_counts"
-    da, db = _check_pair(a, b, ("a", "b"), what)
+    da, db = T.check_pair(a, b, ("a", "b"), what)
     _check_radius(radius_sq, db[0], what)
-    _check_devices((("a", a), ("b", b), ("radius_sq", radius_sq)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(a.device):
-        _check_exact((("a", a), ("b", b)), what)
+    tables = (("a", a), ("b", b))
+    with T.on_device(tables + (("radius_sq", radius_sq),), what, exact=tables):
         return _walk(a, da, b, db, 1, False, radius_sq)["count"]
 
 
@@ -190,19 +173,12 @@ def prdc(real, synthetic, k=5, holdout=None):
     ``PRDC``, whose ``floor`` is ``prdc(real, holdout, k)`` when a holdout is given.  These are functions of the PRIVATE tables and are
     not covered by the accountant."""
     what = "prdc"
-    dr, ds = _check_pair(real, synthetic, ("real", "synthetic"), what)
-    tables = [("real", real), ("synthetic", synthetic)]
-    dh = None
-    if holdout is not None:
-        dh, _ = _check_pair(holdout, real, ("holdout", "real"), what)
-        tables.append(("holdout", holdout))
+    tables = T.check_group(real, synthetic, holdout, ("real", "synthetic", "holdout"), what)
+    dr, ds, dh = ([dims for _, _, dims in tables] + [None])[:3]
     k = _check_k(k, what)
-    for (name, _), dims in zip(tables, (dr, ds, dh)):
+    for name, _, dims in tables:
         if dims[0] < k + 1:
             raise ValueError(f"{what}: {name}: {dims[0]} rows; at least k + 1 = {k + 1} are required (every row needs k other rows)")
-    _check_devices(tables, what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(real.device):
-        _check_exact(tables, what)
+    with T.on_device(tables, what, exact=tables):
         floor = _prdc(real, dr, holdout, dh, k, None) if holdout is not None else None
         return _prdc(real, dr, synthetic, ds, k, floor)

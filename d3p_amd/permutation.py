@@ -58,9 +58,10 @@ from typing import NamedTuple, Tuple
 import torch
 
 from . import _lib
+from . import _tables as T
 from . import fidelity as FD
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["permutation_labels", "label_sums", "energy_test", "LabelSums", "EnergyTest", "INT_EXACT"]
 
@@ -90,23 +91,17 @@ class EnergyTest(NamedTuple):
     dim: int
 
 
-def _count(v, name, what, least):
-    if isinstance(v, bool) or not isinstance(v, int) or v < least:
-        raise ValueError(f"{what}: {name} must be an int >= {least}, got {v!r}")
-    return v
-
-
 def permutation_labels(n_x, n_y, n_perm, seed=0, device=None, _chunk=_LABEL_CHUNK):
     """The label words of the identity labelling (column 0: rows ``>= n_x`` set) and of ``n_perm`` uniform random subsets of ``n_y`` of
     the ``n_x + n_y`` pooled rows: a ``(ceil(m / 32), n_perm + 1)`` uint32 tensor on ``device`` (module docstring).  One generator draw per
     labelling: the output does not depend on the chunk size (``_chunk``, the labellings packed at once: a test aid)."""
     what = "permutation_labels"
-    n_x, n_y, n_perm = _count(n_x, "n_x", what, 1), _count(n_y, "n_y", what, 1), _count(n_perm, "n_perm", what, 1)
-    _count(seed, "seed", what, 0)
-    _count(_chunk, "_chunk", what, 1)
+    n_x, n_y, n_perm = T.check_int(n_x, "n_x", what, 1), T.check_int(n_y, "n_y", what, 1), T.check_int(n_perm, "n_perm", what, 1)
+    T.check_int(seed, "seed", what, 0)
+    T.check_int(_chunk, "_chunk", what, 1)
     m = n_x + n_y
-    if m > FD._MAX_ROWS:
-        raise ValueError(f"{what}: {m} pooled rows; at most {FD._MAX_ROWS}")
+    if m > T.MAX_ROWS:
+        raise ValueError(f"{what}: {m} pooled rows; at most {T.MAX_ROWS}")
     tiles = -(-m // _TILE)
     gen = torch.Generator(device="cpu")
     gen.manual_seed(seed)
@@ -152,7 +147,7 @@ def _sums(z, dz, labels, R, row_sum):
     n1 = torch.empty(R, dtype=torch.int32, device=dev)
     need = int(lib.d3p_pair_label_sums_workspace(m, d, R))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    check(lib.d3p_pair_label_sums(stream_ptr(), ptr(z), 0 if z.dtype == torch.float32 else 1, ld, m, d, R, ptr(labels), ptr(row_sum),
+    check(lib.d3p_pair_label_sums(stream_ptr(), ptr(z), T.dtype_code(z), ld, m, d, R, ptr(labels), ptr(row_sum),
                                   ptr(s11), ptr(s1t), ptr(n1), ptr(ws), int(ws.numel())))
     return s11, s1t, n1.to(torch.int64) & 0xFFFFFFFF
 
@@ -161,18 +156,16 @@ def label_sums(z, labels, row_sum=None):
     """``s11``, ``s1t`` and ``n1`` of every labelling in ``labels`` over the pooled table ``z`` (module docstring): a ``LabelSums`` on
     the table's device.  ``row_sum`` defaults to ``fidelity.pair_stats(z, z, True)["sum"]``."""
     what = "label_sums"
-    dz = FD._check_table(z, "z", what)
+    dz = T.check_table(z, "z", what)
     R = _check_labels(labels, dz[0], what)
     if row_sum is not None:
         if not isinstance(row_sum, torch.Tensor) or row_sum.dtype != torch.float64 or row_sum.dim() != 1 or int(row_sum.shape[0]) != dz[0] \
                 or not row_sum.is_contiguous():
             raise ValueError(f"{what}: row_sum: a contiguous float64 tensor ({dz[0]},) is required")
-    FD._check_devices((("z", z),), what)
+    T.check_devices((("z", z),), what)
     if labels.device != z.device or (row_sum is not None and row_sum.device != z.device):
         raise ValueError(f"{what}: z, labels and row_sum lie on different devices")
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(z.device):
-        FD._check_exact((("z", z),), what)
+    with T.on_device((("z", z),), what, exact=(("z", z),)):
         if row_sum is None:
             row_sum = FD.pair_stats(z, z, True)["sum"]
         s11, s1t, n1 = _sums(z, dz, labels, R, row_sum)
@@ -199,17 +192,15 @@ def energy_test(x, y, n_perm=999, seed=0):
     """The permutation test of the energy distance of the tables ``x`` and ``y`` (module docstring): an ``EnergyTest``.  These are
     functions of the PRIVATE tables and are not covered by the accountant."""
     what = "energy_test"
-    dx, dy = FD._check_pair(x, y, ("x", "y"), what)
-    n_perm = _count(n_perm, "n_perm", what, 1)
-    _count(seed, "seed", what, 0)
+    dx, dy = T.check_pair(x, y, ("x", "y"), what)
+    n_perm = T.check_int(n_perm, "n_perm", what, 1)
+    T.check_int(seed, "seed", what, 0)
     nx, ny, d = dx[0], dy[0], dx[1]
     m = nx + ny
-    if m > FD._MAX_ROWS:
-        raise ValueError(f"{what}: {m} pooled rows; at most {FD._MAX_ROWS}")
-    FD._check_devices((("x", x), ("y", y)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        FD._check_exact((("x", x), ("y", y)), what)
+    if m > T.MAX_ROWS:
+        raise ValueError(f"{what}: {m} pooled rows; at most {T.MAX_ROWS}")
+    tables = (("x", x), ("y", y))
+    with T.on_device(tables, what, exact=tables):
         z = torch.cat([x.reshape(nx, d), y.reshape(ny, d)], dim=0).contiguous()
         dz = (m, d, d)
         labels = permutation_labels(nx, ny, n_perm, seed, device=z.device)

@@ -38,6 +38,7 @@ from . import _lib
 from . import modelling as M
 from . import predictive as P
 from ._lib import check, ptr, stream_ptr
+from ._tables import dtype_code
 from .infer_util import _check_guide, _model_struct, _pack, _sample_shape
 
 __all__ = ["replicate_stats", "predictive_stats", "posterior_predictive_stats", "posterior_predictive_check", "ReplicateStats", "PPCResult",
@@ -183,7 +184,7 @@ def replicate_stats(matrix, shift=0.0):
         out = torch.empty((5, n), dtype=torch.float64, device=m.device)
         nbytes = int(lib.d3p_rep_stats_workspace(rows, n))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=m.device)
-        check(lib.d3p_rep_stats(stream_ptr(), ptr(m), 0 if m.dtype == torch.float32 else 1, ld, n, rows, shift, ptr(out), ptr(ws), nbytes))
+        check(lib.d3p_rep_stats(stream_ptr(), ptr(m), dtype_code(m), ld, n, rows, shift, ptr(out), ptr(ws), nbytes))
     return _result(out, rows, shift, single)
 
 

@@ -46,6 +46,7 @@ from . import intervals as IV
 from . import modelling as M
 from . import predictive as PS
 from ._lib import check, ptr, stream_ptr
+from ._tables import dtype_code
 
 __all__ = ["score_draws", "crps", "pit", "pit_histogram", "draws_limit", "predictive_crps", "posterior_predictive_crps", "compare_scores",
            "CRPSResult", "ScoreComparison"]
@@ -113,7 +114,7 @@ def _score(m, ld, n, cols, y):
     out = torch.empty((4, cols), dtype=torch.float32, device=m.device)
     counts = torch.empty((2, cols), dtype=torch.int32, device=m.device)
     if cols:
-        check(_lib.load().d3p_col_crps(stream_ptr(), ptr(m), 0 if m.dtype == torch.float32 else 1, ld, n, cols, ptr(y), ptr(out), cols,
+        check(_lib.load().d3p_col_crps(stream_ptr(), ptr(m), dtype_code(m), ld, n, cols, ptr(y), ptr(out), cols,
                                        ptr(counts), cols))
     return {"crps": out[0], "crps_fair": out[1], "mae": out[2], "spread": out[3], "below": counts[0], "equal": counts[1]}
 

@@ -54,12 +54,10 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
+from . import _tables as T
 from . import covariance as CV
-from . import fidelity as FD
-from . import mmd as MM
-from . import univariate as UV
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["softmin_rows", "sinkhorn_divergence", "SinkhornDivergence", "INT_EXACT"]
 
@@ -101,7 +99,7 @@ def _walk(a, da, b, db, gamma, h, shift, scale, prev, omega, logw):
     pot = torch.empty(na, dtype=torch.float64, device=a.device)
     out_h = torch.empty(na, dtype=torch.float32, device=a.device) if logw is not None else None
     ws = torch.empty(int(lib.d3p_softmin_rows_workspace(na, nb)), dtype=torch.uint8, device=a.device)
-    check(lib.d3p_softmin_rows(stream_ptr(), ptr(a), ptr(b), 0 if a.dtype == torch.float32 else 1, a_ld, b_ld, na, nb, d, ptr(shift), ptr(scale),
+    check(lib.d3p_softmin_rows(stream_ptr(), ptr(a), ptr(b), T.dtype_code(a), a_ld, b_ld, na, nb, d, ptr(shift), ptr(scale),
                                gamma, ptr(h), ptr(prev), omega, ptr(logw), ptr(pot), ptr(out_h), ptr(ws), int(ws.numel())))
     return pot, out_h
 
@@ -110,21 +108,18 @@ def softmin_rows(a, b, gamma, h, shift=None, scale=None, prev=None, omega=1.0, l
     """Per row of ``a`` the negated base-2 log-sum-exp of ``h_j - gamma q_ij`` over the rows of ``b``, averaged with ``prev`` by
     ``omega``, and with ``logw`` the float32 ``h`` of the opposite walk (module docstring): ``(pot, out_h)`` on the tables' device."""
     what = "softmin_rows"
-    da, db = FD._check_pair(a, b, ("a", "b"), what)
-    UV._check_rows(da, "a", what, False)
-    UV._check_rows(db, "b", what, False)
-    gamma = MM._check_positive(gamma, "gamma", what)
+    da, db = T.check_pair(a, b, ("a", "b"), what)
+    T.check_rows(da, "a", what, False)
+    T.check_rows(db, "b", what, False)
+    gamma = T.check_positive(gamma, "gamma", what)
     _check_rows_vector(h, "h", db[0], torch.float32, what, optional=False)
-    MM._check_vector(shift, "shift", da[1], what)
-    MM._check_vector(scale, "scale", da[1], what)
+    T.check_column_vector(shift, "shift", da[1], what)
+    T.check_column_vector(scale, "scale", da[1], what)
     _check_rows_vector(prev, "prev", da[0], torch.float64, what)
     omega = _check_omega(omega, what)
     _check_rows_vector(logw, "logw", da[0], torch.float32, what)
-    FD._check_devices([("a", a), ("b", b), ("h", h)] + [(n, v) for n, v in (("shift", shift), ("scale", scale), ("prev", prev), ("logw", logw))
-                                                         if v is not None], what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(a.device):
-        FD._check_exact((("a", a), ("b", b)), what)
+    tables = (("a", a), ("b", b))
+    with T.on_device(tables + (("h", h), ("shift", shift), ("scale", scale), ("prev", prev), ("logw", logw)), what, exact=tables):
         return _walk(a, da, b, db, gamma, h, shift, scale, prev, omega, logw)
 
 
@@ -162,38 +157,33 @@ def sinkhorn_divergence(x, y, epsilon="median", epsilon_share=0.05, wx=None, wy=
     potentials (module docstring): a ``SinkhornDivergence``.  These are functions of the PRIVATE tables and are not covered by the
     accountant."""
     what = "sinkhorn_divergence"
-    dx, dy = FD._check_pair(x, y, ("x", "y"), what)
-    UV._check_rows(dx, "x", what, False)
-    UV._check_rows(dy, "y", what, False)
+    dx, dy = T.check_pair(x, y, ("x", "y"), what)
+    T.check_rows(dx, "x", what, False)
+    T.check_rows(dy, "y", what, False)
     if not (isinstance(epsilon, str) and epsilon == "median"):
         if isinstance(epsilon, str):
             raise ValueError(f"{what}: epsilon must be 'median' or a finite number > 0, got {epsilon!r}")
-        epsilon = MM._check_positive(epsilon, "epsilon", what)
-    epsilon_share = MM._check_positive(epsilon_share, "epsilon_share", what)
+        epsilon = T.check_positive(epsilon, "epsilon", what)
+    epsilon_share = T.check_positive(epsilon_share, "epsilon_share", what)
     _check_weights(wx, "wx", dx[0], what)
     _check_weights(wy, "wy", dy[0], what)
-    for v, name in ((n_iter, "n_iter"), (check_every, "check_every")):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-            raise ValueError(f"{what}: {name} must be an int >= 1, got {v!r}")
-    tol = MM._check_positive(tol, "tol", what)
+    T.check_int(n_iter, "n_iter", what, 1)
+    T.check_int(check_every, "check_every", what, 1)
+    tol = T.check_positive(tol, "tol", what)
     if isinstance(scaling, bool) or not isinstance(scaling, (int, float)) or not 0.0 < scaling < 1.0:
         raise ValueError(f"{what}: scaling must be a number in (0, 1), got {scaling!r}")
     if not (scale is None or (isinstance(scale, str) and scale == "std")):
         raise ValueError(f"{what}: scale must be 'std' or None, got {scale!r}")
-    FD._check_devices([("x", x), ("y", y)] + [(n, v) for n, v in (("wx", wx), ("wy", wy)) if v is not None], what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
-        FD._check_exact((("x", x), ("y", y)), what)
+    tables = (("x", x), ("y", y))
+    with T.on_device(tables + (("wx", wx), ("wy", wy)), what, exact=tables):
         dev = x.device
         wxn, lwx = _log_weights(wx, dx[0], dev, "wx", what)
         wyn, lwy = _log_weights(wy, dy[0], dev, "wy", what)
-        mom = CV._moments(x, dx)
-        shift = mom.mean.to(torch.float32)
+        shift, inv_std = CV.standardise(x, dx)
         if scale is not None:
-            sd = (mom.m2.diagonal() / float(dx[0] - 1)).sqrt() if dx[0] > 1 else torch.zeros_like(mom.mean)
-            scale = torch.where(sd > 0, 1.0 / sd, torch.zeros_like(sd)).to(torch.float32)
+            scale = inv_std.to(torch.float32)
         if isinstance(epsilon, str):
-            epsilon = epsilon_share * MM._median_q(x, y, shift, scale)
+            epsilon = epsilon_share * T.median_q(x, y, shift, scale)
             if not (epsilon > 0 and math.isfinite(epsilon)):
                 raise ValueError(f"{what}: the median squared distance of the subsample gives epsilon = {epsilon}: pass an epsilon")
         rungs = []

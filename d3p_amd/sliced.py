@@ -48,11 +48,11 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
+from . import _tables as T
 from . import covariance as CV
-from . import fidelity as FD
 from . import univariate as UV
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["random_directions", "project", "w2_distance", "sliced_wasserstein", "SlicedWasserstein", "INT_EXACT"]
 
@@ -75,12 +75,6 @@ class SlicedWasserstein(NamedTuple):
     floor: Optional["SlicedWasserstein"]
 
 
-def _check_int(v, name, what, low):
-    if isinstance(v, bool) or not isinstance(v, int) or v < low:
-        raise ValueError(f"{what}: {name} must be an int >= {low}, got {v!r}")
-    return v
-
-
 def _check_scale(scale, d, what):
     if scale is None:
         return None
@@ -92,9 +86,9 @@ def _check_scale(scale, d, what):
 def random_directions(d, n_dirs, seed=0, scale=None, device=None):
     """``n_dirs`` random unit directions of ``d`` columns, times ``scale``, as a ``(d, n_dirs)`` float32 tensor (module docstring)."""
     what = "random_directions"
-    _check_int(d, "d", what, 1)
-    _check_int(n_dirs, "n_dirs", what, 1)
-    _check_int(seed, "seed", what, 0)
+    T.check_int(d, "d", what, 1)
+    T.check_int(n_dirs, "n_dirs", what, 1)
+    T.check_int(seed, "seed", what, 0)
     scale = _check_scale(scale, d, what)
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
@@ -114,12 +108,8 @@ def _check_theta(theta, shift, d, what):
     L = int(theta.shape[1])
     if L > 1 and theta.stride(1) != 1:
         raise ValueError(f"{what}: theta: the directions must have unit stride (the rows may be strided)")
-    ld_t = int(theta.stride(0)) if d > 1 else L
-    if ld_t < L:
-        raise ValueError(f"{what}: theta: the rows of the tensor overlap (strides {tuple(theta.stride())})")
-    if shift is not None and (not isinstance(shift, torch.Tensor) or shift.dtype != torch.float32 or tuple(shift.shape) != (d,)
-                              or not shift.is_contiguous()):
-        raise ValueError(f"{what}: shift must be None or a contiguous float32 tensor of shape ({d},)")
+    ld_t = T.check_row_stride(theta, "theta", what)
+    T.check_column_vector(shift, "shift", d, what)
     return L, ld_t
 
 
@@ -128,19 +118,16 @@ def _project(x, dx, theta, dt, shift):
     n, d, ld = dx
     L, ld_t = dt
     p = torch.empty((n, L), dtype=torch.float32, device=x.device)
-    check(_lib.load().d3p_project_rows(stream_ptr(), ptr(x), 0 if x.dtype == torch.float32 else 1, ld, n, d, ptr(theta), ld_t, L, ptr(shift),
-                                       ptr(p), L))
+    check(_lib.load().d3p_project_rows(stream_ptr(), ptr(x), T.dtype_code(x), ld, n, d, ptr(theta), ld_t, L, ptr(shift), ptr(p), L))
     return p
 
 
 def project(x, theta, shift=None):
     """The rows of ``x``, less ``shift``, projected onto the columns of ``theta`` (module docstring): ``(n, L)`` float32."""
     what = "project"
-    dx = UV._check_rows(FD._check_table(x, "x", what), "x", what, False)
+    dx = T.check_rows(T.check_table(x, "x", what), "x", what, False)
     dt = _check_theta(theta, shift, dx[1], what)
-    FD._check_devices([("x", x), ("theta", theta)] + ([("shift", shift)] if shift is not None else []), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
+    with T.on_device((("x", x), ("theta", theta), ("shift", shift)), what):
         return _project(x, dx, theta, dt, shift)
 
 
@@ -150,7 +137,7 @@ def _check_sorted(s, name, what):
     d, n = int(s.shape[0]), int(s.shape[1])
     if d < 1 or n < 1:
         raise ValueError(f"{what}: {name}: at least one column and one value per column")
-    if n > UV._MAX_ROWS:
+    if n > T.MAX_ROWS_SORTED:
         raise ValueError(f"{what}: {name}: {n} values per column; at most 2^31 - 1")
     if n > 1 and s.stride(1) != 1:
         raise ValueError(f"{what}: {name}: the values of a column must have unit stride")
@@ -166,8 +153,8 @@ def _w2(sa, da, sb, db):
     lib = _lib.load()
     out = torch.empty(d, dtype=torch.float64, device=sa.device)
     ws = torch.empty(int(lib.d3p_column_w2_distance_workspace(n_a, n_b, d)), dtype=torch.uint8, device=sa.device)
-    check(lib.d3p_column_w2_distance(stream_ptr(), ptr(sa), ld_a, n_a, ptr(sb), ld_b, n_b, 0 if sa.dtype == torch.float32 else 1, d, ptr(out),
-                                     ptr(ws), int(ws.numel())))
+    check(lib.d3p_column_w2_distance(stream_ptr(), ptr(sa), ld_a, n_a, ptr(sb), ld_b, n_b, T.dtype_code(sa), d, ptr(out), ptr(ws),
+                                     int(ws.numel())))
     return out
 
 
@@ -176,13 +163,8 @@ def w2_distance(sa, sb):
     functions of the PRIVATE tables and are not covered by the accountant."""
     what = "w2_distance"
     da, db = _check_sorted(sa, "sa", what), _check_sorted(sb, "sb", what)
-    if sa.dtype != sb.dtype:
-        raise ValueError(f"{what}: sa is {sa.dtype} and sb is {sb.dtype}: one dtype for both tables")
-    if da[0] != db[0]:
-        raise ValueError(f"{what}: sa has {da[0]} columns and sb has {db[0]}: one d for both tables")
-    FD._check_devices((("sa", sa), ("sb", sb)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(sa.device):
+    T.check_match(sa, sb, da[0], db[0], ("sa", "sb"), what)
+    with T.on_device((("sa", sa), ("sb", sb)), what):
         return _w2(sa, da, sb, db)
 
 
@@ -213,27 +195,19 @@ def sliced_wasserstein(real, synthetic, n_dirs=128, seed=0, scale="std", holdout
     ``holdout``, the noise floor that the holdout scores against ``real`` (module docstring): a ``SlicedWasserstein``.  These are
     functions of the PRIVATE tables and are not covered by the accountant."""
     what = "sliced_wasserstein"
-    dr, ds = FD._check_pair(real, synthetic, ("real", "synthetic"), what)
-    tables = [("real", real, dr), ("synthetic", synthetic, ds)]
-    if holdout is not None:
-        dh, _ = FD._check_pair(holdout, real, ("holdout", "real"), what)
-        tables.append(("holdout", holdout, dh))
+    tables = T.check_group(real, synthetic, holdout, ("real", "synthetic", "holdout"), what)
+    dr = tables[0][2]
     for name, _, dx in tables:
-        UV._check_rows(dx, name, what, False)
-    _check_int(n_dirs, "n_dirs", what, 1)
-    _check_int(seed, "seed", what, 0)
-    _check_int(slab_bytes, "slab_bytes", what, 1)
+        T.check_rows(dx, name, what, False)
+    T.check_int(n_dirs, "n_dirs", what, 1)
+    T.check_int(seed, "seed", what, 0)
+    T.check_int(slab_bytes, "slab_bytes", what, 1)
     if not (scale is None or (isinstance(scale, str) and scale == "std")):
         _check_scale(scale, dr[1], what)
-    FD._check_devices([(name, t) for name, t, _ in tables], what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(real.device):
-        FD._check_exact([(name, t) for name, t, _ in tables], what)
-        mom = CV._moments(real, dr)
-        shift = mom.mean.to(torch.float32)
+    with T.on_device(tables, what, exact=tables):
+        shift, inv_std = CV.standardise(real, dr)
         if isinstance(scale, str):
-            sd = (mom.m2.diagonal() / float(dr[0] - 1)).sqrt() if dr[0] > 1 else torch.zeros_like(mom.mean)
-            scale = torch.where(sd > 0, 1.0 / sd, torch.zeros_like(sd))
+            scale = inv_std
         theta = random_directions(dr[1], n_dirs, seed, scale, real.device)
         rep = []
         for _, t, dx in tables[1:]:

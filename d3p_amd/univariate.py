@@ -46,16 +46,12 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
+from . import _tables as T
 from . import covariance as CV
-from . import fidelity as FD
 from ._lib import check, ptr, stream_ptr
-from .energy import INT_EXACT
+from ._tables import INT_EXACT
 
 __all__ = ["sort_columns", "midranks", "spearman", "cdf_distance", "univariate_fidelity", "CdfDistance", "UnivariateFidelity", "INT_EXACT"]
-
-_MAX_ROWS = 2 ** 31 - 1
-_MAX_ROWS_RANKS = 2 ** 30 - 1
-
 
 class CdfDistance(NamedTuple):
     ks: torch.Tensor       # (d,) float64: ks_num / (n_a n_b)
@@ -81,14 +77,6 @@ class UnivariateFidelity(NamedTuple):
     floor: Optional["UnivariateFidelity"]
 
 
-def _check_rows(dx, name, what, ranks):
-    if dx[0] > _MAX_ROWS:
-        raise ValueError(f"{what}: {name}: {dx[0]} rows; at most 2^31 - 1 are sorted")
-    if ranks and dx[0] > _MAX_ROWS_RANKS:
-        raise ValueError(f"{what}: {name}: {dx[0]} rows; the doubled midranks are int32: at most 2^30 - 1 rows")
-    return dx
-
-
 def _check_spearman(dx, name, what):
     if 2 * dx[0] > INT_EXACT:
         raise ValueError(f"{what}: {name}: int32 values beyond 2^24 in magnitude: the doubled midranks reach 2 n = {2 * dx[0]} and "
@@ -102,7 +90,7 @@ def _sort(x, dx, want_ranks):
     out = torch.empty((d, n), dtype=x.dtype, device=x.device)
     ranks = torch.empty((n, d), dtype=torch.int32, device=x.device) if want_ranks else None
     ws = torch.empty(int(lib.d3p_sort_columns_workspace(n, d, 1 if want_ranks else 0)), dtype=torch.uint8, device=x.device)
-    check(lib.d3p_sort_columns(stream_ptr(), ptr(x), 0 if x.dtype == torch.float32 else 1, ld, n, d, ptr(out), n, ptr(ranks), d, ptr(ws),
+    check(lib.d3p_sort_columns(stream_ptr(), ptr(x), T.dtype_code(x), ld, n, d, ptr(out), n, ptr(ranks), d, ptr(ws),
                                int(ws.numel())))
     return out, ranks
 
@@ -116,7 +104,7 @@ def _cdf(sa, sb):
     at = torch.empty(d, dtype=sa.dtype, device=dev)
     w1 = torch.empty(d, dtype=torch.float64, device=dev)
     ws = torch.empty(int(lib.d3p_column_cdf_distance_workspace(n_a, n_b, d)), dtype=torch.uint8, device=dev)
-    check(lib.d3p_column_cdf_distance(stream_ptr(), ptr(sa), n_a, n_a, ptr(sb), n_b, n_b, 0 if sa.dtype == torch.float32 else 1, d, ptr(num),
+    check(lib.d3p_column_cdf_distance(stream_ptr(), ptr(sa), n_a, n_a, ptr(sb), n_b, n_b, T.dtype_code(sa), d, ptr(num),
                                       ptr(at), ptr(w1), ptr(ws), int(ws.numel())))
     ks = torch.where(num < 0, torch.full_like(w1, float("nan")), num.to(torch.float64) / float(n_a * n_b))
     return CdfDistance(ks, at, w1, n_a, n_b, num)
@@ -125,20 +113,16 @@ def _cdf(sa, sb):
 def sort_columns(x):
     """Every column of ``x`` sorted over all rows (module docstring): a ``(d, n)`` tensor of ``x``'s dtype on its device."""
     what = "sort_columns"
-    dx = _check_rows(FD._check_table(x, "x", what), "x", what, False)
-    FD._check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
+    dx = T.check_rows(T.check_table(x, "x", what), "x", what, False)
+    with T.on_device((("x", x),), what):
         return _sort(x, dx, False)[0]
 
 
 def midranks(x):
     """The doubled midranks of every column of ``x`` (module docstring): ``(n, d)`` int32 on the table's device."""
     what = "midranks"
-    dx = _check_rows(FD._check_table(x, "x", what), "x", what, True)
-    FD._check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
+    dx = T.check_rows(T.check_table(x, "x", what), "x", what, True)
+    with T.on_device((("x", x),), what):
         return _sort(x, dx, True)[1]
 
 
@@ -149,11 +133,9 @@ def _rank_m2(ranks):
 def spearman(x):
     """The ``(d, d)`` float64 Spearman rank correlation matrix of the columns of ``x`` (module docstring)."""
     what = "spearman"
-    dx = _check_rows(FD._check_table(x, "x", what), "x", what, True)
+    dx = T.check_rows(T.check_table(x, "x", what), "x", what, True)
     _check_spearman(dx, "x", what)
-    FD._check_devices((("x", x),), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(x.device):
+    with T.on_device((("x", x),), what):
         return CV._corr(_rank_m2(_sort(x, dx, True)[1]))
 
 
@@ -161,12 +143,10 @@ def cdf_distance(a, b):
     """The two-sample KS statistic and the 1-Wasserstein distance per column of the tables ``a`` and ``b`` (module docstring): a
     ``CdfDistance`` on the tables' device.  These are functions of the PRIVATE tables and are not covered by the accountant."""
     what = "cdf_distance"
-    da, db = FD._check_pair(a, b, ("a", "b"), what)
-    _check_rows(da, "a", what, False)
-    _check_rows(db, "b", what, False)
-    FD._check_devices((("a", a), ("b", b)), what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(a.device):
+    da, db = T.check_pair(a, b, ("a", "b"), what)
+    T.check_rows(da, "a", what, False)
+    T.check_rows(db, "b", what, False)
+    with T.on_device((("a", a), ("b", b)), what):
         return _cdf(_sort(a, da, False)[0], _sort(b, db, False)[0])
 
 
@@ -191,19 +171,10 @@ def _report(sr, rho_r, ss, rho_s, top):
     scaled = torch.where(iqr > 0, dist.w1 / iqr, torch.full_like(iqr, float("nan")))
     w = torch.topk(torch.nan_to_num(dist.ks, nan=-1.0), min(top, d)) if top else None
     worst_c = tuple((i, float(dist.ks[i])) for i in w.indices.tolist()) if w is not None else ()
-    diff = (rho_s - rho_r).abs()
-    iu = torch.triu_indices(d, d, offset=1, device=diff.device)
-    vals = diff[iu[0], iu[1]]
-    ok = ~torch.isnan(vals)
-    kept = vals[ok]
-    worst_p = ()
-    if top and kept.numel():
-        w2 = torch.topk(kept, min(top, kept.numel()))
-        at = ok.nonzero().flatten()[w2.indices]
-        worst_p = tuple(((int(iu[0][a]), int(iu[1][a])), float(v)) for a, v in zip(at.tolist(), w2.values.tolist()))
+    kept, n_skipped, worst_p = T.worst_pairs((rho_s - rho_r).abs(), top)
     nan = float("nan")
     return UnivariateFidelity(dist.ks, dist.w1, scaled, worst_c, float(kept.mean()) if kept.numel() else nan,
-                              float(kept.max()) if kept.numel() else nan, worst_p, int((~ok).sum()), int(sr.shape[1]), int(ss.shape[1]), d, None)
+                              float(kept.max()) if kept.numel() else nan, worst_p, n_skipped, int(sr.shape[1]), int(ss.shape[1]), d, None)
 
 
 def univariate_fidelity(real, synthetic, holdout=None, top=5):
@@ -211,19 +182,13 @@ def univariate_fidelity(real, synthetic, holdout=None, top=5):
     ``holdout``, the noise floor that the holdout scores against ``real`` (module docstring): a ``UnivariateFidelity``.  These are
     functions of the PRIVATE tables and are not covered by the accountant."""
     what = "univariate_fidelity"
-    dr, ds = FD._check_pair(real, synthetic, ("real", "synthetic"), what)
-    tables = [("real", real, dr), ("synthetic", synthetic, ds)]
-    if holdout is not None:
-        dh, _ = FD._check_pair(holdout, real, ("holdout", "real"), what)
-        tables.append(("holdout", holdout, dh))
+    tables = T.check_group(real, synthetic, holdout, ("real", "synthetic", "holdout"), what)
     for name, _, dx in tables:
-        _check_rows(dx, name, what, True)
+        T.check_rows(dx, name, what, True)
         _check_spearman(dx, name, what)
     if isinstance(top, bool) or not isinstance(top, int) or top < 0:
         raise ValueError(f"{what}: top must be a non-negative int")
-    FD._check_devices([(name, t) for name, t, _ in tables], what)
-    _lib.require_device()   # (every check above runs without a device)
-    with torch.cuda.device(real.device):
+    with T.on_device(tables, what):
         sorted_rho = []
         for _, t, dx in tables:
             s, ranks = _sort(t, dx, True)
